@@ -21,10 +21,13 @@ all-gather (ncclAllGather called from C behind the C-ABI, include/vkr_slab_excha
 frame delivers all slabs to all ranks and a scatter kernel reassembles the frame - all inside
 the timed region, overlapped with the shading of the next frame.  The value at N = 1 is the
 plain single-GPU pass (no exchange), so the per-N values of one workload are comparable.
-Every run also measures BASELINE config 4 (3840x2160, 8 spp, 8 lights: the configuration
-BASELINE.json tiles over 8 GPUs) as a second workload and attaches it as "secondary" to the
-JSON line (--no-secondary to skip).  --scaling weak / --exchange none keep the round-1 mode
-(frame height x N, slabs stay where they are) as an option.
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit,
+ms_per_step, ...); --dump-outputs DIR also writes the frame of the last timed step as DIR/<name>.npy.
+Everything else moves behind --full: the CPU baseline and parity against the oracle, the other
+arithmetic modes, the roofline (kernel alone, HBM counters of a profiled child run), the extra
+1920x1080 workloads and, as "secondary", BASELINE config 4 (3840x2160, 8 spp, 8 lights: the
+configuration BASELINE.json tiles over 8 GPUs; --no-secondary to skip).  --scaling weak /
+--exchange none keep the round-1 mode (frame height x N, slabs stay where they are) as an option.
 
 PyTorch is plumbing here: device selection, the stream, the process group used for the
 rendezvous token, barriers and the max over ranks of the timing.
@@ -95,6 +98,10 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true", help="do not measure roofline.traffic in this run (two short rocprofv3 --pmc passes around a child run of the headline workload); the committed passes of profiles/pmc_traffic.json are used instead")
     ap.add_argument("--force-distributed", action="store_true", help="run the N > 1 code path (slab layout, exchange) even with one rank")
     ap.add_argument("--details", default=None, help="where the full record of the run goes (default gpurun_out/bench_details.json); the printed line is the short one")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: CPU baseline and parity, other arithmetic modes, roofline and per-kernel figures, "
+                                                          "the frame read back every step, extra workloads, BASELINE config 4 as secondary, the N > 1 exchange diagnostics (the --no-* options below select among them); "
+                                                          "a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the frame the last timed step computed as DIR/<name>.npy (float32; a fixed seeded sample of its pixels if it exceeds 64 MB)")
     ap.add_argument("--dry-line", default=None, metavar="RECORD", help="no GPU work: print the short line for the full record of an earlier run (a details file, or a file whose last line is a record)")
     ap.add_argument("--dry-launch", action="store_true", help="no GPU work: the ranks join a gloo process group, exchange a token, print one JSON line and leave (checks the launch path of --gpus N)")
     args = ap.parse_args()
@@ -116,6 +123,21 @@ def main():
 
     job = Job(args)
     result = run_workload(job, args.config, "primary")
+    if args.full:
+        measure_beside_the_headline(job, result)
+    # the library reports like the reference does (printf): every rank flushes C stdio before rank 0
+    # prints, so that the JSON line is the last line of the job's output
+    ctypes.CDLL(None).fflush(None)
+    job.barrier()
+    if job.rank == 0:
+        details_path = write_details(result, args.details) if (args.full or args.details) else None
+        print(json.dumps(short_line(result, details_path), separators=(",", ":")), flush=True)
+    job.close()
+
+
+def measure_beside_the_headline(job, result):
+    """--full: the other workloads and diagnostics, attached to the headline's record"""
+    args = job.args
     customised = bool(args.width or args.height or args.spp)
     if not args.no_extra and args.config == 3 and not customised and job.world == 1:
         # the other 1920x1080 shapes the contract names, on the same clock: north_star's target and BASELINE config 2
@@ -143,14 +165,6 @@ def main():
         second = run_workload(job, 4, "secondary")
         keep = ("value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "scaling", "config", "shadow_rays_per_frame", "Mrays_per_s", "light_shafts", "stages", "scaling_parity", "setup", "roofline", "traversal")
         result["secondary"] = {k: second[k] for k in keep if k in second}
-    # the library reports like the reference does (printf): every rank flushes C stdio before rank 0
-    # prints, so that the JSON line is the last line of the job's output
-    ctypes.CDLL(None).fflush(None)
-    job.barrier()
-    if job.rank == 0:
-        details_path = write_details(result, args.details)
-        print(json.dumps(short_line(result, details_path), separators=(",", ":")), flush=True)
-    job.close()
 
 
 if __name__ == "__main__":

@@ -30,11 +30,11 @@ for W in $WORKLOADS; do
 	# that "per dispatch" is per frame
 	unset VKR_BAND_COUNT; [ "$CFG" = "4" ] && export VKR_BAND_COUNT=1
 	# the bench command itself (default steps / warm-up, three frames in flight) ...
-	[ $FULL = 1 ] && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_trace -o trace -- python $R/bench.py --config $CFG $QUIET > ${P}_trace.log 2>&1
+	[ $FULL = 1 ] && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_trace -o trace -- python $R/bench.py --full --config $CFG $QUIET > ${P}_trace.log 2>&1
 	# ... and with one frame at a time: every kernel alone on the GPU
 	SERIAL="--steps 200 --warmup 50"; [ "$CFG" = "4" ] && SERIAL="--steps 12 --warmup 3"; [ "$SCENE" = "large" ] && SERIAL="--steps 60 --warmup 10"
-	timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_serial -o trace -- python $R/bench.py --config $CFG $QUIET --frames-in-flight 1 $SERIAL > ${P}_serial.log 2>&1
-	B="python $R/bench.py --config $CFG $QUIET $STEPS"
+	timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_serial -o trace -- python $R/bench.py --full --config $CFG $QUIET --frames-in-flight 1 $SERIAL > ${P}_serial.log 2>&1
+	B="python $R/bench.py --full --config $CFG $QUIET $STEPS"
 	timeout 150 rocprofv3 --kernel-trace $FILTER --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU -d ${P}_pmc1 -o pmc -- $B > ${P}_pmc1.log 2>&1
 	timeout 150 rocprofv3 --kernel-trace $FILTER --pmc SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_THREAD_CYCLES_VALU SQ_INSTS_FLAT SQ_INSTS_LDS SQ_ACTIVE_INST_SCA GRBM_GUI_ACTIVE -d ${P}_pmc2 -o pmc -- $B > ${P}_pmc2.log 2>&1
 	timeout 150 rocprofv3 --kernel-trace $FILTER --pmc FETCH_SIZE GRBM_GUI_ACTIVE -d ${P}_pmc3 -o pmc -- $B > ${P}_pmc3.log 2>&1
@@ -45,7 +45,7 @@ for W in $WORKLOADS; do
 	[ $FULL = 1 ] && timeout 150 rocprofv3 --kernel-trace $FILTER --pmc SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT64 SQ_INSTS_SMEM -d ${P}_pmc7 -o pmc -- $B > ${P}_pmc7.log 2>&1
 	# the bench line itself, un-profiled, for the record
 	unset VKR_BAND_COUNT
-	timeout 300 python $R/bench.py --config $CFG --scene $SCENE --mode $MODE --no-secondary --no-extra --no-other-modes --details ${P}_bench_details.json > ${P}_bench.json 2> ${P}_bench.err
+	timeout 300 python $R/bench.py --full --config $CFG --scene $SCENE --mode $MODE --no-secondary --no-extra --no-other-modes --details ${P}_bench_details.json > ${P}_bench.json 2> ${P}_bench.err
 done
 # (raw traces are large: the summaries need the statistics and the counter files only)
 find $O -name "*kernel_trace.csv" -size +3M -delete

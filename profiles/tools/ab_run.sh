@@ -5,7 +5,7 @@ set -u
 TAG=$1; LIBS=$2; ARGS=${3:---no-secondary --no-cpu-baseline}
 O=gpurun_out/$TAG; mkdir -p $O
 for L in $LIBS; do
-	VKR_SHADING_LIBRARY=$PWD/vulkan_renderer_amd/libvkr_$L.so timeout 300 python bench.py $ARGS > $O/ab_$L.json 2> $O/ab_$L.err
+	VKR_SHADING_LIBRARY=$PWD/vulkan_renderer_amd/libvkr_$L.so timeout 300 python bench.py --full $ARGS > $O/ab_$L.json 2> $O/ab_$L.err
 	python - <<P
 import json
 try:

@@ -7,7 +7,7 @@ export VKR_SHADING_LIBRARY=$(pwd)/vulkan_renderer_amd/libvkr_mini_$LIB.so
 for CASE in "large:--config 3 --scene large" "target:--config target"; do
 	NAME=${CASE%%:*}; ARGS=${CASE#*:}
 	for SHAFTS in 0 1; do
-		VKR_LIGHT_SHAFTS=$SHAFTS timeout 300 python bench.py $ARGS --no-secondary --no-extra --no-other-modes --no-cpu-baseline > $O/${NAME}_$SHAFTS.json 2> $O/${NAME}_$SHAFTS.err
+		VKR_LIGHT_SHAFTS=$SHAFTS timeout 300 python bench.py --full $ARGS --no-secondary --no-extra --no-other-modes --no-cpu-baseline > $O/${NAME}_$SHAFTS.json 2> $O/${NAME}_$SHAFTS.err
 		python - <<PY
 import json
 try:

@@ -1,7 +1,7 @@
 # Memory-pipeline counters of the trace kernel (config 3).  Run on the GPU box:
 #   gpurun -- 'bash profiles/tools/pmc_mem.sh'
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
-B="python $R/bench.py --config ${CFG:-3} --steps 4 --warmup 2 --no-cpu-baseline"
+B="python $R/bench.py --full --config ${CFG:-3} --steps 4 --warmup 2 --no-cpu-baseline"
 F="--kernel-include-regex ${KERNEL:-trace_shadow_rays} --output-format csv"
 i=0
 for set in "TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum GRBM_GUI_ACTIVE" \

@@ -1,7 +1,7 @@
 # Instruction mix of the shading kernel (no rays): FMA / MUL / ADD / TRANS / INT / CVT
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
 for mode in ${MODES:-exact fast}; do
-	B="python $R/bench.py --config ${CFG:-3} --steps 3 --warmup 1 --no-cpu-baseline --no-rays --mode $mode"
+	B="python $R/bench.py --full --config ${CFG:-3} --steps 3 --warmup 1 --no-cpu-baseline --no-rays --mode $mode"
 	timeout 90 rocprofv3 --kernel-trace --kernel-include-regex shade_pixels --output-format csv --pmc SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_SALU -d /tmp/pm_$mode -o pmc -- $B > /tmp/pm_$mode.log 2>&1 || echo "failed $mode"
 	python - <<PY
 import csv, glob, collections

@@ -3,7 +3,7 @@
 # Counters in their own passes (never combined with other trace domains), one workload per pass.
 export TMPDIR=/tmp; R=${GRAFT_REPO_ROOT:-$(pwd)}; cd /tmp
 OUT=$R/${OUT:-gpurun_out/pmc_scene}; mkdir -p $OUT
-B="python $R/bench.py --config ${CFG:-3} --scene ${SCENE:-bench} --steps 4 --warmup 2 --prewarm-frames 8 --no-cpu-baseline --no-secondary --no-extra --no-other-modes $EXTRA"
+B="python $R/bench.py --full --config ${CFG:-3} --scene ${SCENE:-bench} --steps 4 --warmup 2 --prewarm-frames 8 --no-cpu-baseline --no-secondary --no-extra --no-other-modes $EXTRA"
 F="--kernel-include-regex ${KERNEL:-trace_shadow_rays|shade_pixels|light_shafts|resolve_shadow} --output-format csv"
 i=0
 for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU" \

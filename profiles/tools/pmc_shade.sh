@@ -1,6 +1,6 @@
 # Front-end counters of the shading kernel.  gpurun -- 'CFG=3 bash profiles/tools/pmc_shade.sh'
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
-B="python $R/bench.py --config ${CFG:-3} --steps 4 --warmup 2 --no-cpu-baseline ${EXTRA:-}"
+B="python $R/bench.py --full --config ${CFG:-3} --steps 4 --warmup 2 --no-cpu-baseline ${EXTRA:-}"
 F="--kernel-include-regex ${KERNEL:-shade_pixels} --output-format csv"
 i=0
 for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \

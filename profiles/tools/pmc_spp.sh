@@ -2,7 +2,7 @@
 # instructions per pixel = fixed + lights * (prepare + spp * per_sample_pair)
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
 for spp in 1 2 4 8; do
-	B="python $R/bench.py --config ${CFG:-3} --steps 3 --warmup 1 --no-cpu-baseline --no-rays --spp $spp"
+	B="python $R/bench.py --full --config ${CFG:-3} --steps 3 --warmup 1 --no-cpu-baseline --no-rays --spp $spp"
 	timeout 90 rocprofv3 --kernel-trace --kernel-include-regex shade_pixels --output-format csv --pmc SQ_INSTS_VALU SQ_WAVES -d /tmp/ps_$spp -o pmc -- $B > /tmp/ps_$spp.log 2>&1 || echo "failed $spp"
 	python - <<PY
 import csv, glob, collections

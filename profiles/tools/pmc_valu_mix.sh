@@ -11,7 +11,7 @@ cd /tmp
 rocprofv3 --list-avail > $O/avail.txt 2>&1
 FILTER="--kernel-include-regex shade_pixels|trace_shadow_rays|resolve_shadow --output-format csv"
 for CFG in ${CONFIGS:-3}; do
-	B="python $R/bench.py --config $CFG --steps 6 --warmup 2 --prewarm-frames 8 --no-cpu-baseline --no-secondary ${BENCH_ARGS:-}"
+	B="python $R/bench.py --full --config $CFG --steps 6 --warmup 2 --prewarm-frames 8 --no-cpu-baseline --no-secondary ${BENCH_ARGS:-}"
 	timeout 150 rocprofv3 --kernel-trace $FILTER --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 -d $O/cfg${CFG}_mix1 -o pmc -- $B > $O/cfg${CFG}_mix1.log 2>&1
 	timeout 150 rocprofv3 --kernel-trace $FILTER --pmc SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_ADD_F16 SQ_INSTS_VALU_INT64 SQ_INSTS_SALU SQ_INSTS_SMEM -d $O/cfg${CFG}_mix2 -o pmc -- $B > $O/cfg${CFG}_mix2.log 2>&1
 	timeout 150 rocprofv3 --kernel-trace $FILTER --pmc SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $O/cfg${CFG}_mix3 -o pmc -- $B > $O/cfg${CFG}_mix3.log 2>&1

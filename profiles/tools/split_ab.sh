@@ -3,7 +3,7 @@ O=gpurun_out/r05l; mkdir -p $O
 export VKR_SHADING_LIBRARY=$(pwd)/vulkan_renderer_amd/libvkr_mini_split.so
 for SPLIT in 1 0; do
   for SCENE in large bench; do
-    VKR_BVH_SPLIT_TRIANGLES=$SPLIT timeout 300 python bench.py --scene $SCENE --config 3 --no-extra --no-secondary --no-other-modes --steps 100 --warmup 10 > $O/${SCENE}_split$SPLIT.json 2> $O/${SCENE}_split$SPLIT.err
+    VKR_BVH_SPLIT_TRIANGLES=$SPLIT timeout 300 python bench.py --full --scene $SCENE --config 3 --no-extra --no-secondary --no-other-modes --steps 100 --warmup 10 > $O/${SCENE}_split$SPLIT.json 2> $O/${SCENE}_split$SPLIT.err
     python - <<PY
 import json
 try:

@@ -114,7 +114,7 @@ def test_bench_launches_two_ranks_by_itself_on_one_gpu(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "VKR_BENCH_SELF_LAUNCHED")}
     env.update({"VKR_BENCH_DEVICE": "0", "VKR_BENCH_BACKEND": "gloo"})
-    done = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--prewarm-frames", "24", "--prewarm-seconds", "0.2",
+    done = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "12", "--warmup", "3", "--prewarm-frames", "24", "--prewarm-seconds", "0.2",
                            "--no-secondary", "--no-cpu-baseline", "--no-extra", "--ltc-resolution", "16"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert done.returncode == 0, done.stdout[-1500:] + done.stderr[-1500:]
     lines = [json.loads(line) for line in done.stdout.splitlines() if line.startswith("{")]

@@ -9,6 +9,7 @@ import time
 import numpy as np
 
 from .common import ROOT, algorithmic_bytes_per_pixel
+from .outputs import timed_outputs, write_outputs
 from .parity import band_parity, cpu_baseline_and_parity
 from .roofline import build_roofline
 
@@ -151,15 +152,37 @@ def run_workload(job, config, role, scene=None, exchange_format=None):
     elapsed = job.max_over_ranks(time.perf_counter() - t0)
     ms_per_step = elapsed / steps * 1e3
     value = total_pixels * sample_count / (elapsed / steps) / 1e6
+    if primary and rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, timed_outputs(r, exchange, slab))
+    pipelined = bool(r.app.shading_pass.last_frame_in_flight)
+    bands_per_frame = int(r.app.shading_pass.last_band_count)
+    frames_in_flight = int(r.app.shading_pass.last_frame_in_flight) if pipelined else 1
+    config_record = {"workload": "BASELINE config %s: %dx%d, %d spp per technique, %d polygonal light(s), %s + %s, %s, %s arithmetic"
+                                 % ("%s%s" % (config, "" if scene == "bench" else " on the large scene"), width, height, sample_count, light_count, settings["sampling_strategies"], settings["polygon_technique"],
+                                    ("shadow rays through the %s BVH (%s)" % ("four-wide" if (structure.wide_nodes and not args.binary_traversal and not args.inline_rays) else "binary",
+                                                                              renderer.BVH_BUILDER_NAME[int(structure.builder)])) if settings["trace_shadow_rays"] else "no shadow rays", args.mode),
+                     "width": width, "height": height, "spp": sample_count, "lights": light_count, "techniques": techniques,
+                     "parallelism": ("tiles %dx%d round-robin over %d rank(s), %s" % (args.tile_size, args.tile_size, world,
+                                     ("RCCL all-gather of %s slabs (ncclAllGather from C, in place) %s inside the timed region, overlapped with the next frame" % (exchange, "+ scatter per frame" if args.assemble == "every-frame" else "per frame, un-tiled when read")) if exchange != "none" else "every rank keeps its slab of the frame (no data-path collective)")) if distributed else "one GPU, whole frame",
+                     "scene": scene, "scene_triangles": int(r.app.scene.mesh.triangle_count), "scene_materials": int(r.app.scene.materials.material_count), "ltc_resolution": int(r.app.ltc_table.roughness_count),
+                     "arithmetic": args.mode, "bands_per_frame": bands_per_frame, "frames_in_flight": frames_in_flight}
+    headline = {
+        "metric": "Msamples/s (pixels x spp / s), shading pass", "value": round(value, 3), "unit": "Msamples/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": args.scaling if world > 1 else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": config_record, "prewarm_frames": prewarm, "host_issue_ms_per_step": round(issue_seconds / steps * 1e3, 4)}
+    if not args.full:
+        # a plain run: the headline figure and nothing that needs more GPU work (everything below comes with --full)
+        if exchange != "none":
+            r.destroy_exchange()
+        r.close()
+        return headline
 
     # ---- what the timed region looked like from the inside ---------------------------------------
     timed_frames = max(1, min(steps // max(timing_stride, 1), 256))
     overlapped_kernel_ms = r.shading_kernel_ms(timed_frames)
     period_ms = r.frame_period_ms(max(1, timed_frames - 1))
     launch_ms = r.dispatch_ms(timed_frames)
-    pipelined = bool(r.app.shading_pass.last_frame_in_flight)
-    bands_per_frame = int(r.app.shading_pass.last_band_count)
-    frames_in_flight = int(r.app.shading_pass.last_frame_in_flight) if pipelined else 1
     rays = r.last_ray_count()
     shafts = r.light_shaft_statistics()
     # The reference's protocol is the median of at least 100 frame times (src/frame_timer.c:24,47-72, main.c:1958-1959).  A
@@ -305,9 +328,7 @@ def run_workload(job, config, role, scene=None, exchange_format=None):
                               pass_alone_ms=pass_alone_ms, shaft_alone_ms=shaft_alone_ms, shafts=shafts, frames_in_flight=frames_in_flight, pass_ms=pass_ms, overlapped_kernel_ms=overlapped_kernel_ms,
                               ms_per_step=ms_per_step, distributed=distributed)
     shaded_fraction = float(job.max_over_ranks(shaded / max(own_visibility.size, 1))) if distributed else shaded / max(own_visibility.size, 1)
-    result = {
-        "metric": "Msamples/s (pixels x spp / s), shading pass", "value": round(value, 3), "unit": "Msamples/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_per_step, 4),
+    result = dict(headline, **{
         "median_frame_period_ms": round(median_ms, 4) if median_ms else None, "median_over_frames": median_frames, "median_window_frames": window if median_ms else None,
         "value_from_median": round(total_pixels * sample_count / (median_ms * 1e-3) / 1e6, 3) if median_ms else None,
         "latency_ms": round(float(np.mean(pass_alone_ms)), 4) if pass_alone_ms else None,
@@ -315,17 +336,6 @@ def run_workload(job, config, role, scene=None, exchange_format=None):
         "shaded_fraction": round(shaded_fraction, 4), "value_shaded_only": round(value * shaded_fraction, 3),
         "value_note": "value = W x H x spp / time over ALL pixels of the frame (SURVEY.md 8d), background included, with config.frames_in_flight frames queued like the reference's frame queue (main.h:374-390); latency_ms / value_single_frame = one frame at a time (roofline.pass_alone_ms); value_shaded_only counts the pixels that see geometry"
                       + ("; median_frame_period_ms = median over windows of median_window_frames frames - a multiple of the frames in flight, which finish in bursts - of the time between the ends of the window's first and last frame, per frame (the reference's protocol: median of >= 100 frame times, src/frame_timer.c:47-72)" if median_ms else "; the median of frame periods is reported from 100 steps on"),
-        "higher_is_better": True, "scaling": args.scaling if world > 1 else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE config %s: %dx%d, %d spp per technique, %d polygonal light(s), %s + %s, %s, %s arithmetic"
-                               % ("%s%s" % (config, "" if scene == "bench" else " on the large scene"), width, height, sample_count, light_count, settings["sampling_strategies"], settings["polygon_technique"],
-                                  ("shadow rays through the %s BVH (%s)" % ("four-wide" if (structure.wide_nodes and not args.binary_traversal and not args.inline_rays) else "binary",
-                                                                            renderer.BVH_BUILDER_NAME[int(structure.builder)])) if settings["trace_shadow_rays"] else "no shadow rays", args.mode),
-                   "width": width, "height": height, "spp": sample_count, "lights": light_count, "techniques": techniques,
-                   "parallelism": ("tiles %dx%d round-robin over %d rank(s), %s" % (args.tile_size, args.tile_size, world,
-                                   ("RCCL all-gather of %s slabs (ncclAllGather from C, in place) %s inside the timed region, overlapped with the next frame" % (exchange, "+ scatter per frame" if args.assemble == "every-frame" else "per frame, un-tiled when read")) if exchange != "none" else "every rank keeps its slab of the frame (no data-path collective)")) if distributed else "one GPU, whole frame",
-                   "scene": scene, "scene_triangles": int(r.app.scene.mesh.triangle_count), "scene_materials": int(r.app.scene.materials.material_count), "ltc_resolution": int(r.app.ltc_table.roughness_count),
-                   "arithmetic": args.mode, "bands_per_frame": bands_per_frame, "frames_in_flight": frames_in_flight},
-        "prewarm_frames": prewarm, "host_issue_ms_per_step": round(issue_seconds / steps * 1e3, 4),
         "shadow_rays_per_frame": rays, "Mrays_per_s": round(rays / (ms_per_step * 1e-3) / 1e6, 2) if rays else 0.0,
         "light_shafts": {"patch_light_pairs": shafts["pairs"], "clear_pairs": shafts["clear_pairs"], "clear_fraction": round(shafts["clear_pairs"] / max(shafts["pairs"], 1), 4), "occluder_list_pairs": shafts["list_pairs"], "triangles_per_occluder_list": round(shafts["listed_triangles"] / max(shafts["list_pairs"], 1), 2),
                          "not_clear": shafts["not_clear"], "work": shafts["work"],
@@ -336,7 +346,7 @@ def run_workload(job, config, role, scene=None, exchange_format=None):
                   "readback_ms": round(readback_ms, 3), "pageable_readback_ms": round(pageable_readback_ms, 3), "upload_ms": round(upload_ms, 3),
                   "note": "untimed set-up, once per scene (load = parse .vks / LTC fits / noise + copies to the device); visibility_pass_ms = primary visibility per frame (mean of 4 launches after the first, host clock around a synchronised device), first_visibility_pass_ms includes one-time costs; readback = RGBA32F frame into pinned staging (begin_read_back + end_read_back, nothing else running), pageable_readback = read_back_radiance() into pageable memory, upload = a visibility buffer from the host; with_readback (top level) = frames per second when EVERY frame goes to the host while the next ones render; never part of value"},
         "roofline": roofline,
-    }
+    })
     if with_readback:
         result["with_readback"] = with_readback
     if stages:
