@@ -74,6 +74,7 @@ def lib():
         L.oracle_set_math_mode.argtypes = [C.c_int]
         L.oracle_encode_srgb8.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.oracle_encode_half_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int]
+        L.oracle_srgb8_code_starts.argtypes = [C.c_void_p]
         L.oracle_bvh_build.restype = C.c_void_p
         L.oracle_bvh_build.argtypes = [C.c_void_p, C.c_uint64, fp, fp]
         L.oracle_bvh_destroy.argtypes = [C.c_void_p]
@@ -309,6 +310,14 @@ def encode_srgb8(rgba):
     out = np.zeros(a.shape[:-1] + (4,), np.uint8)
     lib().oracle_encode_srgb8(a.ctypes.data, out.ctypes.data, a.size // 4)
     return out
+
+
+def srgb8_code_starts():
+    """-> (status, starts): starts[c] is the bit pattern (uint32) of the first float in [0, 1] that encode_srgb8
+    turns into code c; status 0 means the code never decreases over [0, 1] and every code occurs"""
+    starts = np.zeros(256, np.uint32)
+    status = lib().oracle_srgb8_code_starts(starts.ctypes.data)
+    return int(status), starts
 
 
 def encode_half_bits(rgba, frame_bits, output_linear_rgb=False):

@@ -128,6 +128,9 @@ void oracle_set_ray_log(int on);
 /* Output encodings of the reference (shading_pass.frag.glsl:871-892) */
 void oracle_encode_srgb8(const float* rgba, uint8_t* out_rgba8, uint64_t pixel_count);
 void oracle_encode_half_bits(const float* rgba, uint8_t* out_rgba8, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb);
+/* bits of the first float in [0, 1] of each sRGB8 code of oracle_encode_srgb8 (a scan of all 2^30 + 1 floats);
+   nonzero if the code decreases anywhere in [0, 1] or some code never occurs */
+int oracle_srgb8_code_starts(uint32_t starts[256]);
 
 /* BVH over the de-quantised triangle soup (contract: reference scene.c:176-187
  * for de-quantisation, shading_pass.frag.glsl:120-138 for the ray query) */

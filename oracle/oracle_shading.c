@@ -2203,14 +2203,58 @@ static float srgb_to_linear(float c) {
 	c = g_clamp(c, 0.0f, 1.0f);
 	return (c <= 0.04045f) ? ((1.0f / 12.92f) * c) : l_powf(fmaf(c, 1.0f / 1.055f, 0.055f / 1.055f), 2.4f);
 }
-/* UNORM8 store of the render target: round to nearest */
+/* UNORM8 store of the render target: round to nearest.  NaN passes g_clamp, and converting it to an integer is
+   undefined in C: it is defined here as code 0 (what the kernels' conversion gives) */
 static uint8_t to_unorm8(float c) {
 	c = g_clamp(c, 0.0f, 1.0f);
+	if (c != c) return 0;
 	return (uint8_t) (c * 255.0f + 0.5f);
 }
 
+/* starts[c] = bits of the first float in [0, 1] whose sRGB8 code to_unorm8(linear_to_srgb(v)) is c: every float of
+   [0, 1] is evaluated.  Returns nonzero if the code ever decreases (then the starts do not describe the function).
+   Chunks of 2^20 floats in parallel, each noting where a code begins inside it; the chunks are joined in order. */
+#define SRGB_SCAN_CHUNK (1u << 20)
+int oracle_srgb8_code_starts(uint32_t starts[256]) {
+	const uint32_t end = 0x3F800001u, chunk_count = (end + SRGB_SCAN_CHUNK - 1) / SRGB_SCAN_CHUNK;
+	uint32_t* local = (uint32_t*) malloc((size_t) chunk_count * 258 * sizeof(uint32_t));
+	if (!local) return 2;
+	int decreasing = 0;
+#pragma omp parallel for schedule(dynamic, 8) reduction(|: decreasing)
+	for (int64_t k = 0; k < (int64_t) chunk_count; ++k) {
+		/* per chunk: the first float of each code that begins in it, then its first and last code */
+		uint32_t* mine = local + (size_t) k * 258;
+		for (int c = 0; c != 256; ++c) mine[c] = 0xFFFFFFFFu;
+		uint32_t first = (uint32_t) k * SRGB_SCAN_CHUNK, last = first + SRGB_SCAN_CHUNK;
+		if (last > end) last = end;
+		uint32_t previous = to_unorm8(linear_to_srgb(u2f(first)));
+		mine[previous] = first;
+		mine[256] = previous;
+		for (uint32_t bits = first + 1; bits != last; ++bits) {
+			uint32_t code = to_unorm8(linear_to_srgb(u2f(bits)));
+			if (code == previous) continue;
+			if (code < previous) decreasing = 1;
+			if (mine[code] == 0xFFFFFFFFu) mine[code] = bits;
+			previous = code;
+		}
+		mine[257] = previous;
+	}
+	for (int c = 0; c != 256; ++c) starts[c] = 0xFFFFFFFFu;
+	for (uint32_t k = 0; k != chunk_count; ++k) {
+		const uint32_t* mine = local + (size_t) k * 258;
+		if (k != 0 && mine[256] < local[(size_t) (k - 1) * 258 + 257]) decreasing = 1;
+		for (int c = 0; c != 256; ++c)
+			if (mine[c] < starts[c]) starts[c] = mine[c];
+	}
+	free(local);
+	for (int c = 0; c != 256; ++c)
+		if (starts[c] == 0xFFFFFFFFu) return 1;
+	return decreasing;
+}
+
 void oracle_encode_srgb8(const float* rgba, uint8_t* out, uint64_t pixel_count) {
-	for (uint64_t i = 0; i != pixel_count; ++i) {
+#pragma omp parallel for schedule(static)
+	for (int64_t i = 0; i < (int64_t) pixel_count; ++i) {
 		for (int c = 0; c != 3; ++c) out[4 * i + c] = to_unorm8(linear_to_srgb(rgba[4 * i + c]));
 		out[4 * i + 3] = to_unorm8(rgba[4 * i + 3]);
 	}
@@ -2242,7 +2286,8 @@ static uint16_t float_to_half(float f) {
 
 void oracle_encode_half_bits(const float* rgba, uint8_t* out, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb) {
 	uint32_t mask = (frame_bits == 1) ? 0xFF : 0xFF00, shift = (frame_bits == 1) ? 0 : 8;
-	for (uint64_t i = 0; i != pixel_count; ++i) {
+#pragma omp parallel for schedule(static)
+	for (int64_t i = 0; i < (int64_t) pixel_count; ++i) {
 		uint32_t h0 = (uint32_t) float_to_half(rgba[4 * i + 0]) | ((uint32_t) float_to_half(rgba[4 * i + 1]) << 16);
 		uint32_t h1 = (uint32_t) float_to_half(rgba[4 * i + 2]) | ((uint32_t) float_to_half(rgba[4 * i + 3]) << 16);
 		float c[3] = {

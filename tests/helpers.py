@@ -120,3 +120,72 @@ def classify_outliers(a, b, a_without_rays=None, b_without_rays=None, threshold=
         "guard_pixels_in_a": int(is_guard_pixel(a).sum()), "guard_pixels_in_b": int(is_guard_pixel(b).sum()),
         "other_coordinates": [tuple(int(v) for v in yx) for yx in np.argwhere(other)[:8]],
     }
+
+
+# ---- inputs and expectations of the output encoders (tests/test_output_encoding.py, test_gpu_output_encoding.py) ----
+
+# quiet and signalling NaNs, several payloads; the same with the sign bit
+NAN_BITS = [0x7FC00000, 0x7FC00001, 0x7FFFFFFF, 0x7F800001, 0x7FBFFFFF, 0x7FA5A5A5, 0x7FD00000, 0x7F802000]
+NAN_BITS = NAN_BITS + [b | 0x80000000 for b in NAN_BITS]
+FLOAT_MAX_BITS = 0x7F7FFFFF
+
+
+def from_bits(bits):
+    return np.asarray(bits, np.uint64).astype(np.uint32).view(np.float32)
+
+
+def unorm8(x):
+    """The UNORM8 store of the reference in float32: clamp to [0, 1], x * 255 + 0.5, truncated; NaN gives 0."""
+    x = np.asarray(x, np.float32)
+    x = np.where(np.isnan(x), np.float32(0), np.minimum(np.maximum(x, np.float32(0)), np.float32(1))).astype(np.float32)
+    return (x * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+
+
+def srgb8_by_starts(x, starts):
+    """sRGB8 code of every float of x by the oracle's code table (oracle.srgb8_code_starts()): the last code whose
+    start x has reached in [0, 1]; NaN and everything <= 0 give 0, everything >= 1 gives 255."""
+    x = np.asarray(x, np.float32).ravel()
+    inside = np.where((x > 0) & (x < 1), x, np.float32(0)).view(np.uint32)
+    code = np.searchsorted(starts, inside, side="right") - 1
+    return np.where(x >= 1, 255, np.where((x > 0) & (x < 1), code, 0)).astype(np.uint8)
+
+
+def codes_of_range(starts, first, count):
+    """sRGB8 codes of the floats with the consecutive bit patterns first ... first + count - 1 (from [0, 1];
+    whatever lies beyond 1.0 is taken as 1.0): code c for every position from its start on."""
+    edges = np.append(np.clip(starts.astype(np.int64) - first, 0, count), count)
+    return np.repeat(np.arange(256, dtype=np.uint8), np.diff(edges))
+
+
+def encoder_specials():
+    """Floats where an sRGB8 / UNORM8 encoder goes wrong: signed zeros, denormals, negatives, values above 1, the
+    extremes, +-inf and NaNs, 1 - ulp and 1 + ulp."""
+    bits = [0x00000000, 0x80000000, 0x00000001, 0x00000002, 0x003FFFFF, 0x00400000, 0x007FFFFF, 0x00800000, 0x00800001,
+            0x80000001, 0x807FFFFF, 0x80800000, 0xBF800000, 0xBF000000, 0xB3800000, 0xFF7FFFFF, 0xFF800000,
+            0x3F7FFFFF, 0x3F800000, 0x3F800001, 0x3FC00000, 0x40000000, 0x4B000000, 0x7149F2CA, FLOAT_MAX_BITS, 0x7F800000,
+            0x3B4D2E1C, 0x3B4D2E1B, 0x3B4D2E1D]  # (0.0031308f and its neighbours: the two branches of linear_to_srgb)
+    return from_bits(bits + NAN_BITS)
+
+
+def half_test_values():
+    """Inputs of the half-float split (frame_bits 1 and 2) without the sweeps: every finite half and +-inf; for every
+    two adjacent halves (65504 and the 65536 it would round up to included) the float midpoint and its two float
+    neighbours, so that ties to even are exercised in every binade; NaNs of both signs with several payloads."""
+    halves = np.arange(0, 0x7C01, dtype=np.uint16).view(np.float16).astype(np.float32)  # +0 ... 65504, +inf
+    ladder = np.append(halves[:-1], np.float32(65536)).astype(np.float64)
+    middle = ((ladder[:-1] + ladder[1:]) / 2).astype(np.float32)  # (12 significant bits: exact in float32)
+    around = np.concatenate([middle, np.nextafter(middle, np.float32(-np.inf)), np.nextafter(middle, np.float32(np.inf))])
+    positive = np.concatenate([halves, around])
+    return np.concatenate([positive, -positive, from_bits(NAN_BITS)]).astype(np.float32)
+
+
+# the exhaustive ranges of the half split, as first and last bit pattern: every float of the binades 2^-26 ... 2^-15
+# (rounding into and inside the half subnormal range, 2^-14 is the smallest normal half), every float from 65504 to
+# 2^17 (rounding to 65504 and overflow to infinity)
+HALF_SWEEPS = [(0x32800000, 0x38800000), (0x477FE000, 0x48000000)]
+
+
+def half_sweep_chunks(chunk=1 << 24):
+    for first, last in HALF_SWEEPS:
+        for start in range(first, last + 1, chunk):
+            yield np.arange(start, min(start + chunk, last + 1), dtype=np.uint32).view(np.float32)

@@ -120,8 +120,8 @@ def test_srgb_and_half_encodings(golden_dataset, frames):
     r.close()
     # the sRGB frame of the reference shader (variant with OUTPUT_LINEAR_RGB=0), stored as UNORM8
     expected = (np.clip(frames["cfg1_srgb_encoded"], 0, 1) * 255.0 + 0.5).astype(np.uint8)
-    assert np.abs(srgb[..., :3].astype(int) - expected[..., :3].astype(int)).max() <= 1
-    assert (srgb[..., :3] != expected[..., :3]).mean() < 0.01
+    assert np.array_equal(srgb[..., :3], expected[..., :3])
+    assert (srgb[..., 3] == 255).all()
     assert np.array_equal(low, oracle.encode_half_bits(image, 1, False))
     assert np.array_equal(high, oracle.encode_half_bits(image, 2, True))
     # reassembling the two bytes gives the half-float image (reference main.c:1700-1710)

@@ -1941,19 +1941,31 @@ __device__ __forceinline__ uint32_t to_unorm8(float v) {
 	return (uint32_t) (v * 255.0f + 0.5f);
 }
 
-// to_unorm8(linear_to_srgb(v)) without the pow: the code is the number of thresholds
-// T[c] = srgb_to_linear((c - 0.5) / 255), c = 1 ... 255, that v has reached.  A hardware
-// log2 / exp2 estimate is off by less than one code; the two neighbouring thresholds settle it.
+// to_unorm8(linear_to_srgb(v)) without the pow: the code is the number of starts T[c], c = 1 ... 255, that v has
+// reached, where T[c] is the first float whose code is c in the oracle's float arithmetic (oracle_srgb8_code_starts:
+// gm_powf, no contraction, a code that never decreases over [0, 1]).  The starts lie up to 4 ulps away from the
+// exact thresholds srgb_to_linear((c - 0.5) / 255), on either side, at 171 of the 255 codes.  A hardware log2 / exp2
+// estimate is off by less than one code; the two neighbouring starts settle it.
 // (Three powf per pixel made the encode kernel as expensive as tracing config 2's shadow rays.)
 __device__ float g_srgb_code_thresholds[257];
 
+// the oracle's to_unorm8(linear_to_srgb(v)) for v in [0, 1], operation for operation (this file: -ffp-contract=off)
+__device__ uint32_t srgb_code_by_powf(float v) {
+	float s = (v <= 0.0031308f) ? (12.92f * v) : (1.055f * gm_powf(v, 1.0f / 2.4f) - 0.055f);
+	s = gclamp(s, 0.0f, 1.0f);
+	return (uint32_t) (s * 255.0f + 0.5f);
+}
+
+// thread c bisects the float bit patterns of [0, 1] for the start of code c (30 steps of one powf)
 __global__ void k_fill_srgb_code_thresholds() {
 	uint32_t c = threadIdx.x;
-	double x = ((double) c - 0.5) / 255.0;
-	double linear = (x <= 0.04045) ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4);
-	float t = (float) linear;
-	if ((double) t < linear) t = __uint_as_float(__float_as_uint(t) + 1u);
-	g_srgb_code_thresholds[c] = (c == 0) ? 0.0f : t;
+	uint32_t below = 0u, start = 0x3F800000u;  // code(below) < c <= code(start)
+	while (c != 0 && start - below > 1u) {
+		uint32_t middle = below + (start - below) / 2u;
+		if (srgb_code_by_powf(__uint_as_float(middle)) >= c) start = middle;
+		else below = middle;
+	}
+	g_srgb_code_thresholds[c] = (c == 0) ? 0.0f : __uint_as_float(start);
 	if (c == 0) g_srgb_code_thresholds[256] = __builtin_inff();
 }
 
@@ -1962,8 +1974,8 @@ __global__ void k_fill_srgb_code_thresholds() {
 // content does not depend on who fills it: no host-side state, filling it again is harmless).
 extern "C" int vkr_fill_device_tables(void* stream) {
 	k_fill_srgb_code_thresholds<<<1, 256, 0, (hipStream_t) stream>>>();
-	if (hip_failed(hipGetLastError(), "filling the sRGB thresholds")) return 1;
-	return hip_failed(hipStreamSynchronize((hipStream_t) stream), "filling the sRGB thresholds");
+	if (hip_failed(hipGetLastError(), "filling the sRGB code starts")) return 1;
+	return hip_failed(hipStreamSynchronize((hipStream_t) stream), "filling the sRGB code starts");
 }
 
 __device__ __forceinline__ uint32_t srgb_code(float v) {
@@ -1975,6 +1987,13 @@ __device__ __forceinline__ uint32_t srgb_code(float v) {
 	return c;
 }
 
+// packHalf2x16 of one channel.  Which NaN a NaN becomes is left to the implementation by the reference; it is pinned
+// to the oracle's sign | 0x7E00 here (v_cvt_f16_f32 keeps the payload's upper bits).
+__device__ __forceinline__ uint32_t half_bits(float x) {
+	uint32_t h = __half_as_ushort(__float2half_rn(x));
+	return (x != x) ? (((__float_as_uint(x) >> 16) & 0x8000u) | 0x7E00u) : h;
+}
+
 __device__ __forceinline__ uint32_t encode_pixel(float4 c, uint32_t frame_bits, int output_linear_rgb) {
 	uint32_t r, g, b, a;
 	if (frame_bits == 0) {
@@ -1984,8 +2003,8 @@ __device__ __forceinline__ uint32_t encode_pixel(float4 c, uint32_t frame_bits, 
 	}
 	else {
 		uint32_t mask = (frame_bits == 1) ? 0xFF : 0xFF00, shift = (frame_bits == 1) ? 0 : 8;
-		uint32_t h0 = (uint32_t) __half_as_ushort(__float2half_rn(c.x)) | ((uint32_t) __half_as_ushort(__float2half_rn(c.y)) << 16);
-		uint32_t h1 = (uint32_t) __half_as_ushort(__float2half_rn(c.z));
+		uint32_t h0 = half_bits(c.x) | (half_bits(c.y) << 16);
+		uint32_t h1 = half_bits(c.z);
 		float v[3] = {
 			(float) ((h0 & mask) >> shift) * (1.0f / 255.0f),
 			(float) ((((h0 & 0xFFFF0000u) >> 16) & mask) >> shift) * (1.0f / 255.0f),
