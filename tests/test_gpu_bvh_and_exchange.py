@@ -256,49 +256,6 @@ def test_a_reader_of_the_target_is_ordered_between_two_frames_in_flight(dataset,
     r.close()
 
 
-@pytest.mark.parametrize("frames_in_flight", [2, 3])
-def test_tracing_and_resolve_on_a_high_priority_stream_give_the_same_frames(dataset, frames_in_flight, monkeypatch):
-    """VKR_TRACE_STREAM_PRIORITY=high moves the tracing and the resolve kernel of every launch to a
-    stream of the highest priority behind an event of the shading kernel (an experiment of round 3 that
-    did not pay, profiles/r03_trace.md: the knob stays).  The event hand-overs must order the three
-    kernels of a frame and the frames among each other exactly as the single stream does: the same
-    frames, bit for bit, with frames following each other without synchronisation, also in bands and
-    with a reader of the target in between; and the frame period must not fall apart."""
-    def frames(r):
-        out = []
-        for exposure in (1.0, 3.0, 1.0, 5.0, 3.0):
-            r.app.render_settings.exposure_factor = exposure
-            r.render()
-            out.append(r.read_radiance())
-        for _ in range(40):
-            r.render()
-        r.finish_frames()
-        periods = r.frame_period_ms(16)
-        return out, r.last_ray_count(), float(np.median(periods)) if periods else 0.0
-
-    # (ray counts are compared between runs with different histories: every shaft pair walked in every frame)
-    monkeypatch.setenv("VKR_SHAFT_REST", "0")
-    r, _ = render_config(dataset, 3, 512, 288, frames_in_flight=frames_in_flight)
-    expected, rays, period = frames(r)
-    r.close()
-    assert not np.array_equal(expected[0], expected[1])
-    monkeypatch.setenv("VKR_TRACE_STREAM_PRIORITY", "high")
-    for band_count in (0, 3):
-        r = renderer.Renderer(frames_in_flight=frames_in_flight, band_count=band_count)
-        renderer.setup_config(r, 3, dataset, width=512, height=288, acceleration_structure="sah_device")
-        r.create_targets()
-        r.create_pass()
-        r.render_visibility()
-        got, got_rays, got_period = frames(r)
-        r.close()
-        assert got_rays == rays
-        for a, b in zip(got, expected):
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), band_count
-        # (two more event hand-overs per launch: measured +50 % on frames of 0.13 ms, nothing on long ones)
-        if band_count == 0 and period > 0.0:
-            assert got_period <= 3.0 * period + 0.2, (period, got_period)
-
-
 @pytest.mark.parametrize("slab_format", ["rgba32f", "rgb8"])
 def test_slab_exchange_with_one_rank_reproduces_the_frame(dataset, slab_format):
     """The whole multi-GPU chain on one GPU: slab layout, ncclAllGather through the C-ABI (a

@@ -27,14 +27,8 @@
 #define VKR_MATH_MODE 0
 #endif
 #define VKR_FAST_MATH (VKR_MATH_MODE == 1)
-// glibc's functions in both IEEE modes ...
+// glibc's functions in both IEEE modes (mode 0 keeps the polynomial arctangent: VKR_MATH_MODE == 2 below)
 #define VKR_LIBM_MATH (VKR_MATH_MODE != 1)
-// ... except those named here, which keep their polynomial forms - bit 0: arctangent (that is what
-// mode 0 is), bit 1: inversesqrt, bit 2: acos / sincos (profiling aids, profiles/tools/ab_build.sh:
-// pricing the functions one by one is how mode 0 got its definition)
-#ifndef VKR_LIBM_EXCEPT
-#define VKR_LIBM_EXCEPT (VKR_MATH_MODE == 0 ? 1 : 0)
-#endif
 
 #define VKR_DEV __device__ __forceinline__
 
@@ -157,29 +151,17 @@ VKR_DEV float square_root_unguarded(float x) {
 // reciprocal estimate: fails for the two significands whose root has a significand of all ones, 1 - 2^-24
 // and 1 - 2^-23 - the squared length of every vector that is normalised a second time, 637 872 pixels of a
 // config-3 frame.)
-// VKR_SQRT_VARIANT (A/B knob, profiles/r03x/): 0 the selection above; 1 the same with the special cases
-// spelled out by a second selection (until round 3); 2 the hardware root corrected once with half of
-// v_rsq_f32(x) as the reciprocal and a v_cmp_class_f32 selection for everything that is not a positive normal number
-#ifndef VKR_SQRT_VARIANT
-#define VKR_SQRT_VARIANT 0
-#endif
+// (profiles/r03x/ has the measurements of (a) and of a second selection that spelled out the special cases.)
 VKR_DEV float square_root(float x) {
 #if VKR_FAST_MATH
 	return __builtin_amdgcn_sqrtf(x);
 #elif VKR_IEEE_DIVISION_EVERYWHERE
 	// (the compiler's correctly rounded root - the default of hipcc; __fsqrt_rn() is NOT: it maps to the native instruction)
 	return __builtin_sqrtf(x);
-#elif VKR_SQRT_VARIANT == 2
-	float estimate = __builtin_amdgcn_sqrtf(x);
-	float s = fmaf(fmaf(-estimate, estimate, x), 0.5f * __builtin_amdgcn_rsqf(x), estimate);
-	return __builtin_amdgcn_classf(x, 0x100) ? s : estimate;
-#elif VKR_SQRT_VARIANT == 1
-	float s = square_root_unguarded(x);
-	return (x == 0.0f || x == __builtin_inff()) ? x : s;
 #else
 	// (+-0, +inf, NaN and negative arguments come out as IEEE wants them without a selection:
 	// square_root_unguarded says why, tests/test_gpu_arithmetic.py checks it.  Until round 3 a
-	// selection spelled it out, variant 1: the same frame time, 1.586 against 1.587 ms.)
+	// selection spelled it out: the same frame time, 1.586 against 1.587 ms.)
 	return square_root_unguarded(x);
 #endif
 }
@@ -188,73 +170,20 @@ VKR_DEV float square_root(float x) {
 VKR_DEV float inverse_square_root_ieee(float x) {
 #if VKR_IEEE_DIVISION_EVERYWHERE
 	return __fdiv_rn(1.0f, __builtin_sqrtf(x));
-#elif VKR_SQRT_VARIANT == 2
-	return divide(1.0f, square_root(x));
 #else
 	return divide(1.0f, square_root_unguarded(x));
 #endif
 }
-// GLSL inversesqrt.  Exact mode: integer seed, two Newton steps and one in residual form
-// (<= 0.85 ulp), the same single-rounding operations as vkr_rsqrtf in oracle/oracle_math.h;
-// 12 instructions instead of the 28 of 1 / sqrt.
+// GLSL inversesqrt: 1 / sqrt in both IEEE modes, the hardware instruction in the fast mode
 VKR_DEV float rsqrt(float x) {
 #if VKR_FAST_MATH
 	return __builtin_amdgcn_rsqf(x);
-#elif VKR_LIBM_MATH && !(VKR_LIBM_EXCEPT & 2)
+#else
 	return inverse_square_root_ieee(x);
-#else
-	float hx = 0.5f * x;
-	float y = __uint_as_float(0x5F3759DFu - (__float_as_uint(x) >> 1));
-	float t = y * y;
-	y = y * fmaf(-hx, t, 1.5f);
-	t = y * y;
-	y = y * fmaf(-hx, t, 1.5f);
-	t = y * y;
-	y = fmaf(y, fmaf(-hx, t, 0.5f), y);
-	// zero, negative numbers, infinity and NaN keep their IEEE results (+-inf, NaN, 0, NaN), which
-	// the hardware instruction delivers exactly; the shaders lean on them.  (Denormal arguments
-	// would differ from the oracle's 1 / sqrt; sums of squares are zero or far above 1e-38.)
-	bool ordinary = x >= 1.17549435e-38f && x < __builtin_inff();
-	return ordinary ? y : __builtin_amdgcn_rsqf(x);
 #endif
 }
-
-// Hybrid arithmetic (VKR_FAST_SHADING, measured once in round 3: profiles/r03_hybrid.md): everything that
-// decides WHERE a sample goes - G-buffer decode, LTC matrices, clipping, polygon preparation, sector
-// search, the sampled direction, the ray - stays in the translation unit's IEEE arithmetic, so rays and
-// NaN-guard pixels are those of the exact frame; only the VALUE of a sample (BRDF, densities, MIS
-// weights) uses the approximate reciprocal / root instructions.
-#ifndef VKR_FAST_SHADING
-#define VKR_FAST_SHADING 0
-#endif
-VKR_DEV float value_divide(float a, float b) {
-#if VKR_FAST_SHADING
-	return a * __builtin_amdgcn_rcpf(b);
-#else
-	return divide(a, b);
-#endif
-}
-VKR_DEV float value_rcp(float x) {
-#if VKR_FAST_SHADING
-	return __builtin_amdgcn_rcpf(x);
-#else
-	return rcp(x);
-#endif
-}
-VKR_DEV float value_square_root(float x) {
-#if VKR_FAST_SHADING
-	return __builtin_amdgcn_sqrtf(x);
-#else
-	return square_root(x);
-#endif
-}
-VKR_DEV float value_rsqrt(float x) {
-#if VKR_FAST_SHADING
-	return __builtin_amdgcn_rsqf(x);
-#else
-	return rsqrt(x);
-#endif
-}
+// (Measured and removed, profiles/r03_hybrid.md: a hybrid arithmetic that took only the VALUE of a sample - BRDF,
+// densities, MIS weights - from the approximate reciprocal / root instructions.)
 
 VKR_DEV f3 normalize(f3 a) { return a * rsqrt(dot(a, a)); }
 VKR_DEV f2 normalize(f2 a) { return a * rsqrt(dot(a, a)); }
@@ -292,15 +221,12 @@ VKR_DEV f3 mul_transposed(const m43& m, f3 d) { return mk3(dot(m.c[0], d), dot(m
 
 namespace vkr {
 
-// VKR_ATAN_TABLE (on wherever glibc's arctangent is used, i.e. in the libm mode): its argument range is looked up in
+// In the libm mode, the one that uses glibc's arctangent, its argument range is looked up in
 // an LDS table of 81 rows (1.3 KB per workgroup, fill_atan_rows() at the start of the kernel) instead of found with
 // four compares and sixteen selects per call: gm_atanf_rows in glibc_math.h, equal to atanf for all 2^32 arguments
 // like gm_atanf.  4.5 % fewer instructions in the config-3 kernel: 1.676 -> 1.610 ms per frame; the V = 7 kernel of
 // config 4 loses one of its ten waves per CU to the table and still gains 3 % (profiles/r03k/atan_table.jsonl).
-#ifndef VKR_ATAN_TABLE
-#define VKR_ATAN_TABLE (VKR_LIBM_MATH && !(VKR_LIBM_EXCEPT & 1))
-#endif
-#if VKR_ATAN_TABLE
+#if VKR_MATH_MODE == 2
 VKR_DEV gm_atan_row_t* atan_rows() {
 	__shared__ gm_atan_row_t rows[GM_ATAN_ROW_COUNT];
 	return rows;
@@ -312,7 +238,6 @@ VKR_DEV void fill_atan_rows() {
 VKR_DEV float libm_arctangent(float t) { return gm_atanf_rows(t, atan_rows()); }
 #else
 VKR_DEV void fill_atan_rows() {}
-VKR_DEV float libm_arctangent(float t) { return gm_atanf(t); }
 #endif
 
 // ---- polynomial transcendentals (coefficients: oracle/tools/fit_math.py) -------
@@ -332,7 +257,7 @@ VKR_DEV float atan_unit(float z) {
 }
 
 VKR_DEV float arctan(float t) {
-#if VKR_LIBM_MATH && !(VKR_LIBM_EXCEPT & 1)
+#if VKR_MATH_MODE == 2
 	return libm_arctangent(t);
 #endif
 	float a = fabsf(t);
@@ -348,7 +273,7 @@ VKR_DEV float arctan(float t) {
 // instead of forming the quotient and then its reciprocal.  Operation by operation the mode-1
 // o_positive_atan_ratio of oracle/oracle_math.h (which documents the special cases).
 VKR_DEV float arctan_ratio_positive(float n, float d) {
-#if VKR_LIBM_MATH && !(VKR_LIBM_EXCEPT & 1)
+#if VKR_MATH_MODE == 2
 	// as the shader words it: the quotient, its arctangent, pi for a negative quotient
 	// (the quotient of an angle next to pi / 2 is as large as floats get)
 	float tangent = divide_full_range(n, d);
@@ -376,7 +301,7 @@ VKR_DEV float asin_tail(float z, float s) {
 
 // acos for arguments already clamped to [0, 1]
 VKR_DEV float arccos_unit(float x) {
-#if VKR_LIBM_MATH && !(VKR_LIBM_EXCEPT & 4)
+#if VKR_LIBM_MATH
 	return gm_acosf(x);
 #endif
 	if (x <= 0.5f) {
@@ -458,7 +383,7 @@ VKR_DEV float arctan2(float y, float x) {
 }
 
 VKR_DEV void sincos_poly(float x, float& out_sin, float& out_cos) {
-#if VKR_LIBM_MATH && !(VKR_LIBM_EXCEPT & 4)
+#if VKR_LIBM_MATH
 	gm_sincosf(x, &out_sin, &out_cos);
 	return;
 #endif

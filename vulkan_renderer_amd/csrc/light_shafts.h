@@ -56,34 +56,25 @@ constexpr uint32_t kShaftLights = 8;                          // lights whose sh
 constexpr uint32_t kShaftLightShift = 27;                     // an entry of the queues: node or triangle | light << 27
 constexpr uint32_t kShaftFrontier = 640;                      // inner nodes waiting (LDS); more -> not clear
 constexpr uint32_t kShaftLeaves = 320;                        // triangles waiting
-// Measured (profiles/r05n, r05o, r05p; config 3 / config 4, shaft kernel alone): test (iii) with all 64 shading positions
-// instead of the corners of their bounding box finds 0.2 % more clear pairs and costs 0.288 instead of 0.173 ms / 0.90
-// instead of 0.80 ms (VKR_SHAFT_ORIGIN_LOOP=1); batches of 16 or 8 triangles instead of 32 cost 0.35 / 0.39 ms, 64 the
+// Measured (profiles/r05n, r05o, r05p; config 3 / config 4, shaft kernel alone): the triangle's-plane test with all 64
+// shading positions instead of the corners of their bounding box finds 0.2 % more clear pairs and costs 0.288 instead of
+// 0.173 ms / 0.90 instead of 0.80 ms (removed since); batches of 16 or 8 triangles instead of 32 cost 0.35 / 0.39 ms, 64 the
 // same as 32; the whole per-light set-up computed by every lane alike instead of four lanes and a dozen wave-wide
 // reductions saves 4 % of the kernel alone but takes 126 instead of 79 registers, and the frame with three of them in
 // flight gets slower (1.441 vs 1.428 ms).  With the occluder lists (walks go on where they used to end; profiles/r06d):
 // the reductions over the rectangle's corners within a quad instead of the wave 0.241 -> 0.224 ms, and batches of 48 /
 // 64 triangles 0.212 / 0.210 ms.
-#ifndef VKR_SHAFT_ORIGIN_LOOP
-#define VKR_SHAFT_ORIGIN_LOOP 0
-#endif
-#ifndef VKR_SHAFT_LEAF_BATCH
-#define VKR_SHAFT_LEAF_BATCH 64
-#endif
-constexpr uint32_t kShaftLeafBatch = VKR_SHAFT_LEAF_BATCH;         // triangles that must wait before a batch of them is tested
+constexpr uint32_t kShaftLeafBatch = 64;                      // triangles that must wait before a batch of them is tested
 constexpr uint32_t kShaftMaxSteps = 40;                       // steps of 16 nodes (plus a fifth of it per light); more -> not clear (run-time knob VKR_SHAFT_MAX_STEPS)
 constexpr uint32_t kShaftSmallLaunchSteps = 12;               // the same for launches of less than 12 288 patches (shading_pass.hip)
 constexpr float kShaftDilation = 1.0f / 32.0f;
-// Measured and not adopted (profiles/r05h/): cutting every candidate triangle by all planes of the shaft (test (iii) below)
+// Measured and removed (profiles/r05h/): cutting every candidate triangle by all planes of the shaft as a third test
 // finds 7 % more clear pairs at config 3 (25.0 instead of 23.3 % of all pairs) but costs the kernel 17 registers and 300
 // bytes of scratch per lane: 1.459 instead of 1.414 ms per frame.
-#ifndef VKR_SHAFT_CLIPPING
-#define VKR_SHAFT_CLIPPING 0
-#endif
 // Occluder lists (above).  Measured (profiles/r05zg, frame period of config 3 / config 4 with kShaftListMax = 4, 6, 8, 12,
 // 16; none: 1.400 / 22.6 ms): 1.304 / 21.06, 1.240 / 20.15, 1.217 / 19.41, 1.187 / 19.01, 1.192 / 18.87 ms - a triangle
 // test costs a twelfth of what tracing the ray costs, and the walks that give up do so a little later.
-// (kShaftListMax, VKR_SHAFT_LIST: shading_kernel.h)
+// (kShaftListMax: shading_kernel.h)
 
 // what the walk needs to know about one (patch, light), wave-uniform, in LDS
 struct shaft_state {
@@ -115,9 +106,6 @@ enum { kShaftClear = 1, kShaftList = 2, kShaftNoPixels = 16, kShaftGeometry = 17
 constexpr uint32_t kShaftRestFrames = 7;
 
 struct shaft_patch {
-#if VKR_SHAFT_ORIGIN_LOOP
-	float origin[64][3];
-#endif
 	uint64_t valid;                     // lanes with a shading position
 	float centre[3], half[3], radius;   // bounding box of the positions (with margin), length of its half diagonal
 	// the patch's own plane if all its positions lie on one (within flat_tolerance): n unit, n . x = d
@@ -178,40 +166,6 @@ VKR_DEV bool shaft_triangle_harmless(const shaft_state& s, const shaft_patch& pa
 		float hc = s.flat_sign * (patch.flat_normal[0] * c.x + patch.flat_normal[1] * c.y + patch.flat_normal[2] * c.z - patch.flat_d);
 		if (fmaxf(ha, fmaxf(hb, hc)) <= margin) return true;
 	}
-#if VKR_SHAFT_CLIPPING
-	// (iii) what is left of the triangle inside ALL planes at once: nothing?  (A large triangle next to the narrow end
-	// of the shaft - the top of a box beside a patch on the floor - lies outside the shaft without lying outside any one
-	// of its planes.)  The triangle is cut by one plane after the other; planes are moved outwards by `margin` first.
-	{
-		constexpr int kMost = 12;
-		float x[2][kMost], y[2][kMost], z[2][kMost];
-		x[0][0] = a.x; y[0][0] = a.y; z[0][0] = a.z;
-		x[0][1] = b.x; y[0][1] = b.y; z[0][1] = b.z;
-		x[0][2] = c.x; y[0][2] = c.y; z[0][2] = c.z;
-		int count = 3, from = 0;
-		for (uint32_t k = 0; k != s.plane_count && count != 0 && count <= kMost - 2; ++k) {
-			float nx = s.plane[k][0], ny = s.plane[k][1], nz = s.plane[k][2], d = s.plane[k][3] + margin;
-			int to = from ^ 1, kept = 0;
-			float previous_x = x[from][count - 1], previous_y = y[from][count - 1], previous_z = z[from][count - 1];
-			float previous_distance = fmaf(nx, previous_x, fmaf(ny, previous_y, nz * previous_z)) - d;
-			for (int i = 0; i != count; ++i) {
-				float cx = x[from][i], cy = y[from][i], cz = z[from][i];
-				float distance = fmaf(nx, cx, fmaf(ny, cy, nz * cz)) - d;
-				if ((distance <= 0.0f) != (previous_distance <= 0.0f)) {
-					// the edge crosses the plane
-					float t = previous_distance / (previous_distance - distance);
-					x[to][kept] = fmaf(t, cx - previous_x, previous_x); y[to][kept] = fmaf(t, cy - previous_y, previous_y); z[to][kept] = fmaf(t, cz - previous_z, previous_z);
-					++kept;
-				}
-				if (distance <= 0.0f) { x[to][kept] = cx; y[to][kept] = cy; z[to][kept] = cz; ++kept; }
-				previous_x = cx; previous_y = cy; previous_z = cz; previous_distance = distance;
-			}
-			count = kept;
-			from = to;
-		}
-		if (count == 0) return true;
-	}
-#endif
 	// (ii) in general: the triangle's own plane separates it from the rays - the light's vertices and the first
 	// points of all rays on one side
 	f3 n = cross(b - a, c - a);
@@ -228,21 +182,9 @@ VKR_DEV bool shaft_triangle_harmless(const shaft_state& s, const shaft_patch& pa
 	if (h_max < 0.0f) { n = -n; float t = h_min; h_min = -h_max; h_max = -t; }
 	if (!(h_min > 4.0f * margin)) return false;
 	// lowest origin above the plane
-#if VKR_SHAFT_ORIGIN_LOOP
-	float g_min = 3.0e38f;
-	uint64_t lanes = patch.valid;
-	while (lanes) {
-		int j = __builtin_ctzll(lanes);
-		lanes &= lanes - 1;
-		float g = n.x * (patch.origin[j][0] - a.x) + n.y * (patch.origin[j][1] - a.y) + n.z * (patch.origin[j][2] - a.z);
-		g_min = fminf(g_min, g);
-	}
-	g_min -= margin;
-#else
 	// (the lowest corner of the positions' bounding box: never higher than the lowest position)
 	float g_min = n.x * (patch.centre[0] - a.x) + n.y * (patch.centre[1] - a.y) + n.z * (patch.centre[2] - a.z)
 		- (fabsf(n.x) * patch.half[0] + fabsf(n.y) * patch.half[1] + fabsf(n.z) * patch.half[2]) - margin;
-#endif
 	// the first point of a ray from height g: g + t_min n . u with n . u >= (h_min - g) / reach; grows with g
 	float first = g_min + 1.0e-3f * (h_min - g_min) / s.reach;
 	return g_min <= h_min && first > 2.0f * margin;
@@ -325,9 +267,6 @@ __global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const
 		face_normal = cross(t.e0, t.e1);
 		face_normal = face_normal * __builtin_amdgcn_rsqf(fmaxf(dot(face_normal, face_normal), 1.0e-38f));
 		face_d = dot(face_normal, t.pos[0]);
-#if VKR_SHAFT_ORIGIN_LOOP
-		patch.origin[lane][0] = position.x; patch.origin[lane][1] = position.y; patch.origin[lane][2] = position.z;
-#endif
 	}
 	const float big = 3.0e38f;
 	f3 lo = mk3(wave_min(shaded ? position.x : big), wave_min(shaded ? position.y : big), wave_min(shaded ? position.z : big));

@@ -111,9 +111,6 @@ struct shade_params {
 	// the table of the second prepared polygon of every shading workgroup, for the kernel variants that keep only one in
 	// LDS (psa_table_in_memory(V)): [workgroup of the launch][slot][thread] float2; NULL for all other variants
 	float2* psa_table_memory;
-	// 1: a wave's region of psa_table_memory is that of the hardware slot it runs in (hardware_wave_slot(), kWaveSlots regions),
-	// 0: that of its workgroup
-	uint32_t psa_table_by_wave_slot;
 	// error display (ERROR_INDEX of the reference; the two constants of error_to_color
 	// that the GLSL compiler folds: 10^4.99 and 20 / (5 log2 10), computed on the host)
 	uint32_t error_index;
@@ -148,47 +145,24 @@ constexpr bool is_deferred(int rays) { return rays == kRaysDeferred || rays == k
 // config 4 16.45 -> 15.90 - but the spills go through the L2 to the fabric: FETCH_SIZE + WRITE_SIZE of a config-3 launch
 // 0.20 -> 1.33 GB, of a config-4 frame 2 -> 25 GB.  3 % of time for six to twelve times the memory traffic: no.  (Five waves
 // lose outright, 1.255 ms; the one-technique kernels lose at four, config 2 0.139 -> 0.155.)
-#ifndef VKR_PSA_MEMORY_FROM
-#define VKR_PSA_MEMORY_FROM 6
-#endif
-constexpr bool psa_table_in_memory(int v) { return v >= VKR_PSA_MEMORY_FROM; }
+constexpr bool psa_table_in_memory(int v) { return v >= 6; }
 constexpr uint32_t psa_table_memory_bytes_per_workgroup(int v) { return (2u * (uint32_t) v + 1u) * 64u * 8u; }
-// Where a wave's table lies in that memory: in the region of its workgroup (the default), or - shade_params::
-// psa_table_by_wave_slot, VKR_PSA_TABLE_INDEX=slot - in the region of the HARDWARE SLOT the wave occupies, (XCD, shader engine,
-// shader array, CU, SIMD, wave slot) from HW_REG_XCC_ID and HW_REG_HW_ID, unique among the waves that are resident at any time
-// whatever kernel, stream or frame they belong to (check_hardware_wave_slots() of the C-ABI tests that on the device): one
-// buffer of kWaveSlots regions for the whole pass, written again and again by the waves that follow each other in a slot.  The
-// idea was that such a region stays in its XCD's L2; the counters say the table stores reach the fabric either way (config 4:
-// WRITE_SIZE 5.2 GB per frame with both schemes, profiles/r10o), so it is an option, not the default.
-constexpr uint32_t kWaveSlots = 1u << 17;
-VKR_DEV uint32_t hardware_wave_slot() {
-	// s_getreg_b32 simm16 = (size - 1) << 11 | offset << 6 | register: HW_REG_HW_ID = 4 (wave_id [3:0], simd_id [5:4], pipe_id [7:6],
-	// cu_id [11:8], sh_id [12], se_id [15:13]), HW_REG_XCC_ID = 20 (xcc_id [3:0])
-	uint32_t hw = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4);
-	uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
-	// (the pipe that dispatched the wave is not part of where it runs)
-	return ((xcc & 7u) << 14) | (((hw >> 8) & 0xFFu) << 6) | (hw & 0x3Fu);
-}
+// A wave's table lies in the region of its workgroup.  Measured and removed (profiles/r10o): regions by the hardware slot a
+// wave occupies, in one buffer for the whole pass, so that a region would stay in its XCD's L2; the table stores reached the
+// fabric either way (config 4: WRITE_SIZE 5.2 GB per frame with both schemes).
 // codes of the per-thread term stream written in deferred mode
 // (kCodePendingHiddenNaN: the value of the blocked term is not stored because it can only be NaN - every
 // estimator but the plain optimal MIS heuristic computes it as 0 x something, i.e. +-0 or NaN, and a NaN
 // in any channel sends the whole pixel to the shader's NaN guard, shading_pass.frag.glsl:861-864)
-// triangles on the occluder list of a (patch, light) pair (light_shafts.h); 0: no lists
-#ifndef VKR_SHAFT_LIST
-#define VKR_SHAFT_LIST 12
-#endif
-constexpr uint32_t kShaftListMax = VKR_SHAFT_LIST;
+// triangles on the occluder list of a (patch, light) pair (light_shafts.h)
+constexpr uint32_t kShaftListMax = 12;
 constexpr uint32_t kShaftListEntry = 12;  // floats of a list entry: p0, e1, e2, each padded to four
 // (In every arithmetic mode since round 6: the list test must be the tracing kernel's test to the bit, and the fast mode's
 // translation units contract a b + c into fused operations where the tracing kernel's do not - so the triangle test itself,
 // lbvh.h ray_triangle_edges, is compiled without contraction wherever it is compiled.)
-constexpr bool kUseShaftLists = kShaftListMax != 0u;
 // The final terms of a light that needs no ray are added up here instead of by the resolve kernel.  (In the fast mode the
 // term is made opaque before it is added: a product contracted into the sum would make the sum formed here differ from the one
 // the resolve kernel forms, and a frame would depend on whether the shaft test is on.)
-#ifndef VKR_SUM_FINAL_TERMS
-#define VKR_SUM_FINAL_TERMS 1
-#endif
 enum { kCodeEnd = 0, kCodePending = 1, kCodeVisible = 2, kCodePendingWithHidden = 3, kCodeEndOfLight = 4, kCodeFinal = 5, kCodePendingHiddenNaN = 6 };
 // Byte index of code `cursor` of thread `tid`: four consecutive codes of a thread share one 32-bit
 // word ([cursor / 4][thread] words), so that the resolve kernel fetches four codes per load and can
@@ -224,7 +198,7 @@ VKR_DEV float unorm16(uint32_t v) {
 
 // ---- noise (noise_utility.glsl:63-103) ---------------------------------------------
 
-// The texel of the NEXT fetch is requested as soon as the current one has been unpacked (VKR_NOISE_AHEAD):
+// The texel of the NEXT fetch is requested as soon as the current one has been unpacked :
 // a fetch is the one vector load of a sample, and it used to be waited for right where it was issued -
 // which, on this hardware, also means waiting for every store before it: loads and stores share the
 // vector-memory counter and complete out of order with each other, so the wait for a load with stores in
@@ -232,9 +206,6 @@ VKR_DEV float unorm16(uint32_t v) {
 // trip to the L2).  With the request a sample ahead and the wait pinned in front of the sample's own stores
 // (settle_noise(), called by accumulate()) both the load and the earlier stores have long completed
 // when the wave asks.  Two more live registers.
-#ifndef VKR_NOISE_AHEAD
-#define VKR_NOISE_AHEAD 1
-#endif
 struct noise_accessor {
 	float n0, n1, n2, n3;
 	uint32_t available, px, py, sample_index;
@@ -259,38 +230,26 @@ VKR_DEV noise_accessor make_noise_accessor(const shade_params& p, uint32_t px, u
 	a.n0 = a.n1 = a.n2 = a.n3 = 0.0f;
 	a.available = 0; a.px = px; a.py = py; a.sample_index = 0;
 	a.ahead_x = a.ahead_y = 0u;
-#if VKR_NOISE_AHEAD
 	uint2 texel = fetch_noise_texel(p, a);
 	a.ahead_x = texel.x; a.ahead_y = texel.y;
-#endif
 	return a;
 }
 
 // The requested texel has to have arrived from here on (an empty statement that "uses" its registers)
 VKR_DEV void settle_noise(noise_accessor& a) {
-#if VKR_NOISE_AHEAD
 	asm volatile("" : "+v"(a.ahead_x), "+v"(a.ahead_y));
-#else
-	(void) a;
-#endif
 }
 
 VKR_DEV f2 next_noise_2(const shade_params& p, noise_accessor& a) {
 	if (a.available <= 1) {
-#if VKR_NOISE_AHEAD
 		uint2 texel = make_uint2(a.ahead_x, a.ahead_y);
-#else
-		uint2 texel = fetch_noise_texel(p, a);
-#endif
 		a.n0 = unorm16(texel.x & 0xFFFF); a.n1 = unorm16(texel.x >> 16);
 		a.n2 = unorm16(texel.y & 0xFFFF); a.n3 = unorm16(texel.y >> 16);
 		a.available = 4;
 		++a.sample_index;
-#if VKR_NOISE_AHEAD
 		// (one texel beyond the last one a pixel uses: the coordinates wrap, the read is harmless)
 		uint2 ahead = fetch_noise_texel(p, a);
 		a.ahead_x = ahead.x; a.ahead_y = ahead.y;
-#endif
 	}
 	a.available -= 2;
 	f2 r = mk2(a.n0, a.n1);
@@ -621,7 +580,7 @@ VKR_DEV ltc_coefficients get_ltc_coefficients(const shade_params& p, float fresn
 VKR_DEV float evaluate_ltc_density(const ltc_coefficients& l, f3 dir_shading, float rcp_psa) {
 	f3 dc = shading_to_cosine(l, dir_shading);
 	float len_sq = dot(dc, dc);
-	float density = value_divide(gmax(0.0f, dc.z) * l.determinant, len_sq * len_sq);
+	float density = divide(gmax(0.0f, dc.z) * l.determinant, len_sq * len_sq);
 	return density * rcp_psa;
 }
 
@@ -636,7 +595,7 @@ VKR_DEV float schlick(float f0, float f90, float cos_theta) {
 template <bool DIFFUSE, bool SPECULAR>
 VKR_DEV f3 evaluate_brdf(const shading_data& d, f3 incoming) {
 	f3 half_sum = incoming + d.outgoing;
-	f3 half_vector = half_sum * value_rsqrt(dot(half_sum, half_sum));
+	f3 half_vector = half_sum * rsqrt(dot(half_sum, half_sum));
 	float lambert_incoming = dot(d.normal, incoming);
 	float outgoing_dot_half = dot(d.outgoing, half_vector);
 	f3 brdf = mk3(0.0f, 0.0f, 0.0f);
@@ -649,10 +608,10 @@ VKR_DEV f3 evaluate_brdf(const shading_data& d, f3 incoming) {
 		float normal_dot_half = dot(d.normal, half_vector);
 		float a2 = d.roughness * d.roughness;
 		float ggx = fmaf(fmaf(normal_dot_half, a2, -normal_dot_half), normal_dot_half, 1.0f);
-		ggx = value_divide(a2, ggx * ggx);
-		float masking = lambert_incoming * value_square_root(fmaf(fmaf(-d.lambert_outgoing, a2, d.lambert_outgoing), d.lambert_outgoing, a2));
-		float shadowing = d.lambert_outgoing * value_square_root(fmaf(fmaf(-lambert_incoming, a2, lambert_incoming), lambert_incoming, a2));
-		float smith = value_divide(0.5f, masking + shadowing);
+		ggx = divide(a2, ggx * ggx);
+		float masking = lambert_incoming * square_root(fmaf(fmaf(-d.lambert_outgoing, a2, d.lambert_outgoing), d.lambert_outgoing, a2));
+		float shadowing = d.lambert_outgoing * square_root(fmaf(fmaf(-lambert_incoming, a2, lambert_incoming), lambert_incoming, a2));
+		float smith = divide(0.5f, masking + shadowing);
 		float ct = gclamp(outgoing_dot_half, 0.0f, 1.0f);
 		float gs = ggx * smith;
 		brdf = brdf + mk3(gs * schlick(d.fresnel_0.x, 1.0f, ct), gs * schlick(d.fresnel_0.y, 1.0f, ct), gs * schlick(d.fresnel_0.z, 1.0f, ct));
@@ -1012,7 +971,6 @@ VKR_DEV void accumulate(pixel_context& ctx, f3& result, bool candidate, f3 visib
 		if (blocked) value = !hidden_matters ? mk3(0.0f, 0.0f, 0.0f) : (p.terms_hidden ? hidden_term : mk3(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")));
 		bool needs_ray = candidate && !arrives && !blocked && (hidden_matters || !all_zero(visible_term));
 		bool is_final = (!candidate || arrives || blocked) && !all_zero(value);
-#if VKR_SUM_FINAL_TERMS
 		if (ctx.light_clear && (ctx.final_state & 2u)) {
 			if (is_final) {
 #if VKR_FAST_MATH
@@ -1027,7 +985,6 @@ VKR_DEV void accumulate(pixel_context& ctx, f3& result, bool candidate, f3 visib
 				ctx.final_state = 0u;
 			}
 		}
-#endif
 		if ((needs_ray || is_final) && ctx.term_cursor < p.max_terms && ctx.code_cursor + 2 < p.max_codes) {
 			if (ctx.noise) settle_noise(*ctx.noise);
 			size_t code_index = code_slot(p.thread_count, ctx.code_cursor, ctx.tid);
@@ -1050,21 +1007,21 @@ VKR_DEV void accumulate(pixel_context& ctx, f3& result, bool candidate, f3 visib
 }
 
 VKR_DEV float mis_weight_over_density(int heuristic, float sampled, float other) {
-	if (heuristic == kMisBalance) return value_rcp(sampled + other);
-	if (heuristic == kMisPower) return value_divide(sampled, sampled * sampled + other * other);
+	if (heuristic == kMisBalance) return rcp(sampled + other);
+	if (heuristic == kMisPower) return divide(sampled, sampled * sampled + other * other);
 	return 0.0f;
 }
 
 VKR_DEV float mis_estimate_channel(int heuristic, float in, float s, float sd, float o, float od, float ve) {
 	if (heuristic == kMisWeighted) {
 		float weighted_sum = s * sd + o * od;
-		return value_divide(s * in, weighted_sum);
+		return divide(s * in, weighted_sum);
 	}
 	if (heuristic == kMisOptimalClamped || heuristic == kMisOptimal) {
-		float balance = value_rcp(sd + od);
+		float balance = rcp(sd + od);
 		float weighted_sum = s * sd + o * od;
 		if (heuristic == kMisOptimalClamped) {
-			float weighted = value_divide(s, weighted_sum);
+			float weighted = divide(s, weighted_sum);
 			float mixed = fmaf(-ve, balance, balance);
 			mixed = fmaf(ve, weighted, mixed);
 			return mixed * in;
@@ -1094,17 +1051,17 @@ VKR_DEV void mis_estimate_pair(int heuristic, f3 lit, f3 dark, f3 sw, float sd, 
 #pragma unroll
 		for (int c = 0; c != 3; ++c) {
 			float weighted_sum = s[c] * sd + o[c] * od;
-			ra[c] = value_divide(s[c] * a[c], weighted_sum);
-			rb[c] = value_divide(s[c] * b[c], weighted_sum);
+			ra[c] = divide(s[c] * a[c], weighted_sum);
+			rb[c] = divide(s[c] * b[c], weighted_sum);
 		}
 	}
 	else if (heuristic == kMisOptimalClamped || heuristic == kMisOptimal) {
-		float balance = value_rcp(sd + od);
+		float balance = rcp(sd + od);
 #pragma unroll
 		for (int c = 0; c != 3; ++c) {
 			float weighted_sum = s[c] * sd + o[c] * od;
 			if (heuristic == kMisOptimalClamped) {
-				float weighted = value_divide(s[c], weighted_sum);
+				float weighted = divide(s[c], weighted_sum);
 				float mixed = fmaf(-ve, balance, balance);
 				mixed = fmaf(ve, weighted, mixed);
 				ra[c] = mixed * a[c];
@@ -1574,10 +1531,8 @@ VKR_DEV f3 evaluate_light(pixel_context& ctx, const shading_data& sd, const ltc_
 	}
 	if constexpr (is_deferred(RAYS)) {
 		// close this light's run of terms; the resolve kernel scales by 1 / S and adds it
-#if VKR_SUM_FINAL_TERMS
 		if (ctx.light_clear && (ctx.final_state & 1u)) flush_final_sum(ctx);
 		ctx.final_state = 2u;
-#endif
 		if (ctx.light_has_terms && ctx.code_cursor + 1 < p.max_codes) {
 			if (ctx.noise) settle_noise(*ctx.noise);
 			p.codes[code_slot(p.thread_count, ctx.code_cursor, ctx.tid)] = (uint8_t) kCodeEndOfLight;
@@ -1642,13 +1597,10 @@ constexpr bool has_psa_tables(int strategy, int technique, int error) {
 	return strategy >= kStrategySeparately && (technique == kTechniquePsa || technique == kTechniquePsaBiased) && error != kErrorDiffuse && error != kErrorSpecular;
 }
 // (Rays traced inside the kernel bring the traversal's registers with them: those variants would spill.)
-// (waves per SIMD asked of the register allocator; VKR_SHADE_TABLE_WAVES for the kernels with polygon tables: the experiment above)
-#ifndef VKR_SHADE_TABLE_WAVES
-#define VKR_SHADE_TABLE_WAVES 3
-#endif
+// (waves per SIMD asked of the register allocator)
 constexpr int shade_min_workgroups(int strategy, int technique, int v, int rays, int error) {
 	return ((technique == kTechniquePsa || technique == kTechniquePsaBiased) && error != kErrorDiffuse && error != kErrorSpecular
-		&& v <= (has_psa_tables(strategy, technique, error) ? 7 : 6) && rays != kRaysInline) ? (has_psa_tables(strategy, technique, error) ? VKR_SHADE_TABLE_WAVES : 3) : 1;
+		&& v <= (has_psa_tables(strategy, technique, error) ? 7 : 6) && rays != kRaysInline) ? 3 : 1;
 }
 // bytes of dynamic LDS of a shading workgroup: the polygon tables
 constexpr uint32_t shade_lds_bytes(int strategy, int technique, int v, int error) {
@@ -1661,7 +1613,7 @@ __global__ void __launch_bounds__(kShadeThreads, shade_min_workgroups(STRATEGY, 
 	// of waiting for its block (mean resident waves per SIMD 2.3 -> see profiles/).  Workgroup b runs
 	// on XCD b % 8; the four patches of a block are the workgroups b, b + 8, b + 16, b + 24 of a
 	// group of 32, so they share that XCD's L2.
-	fill_atan_rows();  // (nothing unless VKR_ATAN_TABLE, device_math.h)
+	fill_atan_rows();  // (nothing outside the libm mode, device_math.h)
 	const uint32_t b = blockIdx.x;
 	const uint32_t local_block = ((b >> 5) << 3) | (b & 7u);
 	const uint32_t block = p.first_block + local_block;
@@ -1680,7 +1632,7 @@ __global__ void __launch_bounds__(kShadeThreads, shade_min_workgroups(STRATEGY, 
 	extern __shared__ float2 psa_tables[];
 	// (the wavefront buffers are indexed by the thread's number within this launch)
 	pixel_context ctx = {p, 0, local_block * 256u + thread, 0, 0, false, false, 0u, 0u, nullptr, queue, mk3(0.0f, 0.0f, 0.0f), 2u, kTables ? psa_tables + threadIdx.x : nullptr,
-		(kTables && psa_table_in_memory(V) && p.psa_table_memory) ? p.psa_table_memory + (size_t) (p.psa_table_by_wave_slot ? hardware_wave_slot() : b) * (kPsaTableSlots(V) * kPsaTableStride) + threadIdx.x : nullptr, nullptr};
+		(kTables && psa_table_in_memory(V) && p.psa_table_memory) ? p.psa_table_memory + (size_t) b * (kPsaTableSlots(V) * kPsaTableStride) + threadIdx.x : nullptr, nullptr};
 	if constexpr (RAYS == kRaysDeferredBlocks) {
 		// (the waves of a workgroup never touch each other's entry: no barrier)
 		lds_state_word* state = ray_block_state();
@@ -1724,7 +1676,7 @@ __global__ void __launch_bounds__(kShadeThreads, shade_min_workgroups(STRATEGY, 
 				if constexpr (is_deferred(RAYS)) {
 					// the verdict of the shaft walk (light_shafts.h): 1 clear, 2 | n << 8 a list of n triangles, else trace
 					uint32_t verdict = p.shaft_clear != nullptr ? *(constant_uint_pointer) (uintptr_t) (p.shaft_clear + ((size_t) b * p.light_count + i)) : 0u;
-					bool listed = kUseShaftLists && (verdict & 0xFFu) == 2u && p.shaft_lists != nullptr;
+					bool listed = (verdict & 0xFFu) == 2u && p.shaft_lists != nullptr;
 					ctx.light_clear = verdict == 1u || listed;
 					ctx.list_count = listed ? ((verdict >> 8) & 0x1Fu) : 0u;
 					ctx.list = p.shaft_lists + ((size_t) b * p.light_count + i) * (kShaftListMax * kShaftListEntry);

@@ -173,11 +173,6 @@ static void free_wavefront_buffers(wavefront_buffers* w) {
 // device->stream.
 struct frame_context {
 	wavefront_buffers buffers;
-	// VKR_TRACE_STREAM_PRIORITY=high (experiment of round 3, profiles/r03_trace.md): the tracing and the
-	// resolve kernel of a launch run on a stream of their own with the highest priority, behind an event
-	// that marks the end of the shading kernel
-	hipStream_t trace_stream;
-	hipEvent_t shaded;
 	hipEvent_t done;  // recorded behind the last kernel of the frame
 	bool recorded;    // `done` has been recorded: the next frame's resolve is ordered behind it
 	// what the context's most recent launches wrote their output to (a ring of the last eight): a launch only has to be ordered
@@ -201,19 +196,14 @@ struct frame_pipeline {
 	// part of the light shafts' tag
 	uint32_t inputs_generation;
 	// the polygon tables in device memory (wavefront_buffers::psa_table_memory) of the frames without wavefront rays, which
-	// own no context (and, with VKR_PSA_TABLE_INDEX=slot, of all launches of the pass: regions by hardware wave slot)
+	// own no context
 	wavefront_buffers device_stream_buffers;
 	uint32_t next;            // context of the next pipelined frame
 	uint32_t last;            // context of the most recent frame
 	uint32_t depth;           // frames in flight of the most recent pipelined frame
 	// tuning / test knobs, read from the environment once when the pipeline is created:
 	// VKR_WIDE_STACK_LDS (stack entries per lane that trace_shadow_rays_wide keeps in LDS: tests shrink
-	// it to drive rays through the spill path), VKR_LEAF_BATCH (lanes that must have a triangle waiting
-	// before a wave tests triangles), VKR_REFILL_THRESHOLD (binary walk)
-	// VKR_TRACE_WAVES: persistent waves per SIMD of the tracing kernels (1 ... 8; 0: eight where a lane
-	// queues eight rays or more, four otherwise - measured at config 2, whose 0.9 M rays are a batch or
-	// two per wave: 0.129 -> 0.121 ms per frame)
-	// VKR_TRACE_SINGLE_WAVES: 0 / 1 overrides the choice of the tracing kernel's workgroup size (2: automatic)
+	// it to drive rays through the spill path)
 	// VKR_WAVEFRONT_BUDGET_MIB: most device memory that all sets of wavefront buffers in flight may take
 	// (default 36864 - config 4 then runs as three bands of 12 GB, the fastest of 1 ... 12 bands, profiles/r04c/: a
 	// frame whose worst case needs more is rendered in bands); VKR_BAND_COUNT forces
@@ -225,7 +215,7 @@ struct frame_pipeline {
 	// the target shape, 8, 0.488 -> 0.500 before the occluder lists and 0.501 -> 0.443 with them, which is what moved
 	// the rule from 16 to 8; config 2, 2 rays per pixel, 0.127 -> 0.192)
 	// VKR_SHAFT_REST, VKR_SHAFT_MAX_STEPS, VKR_WIDE_REFILL, VKR_WIDE_REFILL_BELOW (round 5): ensure_frames()
-	uint32_t wide_stack_lds, leaf_batch, refill_threshold, wide_refill, wide_refill_below, trace_waves, trace_single_waves, wavefront_budget_mib, band_count, light_shafts, shaft_lists, shaft_rest, shaft_max_steps;
+	uint32_t wide_stack_lds, wide_refill, wide_refill_below, wavefront_budget_mib, band_count, light_shafts, shaft_lists, shaft_rest, shaft_max_steps;
 };
 
 static uint32_t environment_knob(const char* name, uint32_t fallback, uint32_t low, uint32_t high) {
@@ -240,8 +230,6 @@ static void destroy_wavefront(shading_pass_t* pass) {
 	if (!frames) return;
 	for (frame_context& c : frames->contexts) {
 		if (c.done) { (void) hipEventSynchronize(c.done); (void) hipEventDestroy(c.done); }
-		if (c.trace_stream) { (void) hipStreamSynchronize(c.trace_stream); (void) hipStreamDestroy(c.trace_stream); }
-		if (c.shaded) (void) hipEventDestroy(c.shaded);
 		free_wavefront_buffers(&c.buffers);
 	}
 	free_wavefront_buffers(&frames->device_stream_buffers);
@@ -275,44 +263,25 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 	// kernel of a small launch - a rank's slab at N = 8 - lasts as long as its longest walk.
 	// (0: by the size of the launch - kShaftMaxSteps, or kShaftSmallLaunchSteps below 12 288 shading waves)
 	frames->shaft_max_steps = environment_knob("VKR_SHAFT_MAX_STEPS", 0u, 0u, 1000u);
-	frames->leaf_batch = environment_knob("VKR_LEAF_BATCH", 16u, 1u, 64u);
-	frames->refill_threshold = environment_knob("VKR_REFILL_THRESHOLD", 0u, 0u, 64u);
 	// VKR_WIDE_REFILL: lanes of a tracing wave (four-wide tree) that have to be idle before they are handed the next rays,
 	// once the wave has found its batches less than VKR_WIDE_REFILL_BELOW / 256 busy (wavefront_kernels.h; 256: from the
 	// first batch on); 0: a batch of 64 rays is always walked to its end first (until round 4)
 	frames->wide_refill = environment_knob("VKR_WIDE_REFILL", kWideRefillLanes, 0u, 64u);
 	frames->wide_refill_below = environment_knob("VKR_WIDE_REFILL_BELOW", kWideRefillBelow, 0u, 256u);
-	frames->trace_waves = environment_knob("VKR_TRACE_WAVES", 0u, 0u, 8u);
-	frames->trace_single_waves = environment_knob("VKR_TRACE_SINGLE_WAVES", 2u, 0u, 2u);
 	frames->wavefront_budget_mib = environment_knob("VKR_WAVEFRONT_BUDGET_MIB", 36864u, 64u, 262144u);
 	frames->band_count = environment_knob("VKR_BAND_COUNT", 0u, 0u, 4096u);
-	const char* priority = getenv("VKR_TRACE_STREAM_PRIORITY");
-	if (priority && strcmp(priority, "high") == 0) {
-		int least = 0, greatest = 0;
-		(void) hipDeviceGetStreamPriorityRange(&least, &greatest);
-		for (frame_context& c : frames->contexts)
-			if (hipStreamCreateWithPriority(&c.trace_stream, hipStreamNonBlocking, greatest) != hipSuccess || hipEventCreateWithFlags(&c.shaded, kSyncEventFlags) != hipSuccess) {
-				printf("Failed to create the high-priority tracing streams.\n");
-				destroy_wavefront(pass);
-				return NULL;
-			}
-	}
 	return frames;
 }
 
 // Slots a shading wave reserves per atomic (shade_params.ray_block): pays off when a lane
 // queues many rays; with one or two per lane the unused slots would outnumber the rays.
-// VKR_RAY_BLOCK (a multiple of 64, read once per process): the slots per block; unused slots of a wave's last
-// block become null rays, a contiguous run that the tracing kernel skips a batch at a time.
-static uint32_t ray_block_size(uint32_t max_terms) {
-	static uint32_t slots = 0;
-	if (!slots) {
-		const char* text = getenv("VKR_RAY_BLOCK");
-		long value = text ? strtol(text, NULL, 10) : 0;
-		slots = (value >= 64 && value <= 8192 && value % 64 == 0) ? (uint32_t) value : 256u;
-	}
-	return max_terms >= 8 ? slots : 0u;
-}
+// Unused slots of a wave's last block become null rays, a contiguous run that the tracing kernel
+// skips a batch at a time.
+static uint32_t ray_block_size(uint32_t max_terms) { return max_terms >= 8 ? 256u : 0u; }
+// Arguments of the tracing kernels: lanes that must have a triangle waiting before a wave tests triangles
+// (trace_shadow_rays_wide), and the refill threshold of the binary walk (trace_shadow_rays)
+constexpr uint32_t kLeafBatch = 16;
+constexpr uint32_t kRefillThreshold = 0;
 
 static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light_count, bool lists, hipStream_t stream) {
 	size_t list_words = lists ? words * kShaftListMax * kShaftListEntry : 0;
@@ -485,9 +454,8 @@ static void note_target_reader(application_t* app) {
 // that is already on the device (static camera and lights: no upload at all, like the
 // reference's host-coherent uniform buffer, which costs no GPU time either).
 constexpr uint32_t kConstantSlots = VKR_MAX_FRAMES_IN_FLIGHT + 2;
-// (device->stream, the frame streams and - VKR_TRACE_STREAM_PRIORITY=high - the tracing streams, whose resolve
-// kernels read the exposure)
-constexpr int kConstantReaders = 1 + 2 * VKR_MAX_FRAMES_IN_FLIGHT;
+// (device->stream and the frame streams)
+constexpr int kConstantReaders = 1 + VKR_MAX_FRAMES_IN_FLIGHT;
 struct constants_ring {
 	void* host[kConstantSlots];
 	void* device[kConstantSlots];
@@ -542,16 +510,12 @@ static int create_constants_ring(shading_pass_t* pass, const device_t* device) {
 static int upload_constants(application_t* app, hipStream_t stream) {
 	shading_pass_t* pass = &app->shading_pass;
 	constants_ring* ring = (constants_ring*) pass->constants_ring;
-	// an entry that does not exist (no tracing streams) is marked by `present`: a NULL stream is a stream too
+	// a frame stream that does not exist yet is marked by `present`: a NULL stream is a stream too
 	hipStream_t readers[kConstantReaders] = {(hipStream_t) app->device.stream};
 	bool present[kConstantReaders] = {true};
-	const frame_pipeline* pipeline = (const frame_pipeline*) pass->wavefront;
 	for (int i = 0; i != VKR_MAX_FRAMES_IN_FLIGHT; ++i) {
 		readers[1 + i] = (hipStream_t) app->device.frame_streams[i];
 		present[1 + i] = app->device.frame_streams[i] != NULL;
-		hipStream_t tracing = pipeline ? pipeline->contexts[i].trace_stream : NULL;
-		readers[1 + VKR_MAX_FRAMES_IN_FLIGHT + i] = tracing;
-		present[1 + VKR_MAX_FRAMES_IN_FLIGHT + i] = tracing != NULL;
 	}
 	write_constants(ring->scratch, app);
 	if (!ring->valid || memcmp(ring->scratch, ring->host[ring->current], pass->constants_size) != 0) {
@@ -1093,13 +1057,15 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 		// that give up after 12 steps (more rays traced, a shorter chain of kernels) the slab of config 3 takes 0.177
 		// instead of 0.199 ms, the target shape's 0.070 instead of 0.084; a quarter of the frame (8 160 waves) 0.316
 		// instead of 0.333.  The whole frame (32 640 waves) loses with either: 1.150 -> 1.176 ms with 12 steps.
+		// Otherwise eight waves per SIMD where a lane queues eight rays or more, four where it queues fewer (measured at config 2,
+		// whose 0.9 M rays are a batch or two per wave: 0.129 -> 0.121 ms per frame).
 		const uint32_t launch_waves = shade_grid_size(blocks_per_band);
-		const uint32_t small_launch_waves = frames->trace_waves ? 0u : (launch_waves < 6144u ? 2u : (launch_waves < 12288u ? 4u : 0u));
-		trace_blocks = compute_units * (frames->trace_waves ? frames->trace_waves : (small_launch_waves ? small_launch_waves : (max_terms >= 8u ? 8u : 4u)));
+		const uint32_t small_launch_waves = launch_waves < 6144u ? 2u : (launch_waves < 12288u ? 4u : 0u);
+		trace_blocks = compute_units * (small_launch_waves ? small_launch_waves : (max_terms >= 8u ? 8u : 4u));
 		// (queues of XCD x are only served by workgroups b with b % 8 == x)
 		trace_blocks = (trace_blocks + 7u) & ~7u;
 		p.ray_block = ray_mode == kRaysDeferredBlocks ? ray_block_size(max_terms) : 0u;
-		p.refill_threshold = frames->refill_threshold;
+		p.refill_threshold = kRefillThreshold;
 	}
 	else {
 		if (finish_frames(app)) return 1;
@@ -1165,8 +1131,6 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 			}
 			frame = &frames->contexts[index];
 			frames->last = index;
-			// (with a tracing stream the previous launch of this context did not end on this stream)
-			if (pipelined && frame->trace_stream && frame->recorded) (void) hipStreamWaitEvent(stream, frame->done, 0);
 			if (ensure_wavefront(&frame->buffers, blocks_per_band * 256u, max_terms, p.light_count, hidden_terms, base_color, stream)) return 1;
 			if (use_wide_tree && ensure_spill(&frame->buffers, app->scene.acceleration_structure.wide_stack_need, frames->wide_stack_lds, trace_blocks * 256u)) return 1;
 			const wavefront_buffers* w = &frame->buffers;
@@ -1176,15 +1140,10 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 			p.ray_queue_capacity = w->queue_capacity; p.ray_thread_bits = w->thread_bits;
 		}
 		if (table_in_memory) {
-			// a region per workgroup of the launch, in the launch's own buffers (VKR_PSA_TABLE_INDEX=slot: one buffer for the
-			// whole pass, indexed by the hardware slot a wave runs in - shading_kernel.h hardware_wave_slot.  Measured, config 4:
-			// the same time and the same traffic, 16.40 / 16.42 ms and 8.8 / 9.0 GB per frame, profiles/r10o - the table stores
-			// reach the fabric either way -, so the scheme that assumes nothing about the hardware is the default)
-			const bool by_block = !(getenv("VKR_PSA_TABLE_INDEX") != NULL && strcmp(getenv("VKR_PSA_TABLE_INDEX"), "slot") == 0);
-			wavefront_buffers* owner = (frame && by_block) ? &frame->buffers : &frames->device_stream_buffers;
-			if (ensure_psa_table_memory(owner, (size_t) (by_block ? shade_grid_size(blocks_per_band) : kWaveSlots) * table_bytes_per_workgroup)) return 1;
+			// a region per workgroup of the launch, in the launch's own buffers (shading_kernel.h psa_table_in_memory)
+			wavefront_buffers* owner = frame ? &frame->buffers : &frames->device_stream_buffers;
+			if (ensure_psa_table_memory(owner, (size_t) shade_grid_size(blocks_per_band) * table_bytes_per_workgroup)) return 1;
 			p.psa_table_memory = owner->psa_table_memory;
-			p.psa_table_by_wave_slot = by_block ? 0u : 1u;
 		}
 		pass->last_frame_stream = stream;
 		// (a target that earlier work of the caller still reads: every stream that writes it waits)
@@ -1273,26 +1232,16 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 			: g_launchers[pass->arithmetic_mode + (p.light_texture_descriptors ? 3 : 0)][strategy](technique, capacity, ray_mode, &p, p.block_count, stream);
 		if (timed && band + 1 == band_count) (void) hipEventRecord(ring[kTimingEvents * slot + 2], stream);
 		if (status == 0 && is_deferred(ray_mode)) {
-			if (pipelined && frame->trace_stream) {
-				// the rest of the launch moves to the high-priority stream; the next launch that reuses this context's
-				// frame stream is ordered behind `done` below (which is then recorded on the tracing stream)
-				(void) hipEventRecord(frame->shaded, stream);
-				(void) hipStreamWaitEvent(frame->trace_stream, frame->shaded, 0);
-				stream = frame->trace_stream;
-				pass->last_frame_stream = stream;
-			}
 			ray_stream rays = {p.ray_directions, p.ray_records, p.ray_origins, p.ray_queue_size, p.ray_queue_capacity, p.ray_thread_bits, p.thread_count};
 			if (use_wide_tree) {
 				const uint4* wide_nodes = (const uint4*) app->scene.acceleration_structure.wide_nodes;
 				// single-wave workgroups where a lane queues many rays and the shading kernel runs three waves
 				// per SIMD (wavefront_kernels.h has the measurements)
-				bool single_waves = ray_mode == kRaysDeferredBlocks && capacity <= 7;
-				if (frames->trace_single_waves != 2u) single_waves = frames->trace_single_waves != 0u;
-				if (single_waves) {
-					trace_shadow_rays_wide<64><<<trace_blocks * 4u, 64, 0, stream>>>(p.bvh, wide_nodes, app->scene.acceleration_structure.wide_node_count, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, frames->leaf_batch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
+				if (ray_mode == kRaysDeferredBlocks && capacity <= 7) {
+					trace_shadow_rays_wide<64><<<trace_blocks * 4u, 64, 0, stream>>>(p.bvh, wide_nodes, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, kLeafBatch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
 				}
 				else {
-					trace_shadow_rays_wide<256><<<trace_blocks, 256, 0, stream>>>(p.bvh, wide_nodes, app->scene.acceleration_structure.wide_node_count, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, frames->leaf_batch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
+					trace_shadow_rays_wide<256><<<trace_blocks, 256, 0, stream>>>(p.bvh, wide_nodes, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, kLeafBatch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
 				}
 			}
 			else
@@ -1303,14 +1252,13 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 				// (whether device->stream has already been made to wait for that launch - finish_frames() -
 				// says nothing about this stream)
 				frame_context* previous = &frames->contexts[(frames->last + frames->depth - 1u) % frames->depth];
-				// (bands of one frame, and frames that share a target; VKR_ORDER_ALL_RESOLVES=1: always, as until round 5)
-				static const bool order_all = getenv("VKR_ORDER_ALL_RESOLVES") != NULL;
+				// (bands of one frame, and frames that share a target)
 				// (a caller's ring of targets need not have the length of the pipeline: every other context one of whose recent
 				// launches wrote this target comes first)
 				for (uint32_t c = 0; c != frames->depth; ++c) {
 					frame_context* other = &frames->contexts[c];
 					if (other == frame || !other->recorded) continue;
-					bool same = order_all || (other == previous && band != 0);
+					bool same = other == previous && band != 0;
 					for (const void* written : other->targets) same = same || written == (const void*) p.out_radiance;
 					if (same) (void) hipStreamWaitEvent(stream, other->done, 0);
 				}
@@ -1644,52 +1592,6 @@ extern "C" int compare_device_division(const device_t* device, uint32_t first_si
 		failed = vkr_copy_to_host(out_mismatches_and_first, counters, 2 * sizeof(unsigned long long), device);
 	}
 	(void) hipFree(counters);
-	return failed;
-}
-
-// Every wave claims the word of its hardware slot, stays for a while and leaves it again; a wave that finds the word taken
-// shares its slot with a wave that is still there.  out[0]: such waves, out[1]: slots that were used
-__global__ void __launch_bounds__(64) k_check_hardware_wave_slots(uint32_t* owners, unsigned long long* out, uint32_t spin) {
-	uint32_t slot = hardware_wave_slot();
-	uint32_t old = 0;
-	if (threadIdx.x == 0) old = atomicExch(owners + slot, blockIdx.x + 1u);
-	old = __builtin_amdgcn_readfirstlane(old);
-	if (threadIdx.x == 0 && old != 0u) atomicAdd(out, 1ull);
-	if (threadIdx.x == 0 && old == 0u && atomicOr(owners + kWaveSlots + slot, 1u) == 0u) atomicAdd(out + 1, 1ull);
-	// (work that the compiler cannot remove and whose length differs between waves)
-	float x = (float) threadIdx.x;
-	for (uint32_t i = 0; i != spin * (1u + (blockIdx.x & 7u)); ++i) x = fmaf(x, 1.0000001f, 1.0e-7f);
-	if (x == 12345.678f) out[2] = 1ull;
-	// (with the value it returns: the wave waits for the exchange before it ends.  Without, the wave may be gone - and the next
-	// one in its slot - while the exchange is still on its way, and the next wave finds the slot "taken": 149 of 400 000 waves in
-	// the first version of this check.  The same holds for any store: that a wave's last stores have landed when its successor in
-	// the slot starts is nothing the hardware promises, which is why regions by wave slot are an option of the pass, not its default)
-	if (threadIdx.x == 0 && atomicExch(owners + slot, 0u) == 0xFFFFFFFFu) out[2] = 2ull;
-}
-
-extern "C" int check_hardware_wave_slots(const device_t* device, uint32_t workgroups, uint32_t extra_lds_bytes, uint64_t out_shared_and_used[2]) {
-	uint32_t* owners = NULL;
-	unsigned long long* out = NULL;
-	hipStream_t stream = (hipStream_t) device->stream;
-	int failed = hip_failed(hipMalloc(&owners, sizeof(uint32_t) * 2 * kWaveSlots), "allocating the slot owners") || hip_failed(hipMalloc(&out, 3 * sizeof(unsigned long long)), "allocating counters")
-		|| hip_failed(hipMemsetAsync(owners, 0, sizeof(uint32_t) * 2 * kWaveSlots, stream), "clearing") || hip_failed(hipMemsetAsync(out, 0, 3 * sizeof(unsigned long long), stream), "clearing");
-	if (!failed) {
-		// (two launches on two streams at once: slots are unique across kernels, not only within one)
-		hipStream_t other = (hipStream_t) device->frame_streams[0];
-		if (other) {
-			hipEvent_t ready;
-			failed = hip_failed(hipEventCreateWithFlags(&ready, hipEventDisableTiming), "creating an event") || hip_failed(hipEventRecord(ready, stream), "recording") || hip_failed(hipStreamWaitEvent(other, ready, 0), "waiting");
-			if (!failed) k_check_hardware_wave_slots<<<workgroups, 64, extra_lds_bytes, other>>>(owners, out, 2000u);
-			(void) hipEventDestroy(ready);
-		}
-		k_check_hardware_wave_slots<<<workgroups, 64, extra_lds_bytes, stream>>>(owners, out, 3000u);
-		failed = failed || hip_failed(hipGetLastError(), "launching the slot check");
-		if (other) failed = failed || hip_failed(hipStreamSynchronize(other), "waiting for the slot check");
-	}
-	unsigned long long host[3] = {0, 0, 0};
-	failed = failed || hip_failed(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, stream), "reading the counters") || hip_failed(hipStreamSynchronize(stream), "waiting for the slot check");
-	out_shared_and_used[0] = host[0]; out_shared_and_used[1] = host[1];
-	(void) hipFree(owners); (void) hipFree(out);
 	return failed;
 }
 

@@ -10,29 +10,12 @@ namespace vkr {
 // ---- wavefront: trace and resolve (instantiated once, in shading_pass.hip) -------------------
 
 // Persistent tracing waves per SIMD that the wide kernel is compiled for (register budget 512 / n)
-#ifndef VKR_WIDE_TRACE_WAVES
-#define VKR_WIDE_TRACE_WAVES 8
-#endif
-constexpr uint32_t kWideTraceWaves = VKR_WIDE_TRACE_WAVES;
+constexpr uint32_t kWideTraceWaves = 8;
 // Idle lanes of a tracing wave before the next rays are handed out (trace_shadow_rays_wide, `refill_lanes`; the
 // run-time knob is VKR_WIDE_REFILL, 0 = always a batch at a time)
-#ifndef VKR_WIDE_REFILL_LANES
-#define VKR_WIDE_REFILL_LANES 16
-#endif
-constexpr uint32_t kWideRefillLanes = VKR_WIDE_REFILL_LANES;
+constexpr uint32_t kWideRefillLanes = 16;
 // ... by a wave whose batches kept less than this share (in 1/256) of its lanes busy (VKR_WIDE_REFILL_BELOW)
 constexpr uint32_t kWideRefillBelow = 166;
-
-// Experiment of round 3 (north_star: "LDS-staged BVH node packets"; profiles/r03_trace.md has the
-// measurement): the first VKR_LDS_TOP_NODES nodes of the four-wide tree - its top levels, breadth
-// first: 1 + 4 + 16 = 21 nodes are three levels - are copied into LDS by every workgroup and fetched
-// from there (flat loads: the address decides between LDS and global memory).  0: off (the default).
-#ifndef VKR_TRACE_BLOCKER_CACHE
-#define VKR_TRACE_BLOCKER_CACHE 1
-#endif
-#ifndef VKR_LDS_TOP_NODES
-#define VKR_LDS_TOP_NODES 0
-#endif
 
 // What the tracing kernels read: the queues that the shading kernel filled (shade_params has the
 // same pointers, writable)
@@ -215,16 +198,8 @@ __global__ void __launch_bounds__(256) trace_shadow_rays(bvh_view bvh, ray_strea
 // between the two scenes' 0.77 and 0.56) hands out rays from then on.  VKR_WIDE_REFILL=0: never; VKR_WIDE_REFILL_BELOW=256:
 // from the first batch on.
 template <uint32_t THREADS>
-__global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wide(bvh_view bvh, const uint4* __restrict__ wide_nodes, uint32_t wide_node_count, ray_stream rays, uint32_t* work_cursors, uint8_t* codes, uint32_t* spill, uint32_t leaf_batch, uint32_t lds_entries, uint32_t refill_lanes, uint32_t refill_below) {
+__global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wide(bvh_view bvh, const uint4* __restrict__ wide_nodes, ray_stream rays, uint32_t* work_cursors, uint8_t* codes, uint32_t* spill, uint32_t leaf_batch, uint32_t lds_entries, uint32_t refill_lanes, uint32_t refill_below) {
 	__shared__ uint32_t stack[kWideStackLds * THREADS];
-#if VKR_LDS_TOP_NODES
-	__shared__ uint4 top_nodes[VKR_LDS_TOP_NODES * 4];
-	const uint32_t top_count = min((uint32_t) VKR_LDS_TOP_NODES, wide_node_count);
-	for (uint32_t i = threadIdx.x; i < top_count * 4u; i += THREADS) top_nodes[i] = wide_nodes[i];
-	__syncthreads();
-#else
-	(void) wide_node_count;
-#endif
 	const uint32_t lane = threadIdx.x & 63u;
 	chunk_cursor cursor = make_chunk_cursor(rays, THREADS / 64u);
 	// `item`: what the lane looks at next - a wide node (index), a triangle (kLeafBit | slot) or
@@ -235,10 +210,8 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 	float t_max = 0.0f;
 	// (byte index of the term's code: below 2^32, the host checks)
 	uint32_t item = kIdle, code_index = 0;
-#if VKR_TRACE_BLOCKER_CACHE
 	// the triangle that blocked this lane's most recent blocked ray, or kIdle (see try_last_blocker below)
 	uint32_t last_blocker = kIdle;
-#endif
 	// The stack pointer is the lane's LDS address itself (entries are THREADS x 4 bytes apart), so
 	// that a push is a store and a conditional add; entries beyond the LDS part only exist as a
 	// depth (`top` then points behind the LDS part and is never dereferenced)
@@ -275,9 +248,6 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 		bool pop = false;
 		if (at_node) {
 			const uint4* n = (const uint4*) ((const uint8_t*) wide_nodes + ((size_t) item << 6));
-#if VKR_LDS_TOP_NODES
-			if (item < top_count) n = top_nodes + 4u * item;
-#endif
 			uint4 qx = n[0], qy = n[1], qz = n[2], link = n[3];
 			bool h0 = wide_ray_box(qx.x, qy.x, qz.x, ray, 1.0e-3f, t_max);
 			bool h1 = wide_ray_box(qx.y, qy.y, qz.y, ray, 1.0e-3f, t_max);
@@ -311,9 +281,7 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 			float dist;
 			bool blocked = ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist);
 			// a blocked ray is done: its term keeps the code the shading kernel gave it
-#if VKR_TRACE_BLOCKER_CACHE
 			if (blocked) last_blocker = item & ~kLeafBit;
-#endif
 			if (blocked) { item = kIdle; top = my_stack; }
 			else pop = true;
 		}
@@ -334,13 +302,11 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 	// A ray that has just been taken is tested against it before it walks: a hit ends the ray at once (any hit is a hit: the
 	// result of the query is the same boolean), a miss costs one triangle test next to the 6 - 22 node fetches of a walk.
 	auto try_last_blocker = [&]() {
-#if VKR_TRACE_BLOCKER_CACHE
 		if (item == 0u && last_blocker != kIdle) {
 			const float4* t = bvh.triangles + 3 * (size_t) last_blocker;
 			float dist;
 			if (ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist)) item = kIdle;
 		}
-#endif
 	};
 	bool batch_pending = fetch_batch();
 	// ---- a batch at a time, until the wave finds its lanes idle too often ------------------------------
