@@ -53,13 +53,17 @@ static bvh_view make_bvh_view(const acceleration_structure_t* structure) {
 	return view;
 }
 
+// The strategies that prepare a specular technique besides the diffuse one (the combined diffuse + specular path), and the
+// out-of-range strategies, which select the same preparation (validate_settings)
+static bool has_specular_technique(const render_settings_t* settings) { return settings->sampling_strategies >= sampling_strategies_diffuse_specular_separately; }
+
 static int technique_index(const render_settings_t* settings) {
 	switch (settings->polygon_sampling_technique) {
 	// Arvo's sampler only exists in the diffuse-only / GGX-MIS branch of the reference shader; its
 	// combined diffuse + specular branch uses the paper's own sampler whatever the technique says
 	// (shading_pass.frag.glsl:441, :506-547)
 	case sample_polygon_projected_solid_angle_arvo:
-		return settings->sampling_strategies >= sampling_strategies_diffuse_specular_separately ? kTechniquePsa : kTechniquePsaArvo;
+		return has_specular_technique(settings) ? kTechniquePsa : kTechniquePsaArvo;
 	case sample_polygon_projected_solid_angle: return kTechniquePsa;
 	case sample_polygon_projected_solid_angle_biased: return kTechniquePsaBiased;
 	case sample_polygon_solid_angle: return kTechniqueSolidAngle;
@@ -74,6 +78,14 @@ static int technique_index(const render_settings_t* settings) {
 	case sample_polygon_biquadratic_cosine_warp_clipping_hart: return kTechniqueHartBiquadraticClipping;
 	default: return -1;
 	}
+}
+
+// the projected solid angle techniques: the only ones with an error display and with LTC importance sampling beside them
+static bool is_projected_solid_angle(int technique) { return technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniquePsaArvo; }
+
+// the techniques whose samples aim at the light polygon itself: every shadow ray lies inside the light's shaft
+static bool aims_at_light_polygon(int technique) {
+	return technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniqueSolidAngle || technique == kTechniqueClippedSolidAngle;
 }
 
 // ---- render targets --------------------------------------------------------------
@@ -114,7 +126,9 @@ extern "C" int create_render_targets(render_targets_t* targets, const device_t* 
 // ---- shading pass ----------------------------------------------------------------
 
 // events of a timed frame: its start, the start and the end of the (last band's) shading kernel, its end
-constexpr uint32_t kTimingEvents = 4;
+constexpr uint32_t kTimingFrameStart = 0, kTimingShadingStart = 1, kTimingShadingEnd = 2, kTimingFrameEnd = 3, kTimingEvents = 4;
+
+static hipEvent_t timing_event(const shading_pass_t* pass, uint32_t slot, uint32_t which) { return ((hipEvent_t*) pass->timing_ring)[kTimingEvents * slot + which]; }
 
 // device counter of traced shadow rays, shared by all passes of the process
 
@@ -679,7 +693,8 @@ extern "C" int begin_read_back(application_t* app, uint32_t slot, const void* de
 		}
 		rb->staging_size[slot] = (size_t) bytes;
 	}
-	// behind the frames in flight (the most recent one completes last: resolves are chained) ...
+	// behind the most recent frame in flight (only that one: its resolves wait for earlier frames that wrote the same target,
+	// not for those that wrote another one, which may still be running) ...
 	frame_pipeline* frames = (frame_pipeline*) pass->wavefront;
 	if (frames && pass->last_frame_in_flight) {
 		frame_context* last = &frames->contexts[frames->last];
@@ -734,7 +749,7 @@ static int validate_settings(const application_t* app) {
 		printf("Invalid polygon sampling technique %d.\n", (int) s->polygon_sampling_technique);
 		return 1;
 	}
-	bool is_psa = technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniquePsaArvo;
+	bool is_psa = is_projected_solid_angle(technique);
 	// An out-of-range strategy selects none of the strategy defines of the reference, i.e.
 	// the combined diffuse + specular preparation with no estimator behind it.  That is
 	// only meaningful with an error display (the reference's own experiment table does it,
@@ -744,9 +759,7 @@ static int validate_settings(const application_t* app) {
 		printf("Invalid sampling strategy or MIS heuristic.\n");
 		return 1;
 	}
-	bool needs_specular = s->sampling_strategies == sampling_strategies_diffuse_specular_separately
-		|| s->sampling_strategies == sampling_strategies_diffuse_specular_mis
-		|| s->sampling_strategies == sampling_strategies_diffuse_specular_random;
+	bool needs_specular = strategy_in_range && has_specular_technique(s);
 	if ((technique == kTechniqueBaseline || technique == kTechniqueAreaTurk || technique == kTechniqueHartBilinear || technique == kTechniqueHartBilinearClipping
 			|| technique == kTechniqueHartBiquadratic || technique == kTechniqueHartBiquadraticClipping)
 		&& s->sampling_strategies != sampling_strategies_diffuse_only)
@@ -861,8 +874,9 @@ static void fill_tile_schedule(shade_params& p, const application_t* app, uint32
 	grid_blocks = own_tiles * blocks_per_tile;
 }
 
-extern "C" uint64_t get_slab_pixel_count(const application_t* app, uint32_t rank) {
-	shade_params p;
+// The tiling of `rank`'s slab (p: width, height and tile schedule); returns the slab's pixel count.  Rank 0 owns the most
+// tiles: its count is the stride of the slabs in a gathered buffer.
+static uint64_t slab_tiling(const application_t* app, uint32_t rank, shade_params& p) {
 	memset(&p, 0, sizeof(p));
 	p.width = app->swapchain.extent.width;
 	p.height = app->swapchain.extent.height;
@@ -873,7 +887,12 @@ extern "C" uint64_t get_slab_pixel_count(const application_t* app, uint32_t rank
 	return (uint64_t) grid_blocks * 256;
 }
 
-__global__ void k_encode_output_rgb8(const float4* radiance, uint32_t* packed, uint64_t quad_count, uint32_t frame_bits, int output_linear_rgb);
+extern "C" uint64_t get_slab_pixel_count(const application_t* app, uint32_t rank) {
+	shade_params p;
+	return slab_tiling(app, rank, p);
+}
+
+static void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream);
 
 static int render_pass(application_t* app, void* out_radiance, void* out_rgb8);
 extern "C" int get_traversal_statistics_of_tree(application_t* app, VkBool32 wide_tree, uint64_t out_statistics[8]);
@@ -890,26 +909,22 @@ extern "C" int render_shading_pass_encoded(application_t* app, void* out_radianc
 	return render_pass(app, out_radiance, out_rgb8);
 }
 
-// out_rgb8: the frame (or slab) is also encoded as packed RGB8 on the stream it was rendered on
-static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
-	shading_pass_t* pass = &app->shading_pass;
-	const device_t* device = &app->device;
-	if (pass->variant < 0 || !pass->constants_device) {
-		printf("render_shading_pass() needs a shading pass created by create_shading_pass().\n");
-		return 1;
-	}
-	// settings may have been edited since create_shading_pass(): the same legality rules apply, and the
-	// launcher tables below are indexed with them
-	if (validate_settings(app)) return 1;
-	if (get_constant_buffer_size(app) != pass->constants_size
-		|| get_max_polygon_vertex_count(&app->scene_specification, &app->render_settings) != pass->max_polygon_vertex_count
-		|| (int32_t) app->render_settings.sampling_strategies * kTechniqueCount + technique_index(&app->render_settings) != pass->variant)
-	{
-		printf("Lights or render settings changed in a way that needs a different kernel variant. Recreate the shading pass (the reference recompiles its shader in this situation, main.c:1833-1881).\n");
-		return 1;
-	}
-	hipStream_t stream = (hipStream_t) device->stream;
-	shade_params p;
+// What render_pass() decides about a frame before its first band (plan_frame, plan_bands); the band steps read it
+struct frame_plan {
+	shade_params p;          // the parameters of every launch of the frame; a band step adds the band's blocks and buffers
+	frame_pipeline* frames;  // NULL for a frame without wavefront rays, unless its polygon tables live in device memory
+	int strategy, technique, capacity, error_mode, ray_mode;
+	// (table_in_memory: the kernel variants that keep one of their two polygon tables in device memory, shading_kernel.h psa_table_in_memory)
+	bool table_in_memory, hidden_terms, base_color, use_wide_tree, textured, pipelined;
+	uint32_t grid_blocks, table_bytes_per_workgroup, max_terms;
+	// frames in flight (1: not pipelined), the bands of the frame, workgroups of the tracing kernels (wavefront rays only)
+	uint32_t depth, band_count, blocks_per_band, trace_blocks;
+	// bytes of the output this call writes (a slab in slab layout, else the frame): what pending read-backs are checked against
+	size_t frame_output_bytes;
+};
+
+// the parameters of a frame that come straight from the application
+static void fill_frame_inputs(const application_t* app, void* out_radiance, shade_params& p) {
 	memset(&p, 0, sizeof(p));
 	p.light_count = app->scene_specification.polygonal_light_count;
 	p.max_light_vertex_count = get_max_polygonal_light_vertex_count(&app->scene_specification);
@@ -932,6 +947,50 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 	p.noise_width = app->noise_table.resolution.width;
 	p.noise_height = app->noise_table.resolution.height;
 	p.bvh = make_bvh_view(&app->scene.acceleration_structure);
+}
+
+// Error display (ERROR_DISPLAY_DIFFUSE / _SPECULAR / ERROR_INDEX, main.c:728-750): only
+// the projected solid angle paths look at these flags, and the specular display
+// exists only where the specular technique is prepared.  The program returns
+// before it samples, so no ray is ever traced.
+static void plan_error_display(const application_t* app, frame_plan* f) {
+	int display = (int) app->render_settings.error_display;
+	f->error_mode = kErrorNone;
+	if (display != error_display_none && is_projected_solid_angle(f->technique)) {
+		bool specular = display == error_display_specular_backward || display == error_display_specular_backward_scaled || display == error_display_specular_forward;
+		f->error_mode = specular ? (has_specular_technique(&app->render_settings) ? kErrorSpecular : kErrorNone) : kErrorDiffuse;
+	}
+	if (f->error_mode == kErrorNone) return;
+	f->ray_mode = kRaysNone;
+	f->p.error_index = (display == error_display_diffuse_backward || display == error_display_specular_backward) ? 0u
+		: ((display == error_display_diffuse_backward_scaled || display == error_display_specular_backward_scaled) ? 1u : 2u);
+	// the constants that the GLSL compiler folds in error_to_color (shading_pass.frag.glsl:81-89)
+	f->p.error_max = powf(10.0f, 5.0f - 0.01f);
+	f->p.error_scale = 20.0f / ((5.0f - 0.0f) * log2f(10.0f));
+}
+
+// The checks of a frame and the decisions that need no HIP call: one launch of the whole schedule until plan_bands()
+static int plan_frame(application_t* app, void* out_radiance, frame_plan* f) {
+	const shading_pass_t* pass = &app->shading_pass;
+	if (pass->variant < 0 || !pass->constants_device) {
+		printf("render_shading_pass() needs a shading pass created by create_shading_pass().\n");
+		return 1;
+	}
+	// settings may have been edited since create_shading_pass(): the same legality rules apply, and the
+	// launcher tables below are indexed with them
+	if (validate_settings(app)) return 1;
+	memset(f, 0, sizeof(*f));
+	f->strategy = (int) app->render_settings.sampling_strategies;
+	f->technique = technique_index(&app->render_settings);
+	if (get_constant_buffer_size(app) != pass->constants_size
+		|| get_max_polygon_vertex_count(&app->scene_specification, &app->render_settings) != pass->max_polygon_vertex_count
+		|| (int32_t) app->render_settings.sampling_strategies * kTechniqueCount + f->technique != pass->variant)
+	{
+		printf("Lights or render settings changed in a way that needs a different kernel variant. Recreate the shading pass (the reference recompiles its shader in this situation, main.c:1833-1881).\n");
+		return 1;
+	}
+	shade_params& p = f->p;
+	fill_frame_inputs(app, out_radiance, p);
 	if (!p.positions || !p.visibility || !p.out_radiance || !p.ltc_rgba || !p.noise || !p.material_constants) {
 		printf("render_shading_pass() needs a loaded scene, LTC table, noise table and render targets on the device.\n");
 		return 1;
@@ -940,156 +999,140 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 		printf("The render targets do not match the swapchain extent.\n");
 		return 1;
 	}
-	uint32_t grid_blocks = 0;
-	fill_tile_schedule(p, app, grid_blocks);
-	int ray_mode = !pass->use_ray_tracing ? kRaysNone : (pass->inline_rays ? kRaysInline : kRaysDeferred);
-	// Error display (ERROR_DISPLAY_DIFFUSE / _SPECULAR / ERROR_INDEX, main.c:728-750): only
-	// the projected solid angle paths look at these flags, and the specular display
-	// exists only where the specular technique is prepared.  The program returns
-	// before it samples, so no ray is ever traced.
-	int error_mode = kErrorNone;
-	{
-		int display = (int) app->render_settings.error_display;
-		int technique_now = technique_index(&app->render_settings);
-		bool combined = app->render_settings.sampling_strategies >= sampling_strategies_diffuse_specular_separately;
-		if (display != error_display_none && (technique_now == kTechniquePsa || technique_now == kTechniquePsaBiased || technique_now == kTechniquePsaArvo)) {
-			bool specular = display == error_display_specular_backward || display == error_display_specular_backward_scaled || display == error_display_specular_forward;
-			error_mode = specular ? (combined ? kErrorSpecular : kErrorNone) : kErrorDiffuse;
-		}
-		if (error_mode != kErrorNone) {
-			ray_mode = kRaysNone;
-			p.error_index = (display == error_display_diffuse_backward || display == error_display_specular_backward) ? 0u
-				: ((display == error_display_diffuse_backward_scaled || display == error_display_specular_backward_scaled) ? 1u : 2u);
-			// the constants that the GLSL compiler folds in error_to_color (shading_pass.frag.glsl:81-89)
-			p.error_max = powf(10.0f, 5.0f - 0.01f);
-			p.error_scale = 20.0f / ((5.0f - 0.0f) * log2f(10.0f));
-		}
-	}
-	if (error_mode == kErrorNone && (int) app->render_settings.sampling_strategies >= (int) sampling_strategies_count) {
+	fill_tile_schedule(p, app, f->grid_blocks);
+	f->ray_mode = !pass->use_ray_tracing ? kRaysNone : (pass->inline_rays ? kRaysInline : kRaysDeferred);
+	plan_error_display(app, f);
+	if (f->error_mode == kErrorNone && f->strategy >= (int) sampling_strategies_count) {
 		// (an out-of-range strategy is only legal together with an error display that is really shown:
 		// a specular display without the combined path shows nothing and would index past the launcher table)
-		printf("No kernel variant exists for sampling strategy %d without an error display.\n", (int) app->render_settings.sampling_strategies);
+		printf("No kernel variant exists for sampling strategy %d without an error display.\n", f->strategy);
 		return 1;
 	}
-	if (pass->use_ray_tracing) {
-		// (sixteen counters, one per frame in turn: see the band loop)
-		if (!pass->ray_counter && hip_failed(hipMalloc(&pass->ray_counter, 16 * sizeof(unsigned long long)), "allocating the ray counters")) return 1;
-		p.ray_counter = (unsigned long long*) pass->ray_counter;
-	}
-	int strategy = (int) app->render_settings.sampling_strategies;
-	int technique = technique_index(&app->render_settings);
-	bool is_clipped = technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniqueClippedSolidAngle || technique == kTechniqueHartBilinearClipping || technique == kTechniqueHartBiquadraticClipping || technique == kTechniquePsaArvo;
-	int capacity = (int) p.max_light_vertex_count + (is_clipped ? 1 : 0);
-	// the kernel variants that keep one of their two polygon tables in device memory (shading_kernel.h psa_table_in_memory)
-	const bool table_in_memory = strategy >= kStrategySeparately && (technique == kTechniquePsa || technique == kTechniquePsaBiased) && error_mode == kErrorNone && psa_table_in_memory(capacity);
-	const uint32_t table_bytes_per_workgroup = table_in_memory ? psa_table_memory_bytes_per_workgroup(capacity) : 0u;
-	// Launches with wavefront rays may run n at a time: launch k on frame stream k mod n with
-	// its own buffers, so that the (latency-bound) tracing of one launch overlaps the
-	// (VALU-bound) shading of the next ones.  Everything else runs on device->stream, behind
-	// any launch that is still in flight.
-	// A frame is one launch - or several, "bands" of consecutive 16x16 blocks of the rank's schedule,
-	// when the wavefront buffers of the whole frame (sized for the worst case: every sample of every
-	// light on every pixel queues a ray) would be larger than the budget: a band is shaded, traced and
-	// resolved like a small frame, with buffers sized for the band, and the bands of one frame - and of
-	// the next frames - overlap on the frame streams exactly like whole frames do.
-	bool pipelined = false;
-	// the tracing kernels are persistent: 8 waves per SIMD on every CU, each lane strides over the queues
-	// (8 by default; the count is a knob of the frame pipeline)
-	const uint32_t compute_units = (uint32_t) (app->device.compute_unit_count > 0 ? app->device.compute_unit_count : 256);
-	uint32_t trace_blocks = compute_units * 8u;
-	const bool use_wide_tree = app->scene.acceleration_structure.wide_nodes && !pass->binary_traversal;
-	const uint32_t max_terms = 2u * p.light_count * p.sample_count;
-	if (ray_mode == kRaysDeferred && (int) app->render_settings.sampling_strategies >= (int) sampling_strategies_diffuse_specular_separately && ray_block_size(max_terms))
-		ray_mode = kRaysDeferredBlocks;
+	// (the same as the light vertex count plus one for the techniques that clip, host/constants.c, checked above)
+	f->capacity = (int) pass->max_polygon_vertex_count;
+	const bool specular = has_specular_technique(&app->render_settings);
+	f->table_in_memory = specular && (f->technique == kTechniquePsa || f->technique == kTechniquePsaBiased) && f->error_mode == kErrorNone && psa_table_in_memory(f->capacity);
+	f->table_bytes_per_workgroup = f->table_in_memory ? psa_table_memory_bytes_per_workgroup(f->capacity) : 0u;
+	f->use_wide_tree = app->scene.acceleration_structure.wide_nodes && !pass->binary_traversal;
+	f->max_terms = 2u * p.light_count * p.sample_count;
+	if (f->ray_mode == kRaysDeferred && specular && ray_block_size(f->max_terms)) f->ray_mode = kRaysDeferredBlocks;
 	// values of blocked terms exist for the plain optimal heuristic only (its estimate is not proportional
 	// to the integrand); a colour before the sampled terms only with the light display
-	const bool hidden_terms = app->render_settings.mis_heuristic == mis_heuristic_optimal && (int) app->render_settings.sampling_strategies == (int) sampling_strategies_diffuse_specular_mis;
-	const bool base_color = p.show_polygonal_lights != 0;
-	uint32_t band_count = 1, blocks_per_band = grid_blocks, depth = 1;
-	frame_pipeline* frames = NULL;
-	if (is_deferred(ray_mode)) {
-		frames = ensure_frames(pass);
-		if (!frames) return 1;
-		// (a textured scene has one per-pixel material buffer: one frame at a time)
-		depth = pass->frames_in_flight < VKR_MAX_FRAMES_IN_FLIGHT ? pass->frames_in_flight : VKR_MAX_FRAMES_IN_FLIGHT;
-		// (the device creates four frame streams; a deeper pipeline gets the others now)
-		if (depth >= 2 && !device->frame_streams[depth - 1] && vkr_ensure_frame_streams(&app->device, depth)) return 1;
-		while (depth >= 2 && !device->frame_streams[depth - 1]) --depth;
-		if (depth < 1) depth = 1;
-		pipelined = depth >= 2 && !app->scene.materials.textured;
-		if (!pipelined) depth = 1;
-		// Bands: as few as keep all sets of buffers in flight within the budget, each at least
-		// kMinBandBlocks blocks (a launch has to fill the GPU several times over), whole groups of 8 blocks
-		// (shade_grid_size).  pass->band_count / VKR_BAND_COUNT force a number.
-		const double budget = (double) frames->wavefront_budget_mib * 1048576.0;
-		const uint32_t kMinBandBlocks = 4096;
-		uint32_t wanted = pass->band_count ? pass->band_count : frames->band_count;
-		if (!wanted) {
-			wanted = 1;
-			while (depth * wavefront_bytes(((grid_blocks + wanted - 1) / wanted) * 256u, max_terms, p.light_count, hidden_terms, base_color, table_bytes_per_workgroup / 64u) > budget
-				&& (grid_blocks + wanted) / (wanted + 1) >= kMinBandBlocks)
-				++wanted;
-		}
-		blocks_per_band = (((grid_blocks + wanted - 1) / wanted) + 7u) & ~7u;
-		if (blocks_per_band == 0) blocks_per_band = 8;
-		band_count = (grid_blocks + blocks_per_band - 1) / blocks_per_band;
-		if (band_count == 0) band_count = 1;
-		if (!pipelined && finish_frames(app)) return 1;
-		if (pipelined && frames->depth != depth) {
-			// another pipeline depth: contexts and streams pair up differently, start afresh
-			if (frames->depth && wait_for_device(device)) return 1;
-			for (frame_context& c : frames->contexts) c.recorded = c.pending = false;
-			frames->depth = depth;
-			frames->next = 0;
-		}
-		if (pipelined && pass->inputs_changed) {
-			// Inputs that were produced on device->stream (visibility pass, uploads): all frame
-			// streams wait for them once.  Frames do not wait for anything else on
-			// device->stream - if they did, a consumer of frame k there would hold back frame k + 1.
-			if (hip_failed(hipEventRecord(frames->inputs_ready, (hipStream_t) device->stream), "marking the inputs")) return 1;
-			for (uint32_t i = 0; i != depth; ++i)
-				if (hip_failed(hipStreamWaitEvent((hipStream_t) device->frame_streams[i], frames->inputs_ready, 0), "waiting for the inputs")) return 1;
-			pass->inputs_changed = 0;
-		}
-		// Small launches (round 5, profiles/r07f): a rank's slab at N = 8 is 4 080 shading waves on 3 072 wave slots.  Its
-		// kernels then last about as long as their slowest wave, and what is launched for a whole frame - 8 192 tracing
-		// waves for 230 k rays, shaft walks of up to 72 steps - is mostly waiting: with 2 tracing waves per SIMD and walks
-		// that give up after 12 steps (more rays traced, a shorter chain of kernels) the slab of config 3 takes 0.177
-		// instead of 0.199 ms, the target shape's 0.070 instead of 0.084; a quarter of the frame (8 160 waves) 0.316
-		// instead of 0.333.  The whole frame (32 640 waves) loses with either: 1.150 -> 1.176 ms with 12 steps.
-		// Otherwise eight waves per SIMD where a lane queues eight rays or more, four where it queues fewer (measured at config 2,
-		// whose 0.9 M rays are a batch or two per wave: 0.129 -> 0.121 ms per frame).
-		const uint32_t launch_waves = shade_grid_size(blocks_per_band);
-		const uint32_t small_launch_waves = launch_waves < 6144u ? 2u : (launch_waves < 12288u ? 4u : 0u);
-		trace_blocks = compute_units * (small_launch_waves ? small_launch_waves : (max_terms >= 8u ? 8u : 4u));
-		// (queues of XCD x are only served by workgroups b with b % 8 == x)
-		trace_blocks = (trace_blocks + 7u) & ~7u;
-		p.ray_block = ray_mode == kRaysDeferredBlocks ? ray_block_size(max_terms) : 0u;
-		p.refill_threshold = kRefillThreshold;
-	}
-	else {
-		if (finish_frames(app)) return 1;
-		// (no wavefront buffers, but the table in device memory lives with them: context 0)
-		if (table_in_memory && !(frames = ensure_frames(pass))) return 1;
-	}
-	pass->last_frame_traced_rays = ray_mode != kRaysNone;
-	pass->last_frame_in_flight = pipelined ? depth : 0u;
-	pass->last_band_count = band_count;
+	f->hidden_terms = app->render_settings.mis_heuristic == mis_heuristic_optimal && f->strategy == (int) sampling_strategies_diffuse_specular_mis;
+	f->base_color = p.show_polygonal_lights != 0;
+	f->depth = f->band_count = 1;
+	f->blocks_per_band = f->grid_blocks;
 	// textured scene: sample the material textures of every pixel first (same stream)
-	bool textured = app->scene.materials.textured && app->scene.materials.texture_descriptors;
-	if (textured) {
-		size_t needed = sizeof(float) * 8 * (size_t) p.width * p.height;
-		if (pass->pixel_materials_size != needed) {
-			if (wait_for_device(device)) return 1;
-			(void) hipFree(pass->pixel_materials);
-			pass->pixel_materials = NULL;
-			pass->pixel_materials_size = 0;
-			if (hip_failed(hipMalloc(&pass->pixel_materials, needed), "allocating the per-pixel materials")) return 1;
-			pass->pixel_materials_size = needed;
-		}
+	f->textured = app->scene.materials.textured && app->scene.materials.texture_descriptors;
+	if (f->textured) {
 		p.texture_descriptors = (const uint32_t*) app->scene.materials.texture_descriptors;
 		p.texels = (const uint32_t*) app->scene.materials.texels;
 		p.srgb_table = (const float*) app->scene.materials.srgb_table;
+	}
+	// slab layout: every thread of the grid owns a slot; full-frame layout: the pixels
+	f->frame_output_bytes = sizeof(float4) * (p.slab_layout ? (size_t) f->grid_blocks * 256u : (size_t) p.width * p.height);
+	return 0;
+}
+
+// Launches with wavefront rays may run n at a time: launch k on frame stream k mod n with
+// its own buffers, so that the (latency-bound) tracing of one launch overlaps the
+// (VALU-bound) shading of the next ones.  Everything else runs on device->stream, behind
+// any launch that is still in flight.
+// A frame is one launch - or several, "bands" of consecutive 16x16 blocks of the rank's schedule,
+// when the wavefront buffers of the whole frame (sized for the worst case: every sample of every
+// light on every pixel queues a ray) would be larger than the budget: a band is shaded, traced and
+// resolved like a small frame, with buffers sized for the band, and the bands of one frame - and of
+// the next frames - overlap on the frame streams exactly like whole frames do.
+static int plan_bands(application_t* app, frame_plan* f) {
+	const device_t* device = &app->device;
+	frame_pipeline* frames = f->frames = ensure_frames(&app->shading_pass);
+	if (!frames) return 1;
+	// (a textured scene has one per-pixel material buffer: one frame at a time)
+	uint32_t depth = app->shading_pass.frames_in_flight < VKR_MAX_FRAMES_IN_FLIGHT ? app->shading_pass.frames_in_flight : VKR_MAX_FRAMES_IN_FLIGHT;
+	// (the device creates four frame streams; a deeper pipeline gets the others now)
+	if (depth >= 2 && !device->frame_streams[depth - 1] && vkr_ensure_frame_streams(&app->device, depth)) return 1;
+	while (depth >= 2 && !device->frame_streams[depth - 1]) --depth;
+	if (depth < 1) depth = 1;
+	f->pipelined = depth >= 2 && !app->scene.materials.textured;
+	f->depth = f->pipelined ? depth : 1u;
+	// Bands: as few as keep all sets of buffers in flight within the budget, each at least
+	// kMinBandBlocks blocks (a launch has to fill the GPU several times over), whole groups of 8 blocks
+	// (shade_grid_size).  pass->band_count / VKR_BAND_COUNT force a number.
+	const double budget = (double) frames->wavefront_budget_mib * 1048576.0;
+	const uint32_t kMinBandBlocks = 4096, grid_blocks = f->grid_blocks;
+	uint32_t wanted = app->shading_pass.band_count ? app->shading_pass.band_count : frames->band_count;
+	if (!wanted) {
+		wanted = 1;
+		while (f->depth * wavefront_bytes(((grid_blocks + wanted - 1) / wanted) * 256u, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, f->table_bytes_per_workgroup / 64u) > budget
+			&& (grid_blocks + wanted) / (wanted + 1) >= kMinBandBlocks)
+			++wanted;
+	}
+	f->blocks_per_band = (((grid_blocks + wanted - 1) / wanted) + 7u) & ~7u;
+	if (f->blocks_per_band == 0) f->blocks_per_band = 8;
+	f->band_count = (grid_blocks + f->blocks_per_band - 1) / f->blocks_per_band;
+	if (f->band_count == 0) f->band_count = 1;
+	// The tracing kernels are persistent: a number of waves per SIMD on every CU, each lane strides over the queues.
+	// Small launches (round 5, profiles/r07f): a rank's slab at N = 8 is 4 080 shading waves on 3 072 wave slots.  Its
+	// kernels then last about as long as their slowest wave, and what is launched for a whole frame - 8 192 tracing
+	// waves for 230 k rays, shaft walks of up to 72 steps - is mostly waiting: with 2 tracing waves per SIMD and walks
+	// that give up after 12 steps (more rays traced, a shorter chain of kernels) the slab of config 3 takes 0.177
+	// instead of 0.199 ms, the target shape's 0.070 instead of 0.084; a quarter of the frame (8 160 waves) 0.316
+	// instead of 0.333.  The whole frame (32 640 waves) loses with either: 1.150 -> 1.176 ms with 12 steps.
+	// Otherwise eight waves per SIMD where a lane queues eight rays or more, four where it queues fewer (measured at config 2,
+	// whose 0.9 M rays are a batch or two per wave: 0.129 -> 0.121 ms per frame).
+	const uint32_t compute_units = (uint32_t) (device->compute_unit_count > 0 ? device->compute_unit_count : 256);
+	const uint32_t launch_waves = shade_grid_size(f->blocks_per_band);
+	const uint32_t small_launch_waves = launch_waves < 6144u ? 2u : (launch_waves < 12288u ? 4u : 0u);
+	f->trace_blocks = compute_units * (small_launch_waves ? small_launch_waves : (f->max_terms >= 8u ? 8u : 4u));
+	// (queues of XCD x are only served by workgroups b with b % 8 == x)
+	f->trace_blocks = (f->trace_blocks + 7u) & ~7u;
+	f->p.ray_block = f->ray_mode == kRaysDeferredBlocks ? ray_block_size(f->max_terms) : 0u;
+	f->p.refill_threshold = kRefillThreshold;
+	return 0;
+}
+
+// Orders the frame among the frames in flight: a frame outside the pipeline runs behind all of them (on device->stream); a
+// pipelined one starts afresh at another depth, and its frame streams wait for inputs that changed on device->stream
+static int join_frame_pipeline(application_t* app, frame_plan* f) {
+	shading_pass_t* pass = &app->shading_pass;
+	if (!f->pipelined) {
+		if (finish_frames(app)) return 1;
+		// (no wavefront buffers, but the table in device memory lives with them: context 0)
+		if (!is_deferred(f->ray_mode) && f->table_in_memory && !(f->frames = ensure_frames(pass))) return 1;
+		return 0;
+	}
+	frame_pipeline* frames = f->frames;
+	if (frames->depth != f->depth) {
+		// another pipeline depth: contexts and streams pair up differently, start afresh
+		if (frames->depth && wait_for_device(&app->device)) return 1;
+		for (frame_context& c : frames->contexts) c.recorded = c.pending = false;
+		frames->depth = f->depth;
+		frames->next = 0;
+	}
+	if (pass->inputs_changed) {
+		// Inputs that were produced on device->stream (visibility pass, uploads): all frame
+		// streams wait for them once.  Frames do not wait for anything else on
+		// device->stream - if they did, a consumer of frame k there would hold back frame k + 1.
+		if (hip_failed(hipEventRecord(frames->inputs_ready, (hipStream_t) app->device.stream), "marking the inputs")) return 1;
+		for (uint32_t i = 0; i != f->depth; ++i)
+			if (hip_failed(hipStreamWaitEvent((hipStream_t) app->device.frame_streams[i], frames->inputs_ready, 0), "waiting for the inputs")) return 1;
+		pass->inputs_changed = 0;
+	}
+	return 0;
+}
+
+// The per-pixel materials of a textured scene, which resolve_materials() writes, and the light textures
+static int bind_textures(application_t* app, frame_plan* f) {
+	shading_pass_t* pass = &app->shading_pass;
+	shade_params& p = f->p;
+	size_t needed = sizeof(float) * 8 * (size_t) p.width * p.height;
+	if (f->textured && pass->pixel_materials_size != needed) {
+		if (wait_for_device(&app->device)) return 1;
+		(void) hipFree(pass->pixel_materials);
+		pass->pixel_materials = NULL;
+		pass->pixel_materials_size = 0;
+		if (hip_failed(hipMalloc(&pass->pixel_materials, needed), "allocating the per-pixel materials")) return 1;
+		pass->pixel_materials_size = needed;
 	}
 	// light textures: bound whenever a light asks for one (the technique lives in the constants)
 	for (uint32_t i = 0; i != app->scene_specification.polygonal_light_count; ++i) {
@@ -1102,202 +1145,279 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 		p.light_texture_descriptors = (const uint4*) app->light_textures.descriptors;
 		p.light_texels = (const float4*) app->light_textures.texels;
 	}
+	return 0;
+}
+
+// Band step 1: a band with wavefront rays takes a frame context - the next one in turn, on its frame stream, when the frame
+// is pipelined - and its buffers; the polygon tables in device memory belong to that context or to device->stream
+static int take_frame_context(application_t* app, frame_plan* f, frame_context** out_frame, hipStream_t* stream) {
+	frame_pipeline* frames = f->frames;
+	shade_params& p = f->p;
+	frame_context* frame = NULL;
+	if (is_deferred(f->ray_mode)) {
+		uint32_t index = 0;
+		if (f->pipelined) {
+			index = frames->next;
+			frames->next = (index + 1) % f->depth;
+			*stream = (hipStream_t) app->device.frame_streams[index];
+		}
+		frame = &frames->contexts[index];
+		frames->last = index;
+		if (ensure_wavefront(&frame->buffers, f->blocks_per_band * 256u, f->max_terms, p.light_count, f->hidden_terms, f->base_color, *stream)) return 1;
+		if (f->use_wide_tree && ensure_spill(&frame->buffers, app->scene.acceleration_structure.wide_stack_need, frames->wide_stack_lds, f->trace_blocks * 256u)) return 1;
+		const wavefront_buffers* w = &frame->buffers;
+		p.codes = w->codes; p.terms_visible = w->terms_visible; p.terms_hidden = w->terms_hidden; p.base_color = w->base_color;
+		p.ray_directions = w->ray_directions; p.ray_records = w->ray_records; p.ray_origins = w->ray_origins; p.ray_queue_size = w->ray_queue_size;
+		p.thread_count = w->thread_count; p.max_terms = w->max_terms; p.max_codes = w->max_codes;
+		p.ray_queue_capacity = w->queue_capacity; p.ray_thread_bits = w->thread_bits;
+	}
+	*out_frame = frame;
+	if (f->table_in_memory) {
+		// a region per workgroup of the launch, in the launch's own buffers (shading_kernel.h psa_table_in_memory)
+		wavefront_buffers* owner = frame ? &frame->buffers : &frames->device_stream_buffers;
+		if (ensure_psa_table_memory(owner, (size_t) shade_grid_size(f->blocks_per_band) * f->table_bytes_per_workgroup)) return 1;
+		p.psa_table_memory = owner->psa_table_memory;
+	}
+	app->shading_pass.last_frame_stream = *stream;
+	return 0;
+}
+
+// Band step 2: the band's stream waits for the caller's event, and for the constants, which are uploaded if they changed
+static int upload_band_constants(application_t* app, frame_plan* f, uint32_t band, hipEvent_t caller_event, hipStream_t stream) {
+	// (a target that earlier work of the caller still reads: every stream that writes it waits)
+	if (caller_event && hip_failed(hipStreamWaitEvent(stream, caller_event, 0), "waiting for the caller's event")) return 1;
+	// (wavefront rays: the resolve kernel of the frame's first launch stores the count instead)
+	f->p.first_launch_of_frame = band == 0 ? 1u : 0u;
+	if (band == 0 && f->p.ray_counter && !is_deferred(f->ray_mode) && hip_failed(hipMemsetAsync(f->p.ray_counter, 0, sizeof(unsigned long long), stream), "clearing the ray counter")) return 1;
+	if (upload_constants(app, stream)) return 1;
+	f->p.constants = (const uint8_t*) app->shading_pass.constants_device;
+	return 0;
+}
+
+// Band step 3 (the first band of a textured frame): the materials of every pixel, from the material textures
+static int resolve_materials(application_t* app, shade_params& p, hipStream_t stream) {
+	shading_pass_t* pass = &app->shading_pass;
+	if (g_resolve_launchers[pass->arithmetic_mode](&p, (float*) pass->pixel_materials, stream)) {
+		printf("Launching the material resolve kernel failed.\n");
+		return 1;
+	}
+	p.pixel_materials = (const float*) pass->pixel_materials;
+	return 0;
+}
+
+// light shafts: which patches need no shadow rays toward which lights (light_shafts.h).  For the techniques
+// whose samples aim at the light polygon itself (every ray then lies inside the shaft); the walk uses the
+// four-wide tree whatever tree the rays walk.
+static bool light_shafts_apply(const application_t* app, const frame_plan* f, const frame_context* frame) {
+	const frame_pipeline* frames = f->frames;
+	const uint32_t rays_per_pixel = app->render_settings.sample_count * f->p.light_count * (f->strategy == (int) sampling_strategies_diffuse_only ? 1u : 2u);
+	return frame && (frames->light_shafts == 1u || (frames->light_shafts == 2u && rays_per_pixel >= 8u)) && is_deferred(f->ray_mode) && f->error_mode == kErrorNone
+		&& app->scene.acceleration_structure.wide_nodes && f->p.light_count
+		&& app->scene.acceleration_structure.node_count < (1u << kShaftLightShift)  // (a queue entry of the walk is a node or triangle index and a light)
+		&& aims_at_light_polygon(f->technique);
+}
+
+// The tag of the launch: its geometry AND what its verdicts were derived from - the tree (address, sizes,
+// build time: a scene loaded into the same allocation differs in one of them), the contents of the visibility buffer
+// (a generation counter, bumped by render_visibility_pass / upload_visibility / mark_inputs_changed), the camera and the
+// bytes of the light array in the constants.  When any of them changes no pair rests on a verdict of the old
+// arrangement: ray counts and shaft statistics are then a function of the frame and of how long it has stood still,
+// not of what was rendered before.
+static uint64_t light_shaft_tag(const shading_pass_t* pass, const shade_params& p, const acceleration_structure_t* structure, bool lists, uint32_t inputs_generation) {
+	uint64_t tag = 0xcbf29ce484222325ull;
+	uint32_t build_bits;
+	memcpy(&build_bits, &structure->build_milliseconds, sizeof(build_bits));
+	for (uint64_t word : {(uint64_t) p.first_block, (uint64_t) p.block_count, (uint64_t) p.width, (uint64_t) p.height, (uint64_t) p.tile_size, (uint64_t) p.rank, (uint64_t) p.rank_count,
+			(uint64_t) p.slab_layout, (uint64_t) p.light_count, (uint64_t) (uintptr_t) p.visibility, (uint64_t) lists,
+			(uint64_t) (uintptr_t) structure->wide_nodes, (uint64_t) structure->wide_node_count, (uint64_t) structure->node_count, (uint64_t) build_bits, (uint64_t) inputs_generation})
+		tag = (tag ^ word) * 0x100000001b3ull;
+	const uint8_t* bytes = (const uint8_t*) pass->constants_host;
+	const size_t ranges[3][2] = {{offsetof(per_frame_constants_t, world_to_projection_space), offsetof(per_frame_constants_t, mis_visibility_estimate)},
+		{offsetof(per_frame_constants_t, mesh_dequantization_factor), offsetof(per_frame_constants_t, error_factor)},
+		{sizeof(per_frame_constants_t), pass->constants_size}};
+	for (const size_t* range : ranges)
+		for (size_t i = range[0]; i + 4 <= range[1]; i += 4) {
+			uint32_t word;
+			memcpy(&word, bytes + i, sizeof(word));
+			tag = (tag ^ word) * 0x100000001b3ull;
+		}
+	return tag;
+}
+
+// Band step 4: the shaft kernel of the band where light_shafts_apply(), its tables in p
+static int run_light_shafts(application_t* app, frame_plan* f, frame_context* frame, hipStream_t stream) {
+	shading_pass_t* pass = &app->shading_pass;
+	shade_params& p = f->p;
+	p.shaft_clear = NULL;
+	p.shaft_rectangles = NULL;
+	p.shaft_lists = NULL;
+	if (!light_shafts_apply(app, f, frame)) {
+		pass->last_shaft_groups = 0;
+		return 0;
+	}
+	const frame_pipeline* frames = f->frames;
+	const acceleration_structure_t* structure = &app->scene.acceleration_structure;
+	uint32_t shaft_groups = shade_grid_size(p.block_count);
+	const bool lists = frames->shaft_lists != 0u && kShaftListMax != 0u;
+	if (ensure_shaft_words(&frame->buffers, (size_t) shaft_groups * p.light_count + 8, p.light_count, lists, stream)) return 1;
+	float extent = 0.0f;
+	for (int j = 0; j != 3; ++j) extent = fmaxf(extent, kGridMax / structure->grid_inverse_cell[j]);
+	// (VKR_SHAFT_COUNTERS=1: the walks count their steps into three words behind the table, for get_light_shaft_work())
+	static const bool count_work = getenv("VKR_SHAFT_COUNTERS") != NULL;
+	unsigned long long* work = NULL;
+	if (count_work) {
+		work = (unsigned long long*) (frame->buffers.shaft_clear + (((size_t) shaft_groups * p.light_count + 1u) & ~(size_t) 1u));
+		(void) hipMemsetAsync(work, 0, 3 * sizeof(unsigned long long), stream);
+	}
+	const uint64_t tag = light_shaft_tag(pass, p, structure, lists, frames->inputs_generation);
+	const bool same_launch = frame->buffers.shaft_tag == tag;
+	frame->buffers.shaft_tag = tag;
+	k_light_shafts<<<shaft_groups, 64, 0, stream>>>(p, (const uint4*) structure->wide_nodes, frame->buffers.shaft_clear, frame->buffers.shaft_rectangles, lists ? frame->buffers.shaft_lists : NULL, extent, work, same_launch ? frames->shaft_rest : 0u,
+		// (a small launch lasts as long as its longest walk: plan_bands(), at trace_blocks)
+		frames->shaft_max_steps ? frames->shaft_max_steps : (shaft_groups < 12288u ? kShaftSmallLaunchSteps : kShaftMaxSteps));
+	if (hip_failed(hipGetLastError(), "launching the light shaft kernel")) return 1;
+	p.shaft_clear = frame->buffers.shaft_clear;
+	p.shaft_rectangles = frame->buffers.shaft_rectangles;
+	p.shaft_lists = lists ? frame->buffers.shaft_lists : NULL;
+	pass->last_shaft_groups = shaft_groups;
+	return 0;
+}
+
+// Band step 5: the shading kernel, or the error display's; < 0: no such kernel variant was built
+static int launch_shading(const application_t* app, const frame_plan* f, hipStream_t stream) {
+	const int mode = app->shading_pass.arithmetic_mode;
+	const shade_params* p = &f->p;
+	if (f->error_mode != kErrorNone)
+		return g_error_launchers[mode](has_specular_technique(&app->render_settings), f->technique, f->capacity, f->error_mode, p, p->block_count, stream);
+	return g_launchers[mode + (p->light_texture_descriptors ? 3 : 0)][f->strategy](f->technique, f->capacity, f->ray_mode, p, p->block_count, stream);
+}
+
+// Band step 6: the tracing kernel of the band's queued rays
+static void launch_tracing(const application_t* app, const frame_plan* f, const frame_context* frame, hipStream_t stream) {
+	const frame_pipeline* frames = f->frames;
+	const shade_params& p = f->p;
+	ray_stream rays = {p.ray_directions, p.ray_records, p.ray_origins, p.ray_queue_size, p.ray_queue_capacity, p.ray_thread_bits, p.thread_count};
+	if (f->use_wide_tree) {
+		const uint4* wide_nodes = (const uint4*) app->scene.acceleration_structure.wide_nodes;
+		// single-wave workgroups where a lane queues many rays and the shading kernel runs three waves
+		// per SIMD (wavefront_kernels.h has the measurements)
+		if (f->ray_mode == kRaysDeferredBlocks && f->capacity <= 7) {
+			trace_shadow_rays_wide<64><<<f->trace_blocks * 4u, 64, 0, stream>>>(p.bvh, wide_nodes, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, kLeafBatch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
+		}
+		else {
+			trace_shadow_rays_wide<256><<<f->trace_blocks, 256, 0, stream>>>(p.bvh, wide_nodes, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, kLeafBatch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
+		}
+	}
+	else
+		trace_shadow_rays<<<f->trace_blocks, 256, 0, stream>>>(p.bvh, rays, p.ray_queue_size + kRayQueueCount, p.codes, p.refill_threshold);
+}
+
+// Orders a write of the frame's output on `stream`, in front of the resolve kernel with wavefront rays and in front of the
+// shading kernel otherwise (such a frame is never pipelined)
+static void order_output_write(shading_pass_t* pass, const frame_plan* f, frame_context* frame, uint32_t band, hipStream_t stream) {
+	const void* target = f->p.out_radiance;
+	if (f->pipelined) {
+		frame_pipeline* frames = f->frames;
+		// launches in flight may write the same target: keep their order there
+		// (the launch before this one ran in the context before this one)
+		// (whether device->stream has already been made to wait for that launch - finish_frames() -
+		// says nothing about this stream)
+		frame_context* previous = &frames->contexts[(frames->last + frames->depth - 1u) % frames->depth];
+		// (bands of one frame, and frames that share a target)
+		// (a caller's ring of targets need not have the length of the pipeline: every other context one of whose recent
+		// launches wrote this target comes first)
+		for (uint32_t c = 0; c != frames->depth; ++c) {
+			frame_context* other = &frames->contexts[c];
+			if (other == frame || !other->recorded) continue;
+			bool same = other == previous && band != 0;
+			for (const void* written : other->targets) same = same || written == target;
+			if (same) (void) hipStreamWaitEvent(stream, other->done, 0);
+		}
+		frame->targets[frame->target_cursor++ % 8u] = target;
+		// ... and behind whatever still reads the target on device->stream (output encoding)
+		if (frame->readers_seen != frames->readers_generation) {
+			(void) hipStreamWaitEvent(stream, frames->readers_done, 0);
+			frame->readers_seen = frames->readers_generation;
+		}
+	}
+	wait_for_read_backs_of(pass, target, f->frame_output_bytes, stream);
+}
+
+// Band step 8 (the last band, render_shading_pass_encoded()): the frame or slab as packed RGB8, on the band's stream
+static int encode_frame_rgb8(application_t* app, const frame_plan* f, void* out_rgb8, hipStream_t stream) {
+	// (the resolves of the bands are chained, so the last band's stream has seen them all)
+	uint64_t pixels = f->frame_output_bytes / sizeof(float4);
+	if (pixels % 4 != 0) {
+		printf("The frame cannot be encoded as packed RGB8 (its pixel count has to be a multiple of four).\n");
+		return 1;
+	}
+	wait_for_read_backs_of(&app->shading_pass, out_rgb8, (size_t) pixels * 3u, stream);
+	launch_encode_rgb8(f->p.out_radiance, out_rgb8, pixels, app->screenshot.frame_bits, 0, stream);
+	return hipGetLastError() != hipSuccess;
+}
+
+// out_rgb8: the frame (or slab) is also encoded as packed RGB8 on the stream it was rendered on
+static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
+	shading_pass_t* pass = &app->shading_pass;
+	frame_plan f;
+	if (plan_frame(app, out_radiance, &f)) return 1;
+	shade_params& p = f.p;
+	if (pass->use_ray_tracing) {
+		// (sixteen counters, one per frame in turn: see below)
+		if (!pass->ray_counter && hip_failed(hipMalloc(&pass->ray_counter, 16 * sizeof(unsigned long long)), "allocating the ray counters")) return 1;
+		p.ray_counter = (unsigned long long*) pass->ray_counter;
+	}
+	if ((is_deferred(f.ray_mode) && plan_bands(app, &f)) || join_frame_pipeline(app, &f)) return 1;
+	pass->last_frame_traced_rays = f.ray_mode != kRaysNone;
+	pass->last_frame_in_flight = f.pipelined ? f.depth : 0u;
+	pass->last_band_count = f.band_count;
+	if (bind_textures(app, &f)) return 1;
 	// every timing_stride-th frame is bracketed by events: start, end of the (last band's) shading
 	// kernel, end of the frame (an event record costs about 5 us of idle time on the stream, a tenth
 	// of a config-2 frame for the pair)
-	hipEvent_t* ring = (hipEvent_t*) pass->timing_ring;
-	uint32_t slot = pass->timing_cursor % pass->timing_ring_size;
-	bool timed = pass->timing_stride <= 1 || pass->frame_counter % pass->timing_stride == 0;
+	const uint32_t slot = pass->timing_cursor % pass->timing_ring_size;
+	const bool timed = pass->timing_stride <= 1 || pass->frame_counter % pass->timing_stride == 0;
 	// rays of this frame: one of sixteen counters, taken in turn, so that the bands of this frame never
 	// meet those of a frame that is still in flight (at most eight launches are)
 	if (p.ray_counter) p.ray_counter += pass->frame_counter % 16u;
 	++pass->frame_counter;
 	hipEvent_t caller_event = (hipEvent_t) pass->wait_before_next_frame;
 	pass->wait_before_next_frame = NULL;
-	int status = 0;
+	hipStream_t stream = (hipStream_t) app->device.stream;
 	frame_context* frame = NULL;
-	// bytes of the output this call writes (a slab in slab layout, else the frame): what pending read-backs are checked against
-	const size_t frame_output_bytes = sizeof(float4) * (p.slab_layout ? (size_t) grid_blocks * 256u : (size_t) p.width * p.height);
-	for (uint32_t band = 0; band != band_count && status == 0; ++band) {
-		p.first_block = band * blocks_per_band;
-		p.block_count = grid_blocks - p.first_block < blocks_per_band ? grid_blocks - p.first_block : blocks_per_band;
-		frame = NULL;
-		if (frames && is_deferred(ray_mode)) {
-			uint32_t index = 0;
-			if (pipelined) {
-				index = frames->next;
-				frames->next = (index + 1) % depth;
-				stream = (hipStream_t) device->frame_streams[index];
-			}
-			frame = &frames->contexts[index];
-			frames->last = index;
-			if (ensure_wavefront(&frame->buffers, blocks_per_band * 256u, max_terms, p.light_count, hidden_terms, base_color, stream)) return 1;
-			if (use_wide_tree && ensure_spill(&frame->buffers, app->scene.acceleration_structure.wide_stack_need, frames->wide_stack_lds, trace_blocks * 256u)) return 1;
-			const wavefront_buffers* w = &frame->buffers;
-			p.codes = w->codes; p.terms_visible = w->terms_visible; p.terms_hidden = w->terms_hidden; p.base_color = w->base_color;
-			p.ray_directions = w->ray_directions; p.ray_records = w->ray_records; p.ray_origins = w->ray_origins; p.ray_queue_size = w->ray_queue_size;
-			p.thread_count = w->thread_count; p.max_terms = w->max_terms; p.max_codes = w->max_codes;
-			p.ray_queue_capacity = w->queue_capacity; p.ray_thread_bits = w->thread_bits;
-		}
-		if (table_in_memory) {
-			// a region per workgroup of the launch, in the launch's own buffers (shading_kernel.h psa_table_in_memory)
-			wavefront_buffers* owner = frame ? &frame->buffers : &frames->device_stream_buffers;
-			if (ensure_psa_table_memory(owner, (size_t) shade_grid_size(blocks_per_band) * table_bytes_per_workgroup)) return 1;
-			p.psa_table_memory = owner->psa_table_memory;
-		}
-		pass->last_frame_stream = stream;
-		// (a target that earlier work of the caller still reads: every stream that writes it waits)
-		if (caller_event && hip_failed(hipStreamWaitEvent(stream, caller_event, 0), "waiting for the caller's event")) return 1;
-		// (wavefront rays: the resolve kernel of the frame's first launch stores the count instead)
-		p.first_launch_of_frame = band == 0 ? 1u : 0u;
-		if (band == 0 && p.ray_counter && !is_deferred(ray_mode) && hip_failed(hipMemsetAsync(p.ray_counter, 0, sizeof(unsigned long long), stream), "clearing the ray counter")) return 1;
-		if (upload_constants(app, stream)) return 1;
-		p.constants = (const uint8_t*) pass->constants_device;
+	int status = 0;
+	for (uint32_t band = 0; band != f.band_count && status == 0; ++band) {
+		p.first_block = band * f.blocks_per_band;
+		p.block_count = f.grid_blocks - p.first_block < f.blocks_per_band ? f.grid_blocks - p.first_block : f.blocks_per_band;
+		if (take_frame_context(app, &f, &frame, &stream) || upload_band_constants(app, &f, band, caller_event, stream)) return 1;
 		// (the first event of a timed frame: everything the frame launches lies behind it)
-		if (timed && band == 0) (void) hipEventRecord(ring[kTimingEvents * slot], stream);
-		if (textured && band == 0) {
-			if (g_resolve_launchers[pass->arithmetic_mode](&p, (float*) pass->pixel_materials, stream)) {
-				printf("Launching the material resolve kernel failed.\n");
-				return 1;
-			}
-			p.pixel_materials = (const float*) pass->pixel_materials;
-		}
-		// light shafts: which patches need no shadow rays toward which lights (light_shafts.h).  For the techniques
-		// whose samples aim at the light polygon itself (every ray then lies inside the shaft); the walk uses the
-		// four-wide tree whatever tree the rays walk.
-		p.shaft_clear = NULL;
-		p.shaft_rectangles = NULL;
-		p.shaft_lists = NULL;
-		const uint32_t rays_per_pixel = app->render_settings.sample_count * p.light_count * ((int) app->render_settings.sampling_strategies == (int) sampling_strategies_diffuse_only ? 1u : 2u);
-		if (frame && (frames->light_shafts == 1u || (frames->light_shafts == 2u && rays_per_pixel >= 8u)) && is_deferred(ray_mode) && error_mode == kErrorNone && app->scene.acceleration_structure.wide_nodes && p.light_count
-			&& app->scene.acceleration_structure.node_count < (1u << kShaftLightShift)  // (a queue entry of the walk is a node or triangle index and a light)
-			&& (technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniqueSolidAngle || technique == kTechniqueClippedSolidAngle))
-		{
-			const acceleration_structure_t* structure = &app->scene.acceleration_structure;
-			uint32_t shaft_groups = shade_grid_size(p.block_count);
-			const bool lists = frames->shaft_lists != 0u && kShaftListMax != 0u;
-			if (ensure_shaft_words(&frame->buffers, (size_t) shaft_groups * p.light_count + 8, p.light_count, lists, stream)) return 1;
-			float extent = 0.0f;
-			for (int j = 0; j != 3; ++j) extent = fmaxf(extent, kGridMax / structure->grid_inverse_cell[j]);
-			// (VKR_SHAFT_COUNTERS=1: the walks count their steps into three words behind the table, for get_light_shaft_work())
-			static const bool count_work = getenv("VKR_SHAFT_COUNTERS") != NULL;
-			unsigned long long* work = NULL;
-			if (count_work) {
-				work = (unsigned long long*) (frame->buffers.shaft_clear + (((size_t) shaft_groups * p.light_count + 1u) & ~(size_t) 1u));
-				(void) hipMemsetAsync(work, 0, 3 * sizeof(unsigned long long), stream);
-			}
-			// The tag of the launch: its geometry AND what its verdicts were derived from - the tree (address, sizes,
-			// build time: a scene loaded into the same allocation differs in one of them), the contents of the visibility buffer
-			// (a generation counter, bumped by render_visibility_pass / upload_visibility / mark_inputs_changed), the camera and the
-			// bytes of the light array in the constants.  When any of them changes no pair rests on a verdict of the old
-			// arrangement: ray counts and shaft statistics are then a function of the frame and of how long it has stood still,
-			// not of what was rendered before.
-			uint64_t tag = 0xcbf29ce484222325ull;
-			uint32_t build_bits;
-			memcpy(&build_bits, &structure->build_milliseconds, sizeof(build_bits));
-			for (uint64_t word : {(uint64_t) p.first_block, (uint64_t) p.block_count, (uint64_t) p.width, (uint64_t) p.height, (uint64_t) p.tile_size, (uint64_t) p.rank, (uint64_t) p.rank_count,
-					(uint64_t) p.slab_layout, (uint64_t) p.light_count, (uint64_t) (uintptr_t) p.visibility, (uint64_t) lists,
-					(uint64_t) (uintptr_t) structure->wide_nodes, (uint64_t) structure->wide_node_count, (uint64_t) structure->node_count, (uint64_t) build_bits, (uint64_t) frames->inputs_generation})
-				tag = (tag ^ word) * 0x100000001b3ull;
-			{
-				const uint8_t* bytes = (const uint8_t*) pass->constants_host;
-				const size_t ranges[3][2] = {{offsetof(per_frame_constants_t, world_to_projection_space), offsetof(per_frame_constants_t, mis_visibility_estimate)},
-					{offsetof(per_frame_constants_t, mesh_dequantization_factor), offsetof(per_frame_constants_t, error_factor)},
-					{sizeof(per_frame_constants_t), pass->constants_size}};
-				for (const size_t* range : ranges)
-					for (size_t i = range[0]; i + 4 <= range[1]; i += 4) {
-						uint32_t word;
-						memcpy(&word, bytes + i, sizeof(word));
-						tag = (tag ^ word) * 0x100000001b3ull;
-					}
-			}
-			const bool same_launch = frame->buffers.shaft_tag == tag;
-			frame->buffers.shaft_tag = tag;
-			k_light_shafts<<<shaft_groups, 64, 0, stream>>>(p, (const uint4*) structure->wide_nodes, frame->buffers.shaft_clear, frame->buffers.shaft_rectangles, lists ? frame->buffers.shaft_lists : NULL, extent, work, same_launch ? frames->shaft_rest : 0u,
-				// (a small launch lasts as long as its longest walk: above, at trace_blocks)
-				frames->shaft_max_steps ? frames->shaft_max_steps : (shaft_groups < 12288u ? kShaftSmallLaunchSteps : kShaftMaxSteps));
-			if (hip_failed(hipGetLastError(), "launching the light shaft kernel")) return 1;
-			p.shaft_clear = frame->buffers.shaft_clear;
-			p.shaft_rectangles = frame->buffers.shaft_rectangles;
-			p.shaft_lists = lists ? frame->buffers.shaft_lists : NULL;
-			pass->last_shaft_groups = shaft_groups;
-		}
-		else pass->last_shaft_groups = 0;
+		if (timed && band == 0) (void) hipEventRecord(timing_event(pass, slot, kTimingFrameStart), stream);
+		if ((f.textured && band == 0 && resolve_materials(app, p, stream)) || run_light_shafts(app, &f, frame, stream)) return 1;
 		// (a frame without wavefront rays writes its output from the shading kernel)
-		if (!is_deferred(ray_mode)) wait_for_read_backs_of(pass, p.out_radiance, frame_output_bytes, stream);
+		if (!is_deferred(f.ray_mode)) order_output_write(pass, &f, frame, band, stream);
 		// (the second event of a timed frame: the shading kernel itself begins here, behind the shaft kernel)
-		if (timed && band == 0) (void) hipEventRecord(ring[kTimingEvents * slot + 1], stream);
-		status = error_mode != kErrorNone
-			? g_error_launchers[pass->arithmetic_mode](strategy >= (int) sampling_strategies_diffuse_specular_separately, technique, capacity, error_mode, &p, p.block_count, stream)
-			: g_launchers[pass->arithmetic_mode + (p.light_texture_descriptors ? 3 : 0)][strategy](technique, capacity, ray_mode, &p, p.block_count, stream);
-		if (timed && band + 1 == band_count) (void) hipEventRecord(ring[kTimingEvents * slot + 2], stream);
-		if (status == 0 && is_deferred(ray_mode)) {
-			ray_stream rays = {p.ray_directions, p.ray_records, p.ray_origins, p.ray_queue_size, p.ray_queue_capacity, p.ray_thread_bits, p.thread_count};
-			if (use_wide_tree) {
-				const uint4* wide_nodes = (const uint4*) app->scene.acceleration_structure.wide_nodes;
-				// single-wave workgroups where a lane queues many rays and the shading kernel runs three waves
-				// per SIMD (wavefront_kernels.h has the measurements)
-				if (ray_mode == kRaysDeferredBlocks && capacity <= 7) {
-					trace_shadow_rays_wide<64><<<trace_blocks * 4u, 64, 0, stream>>>(p.bvh, wide_nodes, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, kLeafBatch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
-				}
-				else {
-					trace_shadow_rays_wide<256><<<trace_blocks, 256, 0, stream>>>(p.bvh, wide_nodes, rays, p.ray_queue_size + kRayQueueCount, p.codes, frame->buffers.spill, kLeafBatch, frames->wide_stack_lds, frames->wide_refill, frames->wide_refill_below);
-				}
-			}
-			else
-				trace_shadow_rays<<<trace_blocks, 256, 0, stream>>>(p.bvh, rays, p.ray_queue_size + kRayQueueCount, p.codes, p.refill_threshold);
-			if (pipelined) {
-				// launches in flight may write the same target: keep their order there
-				// (the launch before this one ran in the context before this one)
-				// (whether device->stream has already been made to wait for that launch - finish_frames() -
-				// says nothing about this stream)
-				frame_context* previous = &frames->contexts[(frames->last + frames->depth - 1u) % frames->depth];
-				// (bands of one frame, and frames that share a target)
-				// (a caller's ring of targets need not have the length of the pipeline: every other context one of whose recent
-				// launches wrote this target comes first)
-				for (uint32_t c = 0; c != frames->depth; ++c) {
-					frame_context* other = &frames->contexts[c];
-					if (other == frame || !other->recorded) continue;
-					bool same = other == previous && band != 0;
-					for (const void* written : other->targets) same = same || written == (const void*) p.out_radiance;
-					if (same) (void) hipStreamWaitEvent(stream, other->done, 0);
-				}
-				frame->targets[frame->target_cursor++ % 8u] = p.out_radiance;
-				// ... and behind whatever still reads the target on device->stream (output encoding)
-				if (frame->readers_seen != frames->readers_generation) {
-					(void) hipStreamWaitEvent(stream, frames->readers_done, 0);
-					frame->readers_seen = frames->readers_generation;
-				}
-			}
-			wait_for_read_backs_of(pass, p.out_radiance, frame_output_bytes, stream);
+		if (timed && band == 0) (void) hipEventRecord(timing_event(pass, slot, kTimingShadingStart), stream);
+		status = launch_shading(app, &f, stream);
+		if (timed && band + 1 == f.band_count) (void) hipEventRecord(timing_event(pass, slot, kTimingShadingEnd), stream);
+		if (status == 0 && is_deferred(f.ray_mode)) {
+			launch_tracing(app, &f, frame, stream);
+			order_output_write(pass, &f, frame, band, stream);
 			resolve_shadow_terms_and_reset<<<p.block_count, 256, 0, stream>>>(p);
 			status = hipGetLastError() != hipSuccess;
 		}
-		if (status == 0 && out_rgb8 && band + 1 == band_count) {
-			// (the resolves of the bands are chained, so the last band's stream has seen them all)
-			// slab layout: every thread of the grid owns a slot; full-frame layout: the pixels
-			uint64_t pixels = p.slab_layout ? (uint64_t) grid_blocks * 256u : (uint64_t) p.width * p.height;
-			if (pixels % 4 != 0) {
-				printf("The frame cannot be encoded as packed RGB8 (its pixel count has to be a multiple of four).\n");
-				status = 1;
-			}
-			else {
-				wait_for_read_backs_of(pass, out_rgb8, (size_t) pixels * 3u, stream);
-				k_encode_output_rgb8<<<(uint32_t) ((pixels / 4 + 255) / 256), 256, 0, stream>>>((const float4*) p.out_radiance, (uint32_t*) out_rgb8, pixels / 4, app->screenshot.frame_bits, 0);
-				status = hipGetLastError() != hipSuccess;
-			}
-		}
-		if (status == 0 && pipelined) {
+		if (status == 0 && out_rgb8 && band + 1 == f.band_count) status = encode_frame_rgb8(app, &f, out_rgb8, stream);
+		// band step 9: later frames that write the same target are ordered behind this event
+		if (status == 0 && f.pipelined) {
 			(void) hipEventRecord(frame->done, stream);
 			frame->pending = frame->recorded = true;
 		}
 	}
 	if (timed) {
-		(void) hipEventRecord(ring[kTimingEvents * slot + 3], stream);
+		(void) hipEventRecord(timing_event(pass, slot, kTimingFrameEnd), stream);
 		++pass->timing_cursor;
 	}
 	if (status < 0) {
-		printf("No kernel variant was built for strategy %d, technique %d, vertex capacity %d.\n", strategy, technique, capacity);
+		printf("No kernel variant was built for strategy %d, technique %d, vertex capacity %d.\n", f.strategy, f.technique, f.capacity);
 		return 1;
 	}
 	if (status > 0) {
@@ -1309,65 +1429,54 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 	return 0;
 }
 
-extern "C" uint32_t get_dispatch_milliseconds(application_t* app, float* out, uint32_t count) {
-	shading_pass_t* pass = &app->shading_pass;
+// timed frames whose events are still in the ring
+static uint32_t timed_frames(const shading_pass_t* pass) { return pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size; }
+
+// slot of the i-th of the most recent `count` timed frames
+static uint32_t timing_slot(const shading_pass_t* pass, uint32_t count, uint32_t i) { return (pass->timing_cursor - count + i) % pass->timing_ring_size; }
+
+// milliseconds from `from` to `to` once `to` has completed (0 if either cannot be read)
+static float elapsed_milliseconds(hipEvent_t from, hipEvent_t to) {
+	float ms = 0.0f;
+	if (hipEventSynchronize(to) != hipSuccess || hipEventElapsedTime(&ms, from, to) != hipSuccess) ms = 0.0f;
+	return ms;
+}
+
+// the time from event `from` to event `to` of each of the most recent `count` timed frames
+static uint32_t get_timed_intervals(application_t* app, uint32_t from, uint32_t to, float* out, uint32_t count) {
+	const shading_pass_t* pass = &app->shading_pass;
 	if (!pass->timing_ring) return 0;
-	hipEvent_t* ring = (hipEvent_t*) pass->timing_ring;
-	uint32_t available = pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size;
-	if (count > available) count = available;
+	if (count > timed_frames(pass)) count = timed_frames(pass);
 	for (uint32_t i = 0; i != count; ++i) {
-		uint32_t slot = (pass->timing_cursor - count + i) % pass->timing_ring_size;
-		float ms = 0.0f;
-		if (hipEventSynchronize(ring[kTimingEvents * slot + 3]) != hipSuccess || hipEventElapsedTime(&ms, ring[kTimingEvents * slot], ring[kTimingEvents * slot + 3]) != hipSuccess) ms = 0.0f;
-		out[i] = ms;
+		uint32_t slot = timing_slot(pass, count, i);
+		out[i] = elapsed_milliseconds(timing_event(pass, slot, from), timing_event(pass, slot, to));
 	}
 	return count;
+}
+
+extern "C" uint32_t get_dispatch_milliseconds(application_t* app, float* out, uint32_t count) {
+	return get_timed_intervals(app, kTimingFrameStart, kTimingFrameEnd, out, count);
 }
 
 // what a timed frame spends before its shading kernel starts: the shaft kernel (and, for textured scenes, the material resolve)
 extern "C" uint32_t get_light_shaft_milliseconds(application_t* app, float* out, uint32_t count) {
-	shading_pass_t* pass = &app->shading_pass;
-	if (!pass->timing_ring) return 0;
-	hipEvent_t* ring = (hipEvent_t*) pass->timing_ring;
-	uint32_t available = pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size;
-	if (count > available) count = available;
-	for (uint32_t i = 0; i != count; ++i) {
-		uint32_t slot = (pass->timing_cursor - count + i) % pass->timing_ring_size;
-		float ms = 0.0f;
-		if (hipEventSynchronize(ring[kTimingEvents * slot + 1]) != hipSuccess || hipEventElapsedTime(&ms, ring[kTimingEvents * slot], ring[kTimingEvents * slot + 1]) != hipSuccess) ms = 0.0f;
-		out[i] = ms;
-	}
-	return count;
+	return get_timed_intervals(app, kTimingFrameStart, kTimingShadingStart, out, count);
 }
 
 extern "C" uint32_t get_shading_kernel_milliseconds(application_t* app, float* out, uint32_t count) {
-	shading_pass_t* pass = &app->shading_pass;
-	if (!pass->timing_ring) return 0;
-	hipEvent_t* ring = (hipEvent_t*) pass->timing_ring;
-	uint32_t available = pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size;
-	if (count > available) count = available;
-	for (uint32_t i = 0; i != count; ++i) {
-		uint32_t slot = (pass->timing_cursor - count + i) % pass->timing_ring_size;
-		float ms = 0.0f;
-		if (hipEventSynchronize(ring[kTimingEvents * slot + 2]) != hipSuccess || hipEventElapsedTime(&ms, ring[kTimingEvents * slot + 1], ring[kTimingEvents * slot + 2]) != hipSuccess) ms = 0.0f;
-		out[i] = ms;
-	}
-	return count;
+	return get_timed_intervals(app, kTimingShadingStart, kTimingShadingEnd, out, count);
 }
 
 extern "C" uint32_t get_frame_period_milliseconds(application_t* app, float* out, uint32_t count) {
 	shading_pass_t* pass = &app->shading_pass;
 	if (!pass->timing_ring || pass->timing_cursor < 2) return 0;
-	hipEvent_t* ring = (hipEvent_t*) pass->timing_ring;
 	uint32_t stride = pass->timing_stride > 1 ? pass->timing_stride : 1;
-	uint32_t available = (pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size) - 1;
+	uint32_t available = timed_frames(pass) - 1;
 	if (count > available) count = available;
 	for (uint32_t i = 0; i != count; ++i) {
-		uint32_t later = (pass->timing_cursor - count + i) % pass->timing_ring_size;
+		uint32_t later = timing_slot(pass, count, i);
 		uint32_t earlier = (later + pass->timing_ring_size - 1) % pass->timing_ring_size;
-		float ms = 0.0f;
-		if (hipEventSynchronize(ring[kTimingEvents * later + 3]) != hipSuccess || hipEventElapsedTime(&ms, ring[kTimingEvents * earlier + 3], ring[kTimingEvents * later + 3]) != hipSuccess) ms = 0.0f;
-		out[i] = ms / (float) stride;
+		out[i] = elapsed_milliseconds(timing_event(pass, earlier, kTimingFrameEnd), timing_event(pass, later, kTimingFrameEnd)) / (float) stride;
 	}
 	return count;
 }
@@ -1630,9 +1739,14 @@ extern "C" int evaluate_device_arithmetic(const device_t* device, uint32_t opera
 	return failed;
 }
 
-extern "C" int get_traversal_statistics(application_t* app, uint64_t out_statistics[6]) {
+// the wavefront buffers of the most recent launch with wavefront rays (the last band of the last frame), or NULL
+static const wavefront_buffers* last_launch_buffers(const application_t* app) {
 	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
-	const wavefront_buffers* w = frames ? &frames->contexts[frames->last].buffers : NULL;
+	return frames ? &frames->contexts[frames->last].buffers : NULL;
+}
+
+extern "C" int get_traversal_statistics(application_t* app, uint64_t out_statistics[6]) {
+	const wavefront_buffers* w = last_launch_buffers(app);
 	if (!w || !w->ray_directions || !app->shading_pass.use_ray_tracing || app->shading_pass.inline_rays) {
 		printf("get_traversal_statistics() needs a frame rendered with wavefront shadow rays.\n");
 		return 1;
@@ -1645,7 +1759,7 @@ extern "C" int get_traversal_statistics(application_t* app, uint64_t out_statist
 
 extern "C" int get_traversal_statistics_of_tree(application_t* app, VkBool32 wide_tree, uint64_t out_statistics[12]) {
 	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
-	const wavefront_buffers* w = frames ? &frames->contexts[frames->last].buffers : NULL;
+	const wavefront_buffers* w = last_launch_buffers(app);
 	const acceleration_structure_t* structure = &app->scene.acceleration_structure;
 	if (!w || !w->ray_directions || !app->shading_pass.use_ray_tracing || app->shading_pass.inline_rays || (wide_tree && !structure->wide_nodes)) {
 		printf("get_traversal_statistics_of_tree() needs a frame rendered with wavefront shadow rays (and the tree it is asked about).\n");
@@ -1681,8 +1795,7 @@ __global__ void __launch_bounds__(256) k_count_clear_shafts(const uint32_t* word
 extern "C" int get_light_shaft_statistics(application_t* app, uint64_t out_statistics[12]) {
 	memset(out_statistics, 0, sizeof(uint64_t) * 12);
 	const shading_pass_t* pass = &app->shading_pass;
-	const frame_pipeline* frames = (const frame_pipeline*) pass->wavefront;
-	const wavefront_buffers* w = frames ? &frames->contexts[frames->last].buffers : NULL;
+	const wavefront_buffers* w = last_launch_buffers(app);
 	if (!w || !pass->last_shaft_groups || !w->shaft_clear) return 0;  // the last frame ran without the shaft test: all zero
 	if (finish_frames(app)) return 1;
 	size_t words = (size_t) pass->last_shaft_groups * app->scene_specification.polygonal_light_count;
@@ -1708,8 +1821,7 @@ extern "C" int get_light_shaft_statistics(application_t* app, uint64_t out_stati
 extern "C" int get_light_shaft_work(application_t* app, uint64_t out_work[3]) {
 	out_work[0] = out_work[1] = out_work[2] = 0;
 	const shading_pass_t* pass = &app->shading_pass;
-	const frame_pipeline* frames = (const frame_pipeline*) pass->wavefront;
-	const wavefront_buffers* w = frames ? &frames->contexts[frames->last].buffers : NULL;
+	const wavefront_buffers* w = last_launch_buffers(app);
 	if (!w || !pass->last_shaft_groups || !w->shaft_clear || !getenv("VKR_SHAFT_COUNTERS") || finish_frames(app)) return 0;
 	size_t words = ((size_t) pass->last_shaft_groups * app->scene_specification.polygonal_light_count + 1u) & ~(size_t) 1u;
 	return vkr_copy_to_host(out_work, w->shaft_clear + words, 3 * sizeof(uint64_t), &app->device);
@@ -1718,8 +1830,7 @@ extern "C" int get_light_shaft_work(application_t* app, uint64_t out_work[3]) {
 // (diagnostics) the verdict words of the most recent launch, [patch][light]; returns how many were written
 extern "C" uint64_t read_back_light_shafts(application_t* app, uint32_t* out_words, uint64_t capacity) {
 	const shading_pass_t* pass = &app->shading_pass;
-	const frame_pipeline* frames = (const frame_pipeline*) pass->wavefront;
-	const wavefront_buffers* w = frames ? &frames->contexts[frames->last].buffers : NULL;
+	const wavefront_buffers* w = last_launch_buffers(app);
 	if (!w || !pass->last_shaft_groups || !w->shaft_clear || finish_frames(app)) return 0;
 	uint64_t words = (uint64_t) pass->last_shaft_groups * app->scene_specification.polygonal_light_count;
 	if (words > capacity) words = capacity;
@@ -1754,14 +1865,7 @@ __global__ void __launch_bounds__(256) k_assemble_frame(const PIXEL* slabs, PIXE
 template <typename PIXEL>
 static int assemble_slabs(application_t* app, const void* gathered_slabs, void* out_frame, hipStream_t stream) {
 	shade_params p;
-	memset(&p, 0, sizeof(p));
-	p.width = app->swapchain.extent.width;
-	p.height = app->swapchain.extent.height;
-	uint32_t grid_blocks = 0;
-	application_t first = *app;
-	first.tile_schedule.rank = 0;
-	fill_tile_schedule(p, &first, grid_blocks);
-	uint64_t slab_stride = (uint64_t) grid_blocks * 256;
+	uint64_t slab_stride = slab_tiling(app, 0, p);
 	dim3 grid((p.width + 15) / 16, (p.height + 15) / 16);
 	k_assemble_frame<PIXEL><<<grid, 256, 0, stream>>>((const PIXEL*) gathered_slabs, (PIXEL*) out_frame,
 		p.width, p.height, p.tile_size, p.tiles_x, p.rank_count, slab_stride);
@@ -1799,20 +1903,14 @@ __global__ void __launch_bounds__(256) k_assemble_frame_rgb8(const uint32_t* sla
 
 static int assemble_rgb8_slabs(application_t* app, const void* gathered_slabs, void* out_encoded, hipStream_t stream) {
 	shade_params p;
-	memset(&p, 0, sizeof(p));
-	p.width = app->swapchain.extent.width;
-	p.height = app->swapchain.extent.height;
-	uint32_t grid_blocks = 0;
-	application_t first = *app;
-	first.tile_schedule.rank = 0;
-	fill_tile_schedule(p, &first, grid_blocks);
+	uint64_t slab_stride = slab_tiling(app, 0, p);
 	if (p.tile_size % 4 != 0) {
 		printf("assemble_rgb8_frame_from_slabs() needs a tile size that is a multiple of four.\n");
 		return 1;
 	}
 	dim3 grid((p.width + 255) / 256, (p.height + 3) / 4);
 	k_assemble_frame_rgb8<<<grid, 256, 0, stream>>>((const uint32_t*) gathered_slabs, (uint32_t*) (out_encoded ? out_encoded : app->render_targets.encoded),
-		p.width, p.height, p.tile_size, p.tiles_x, p.rank_count, (uint64_t) grid_blocks * 256);
+		p.width, p.height, p.tile_size, p.tiles_x, p.rank_count, slab_stride);
 	return hip_failed(hipGetLastError(), "assembling the frame");
 }
 
@@ -1936,12 +2034,20 @@ __global__ void __launch_bounds__(256) k_encode_output_rgb8(const float4* radian
 	packed[3 * i + 2] = (p2 >> 16) | (p3 << 8);
 }
 
+static void launch_encode(const void* radiance, void* encoded, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream) {
+	k_encode_output<<<(uint32_t) ((pixel_count + 255) / 256), 256, 0, stream>>>((const float4*) radiance, (uint32_t*) encoded, pixel_count, frame_bits, output_linear_rgb);
+}
+
+// (pixel_count: a multiple of four)
+static void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream) {
+	k_encode_output_rgb8<<<(uint32_t) ((pixel_count / 4 + 255) / 256), 256, 0, stream>>>((const float4*) radiance, (uint32_t*) packed, pixel_count / 4, frame_bits, output_linear_rgb);
+}
+
 extern "C" int encode_output(application_t* app, VkBool32 output_linear_rgb) {
 	if (finish_frames(app)) return 1;
 	uint64_t pixels = (uint64_t) app->swapchain.extent.width * app->swapchain.extent.height;
 	if (!app->render_targets.radiance || !app->render_targets.encoded) return 1;
-	k_encode_output<<<(uint32_t) ((pixels + 255) / 256), 256, 0, (hipStream_t) app->device.stream>>>((const float4*) app->render_targets.radiance, (uint32_t*) app->render_targets.encoded,
-		pixels, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0);
+	launch_encode(app->render_targets.radiance, app->render_targets.encoded, pixels, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0, (hipStream_t) app->device.stream);
 	note_target_reader(app);
 	return hip_failed(hipGetLastError(), "encoding the output");
 }
@@ -1949,8 +2055,7 @@ extern "C" int encode_output(application_t* app, VkBool32 output_linear_rgb) {
 extern "C" int encode_slab(application_t* app, const void* slab_radiance, void* slab_encoded, uint64_t pixel_count, VkBool32 output_linear_rgb) {
 	if (finish_frames(app)) return 1;
 	if (!slab_radiance || !slab_encoded) return 1;
-	k_encode_output<<<(uint32_t) ((pixel_count + 255) / 256), 256, 0, (hipStream_t) app->device.stream>>>((const float4*) slab_radiance, (uint32_t*) slab_encoded,
-		pixel_count, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0);
+	launch_encode(slab_radiance, slab_encoded, pixel_count, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0, (hipStream_t) app->device.stream);
 	note_target_reader(app);
 	return hip_failed(hipGetLastError(), "encoding the slab");
 }
@@ -1961,8 +2066,7 @@ extern "C" int encode_slab_rgb8(application_t* app, const void* slab_radiance, v
 		printf("encode_slab_rgb8() needs buffers and a pixel count that is a multiple of four (slabs are).\n");
 		return 1;
 	}
-	k_encode_output_rgb8<<<(uint32_t) ((pixel_count / 4 + 255) / 256), 256, 0, (hipStream_t) app->device.stream>>>((const float4*) slab_radiance, (uint32_t*) slab_rgb8,
-		pixel_count / 4, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0);
+	launch_encode_rgb8(slab_radiance, slab_rgb8, pixel_count, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0, (hipStream_t) app->device.stream);
 	note_target_reader(app);
 	return hip_failed(hipGetLastError(), "encoding the slab");
 }
