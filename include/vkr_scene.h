@@ -98,7 +98,10 @@ typedef struct acceleration_structure_s {
 		that lie diagonally in their boxes into several leaves (each names the whole triangle; lbvh_build.hip
 		"fragments"; environment VKR_BVH_SPLIT_TRIANGLES=0 turns it off).  node_count = 2 leaf_count - 1. */
 	uint32_t leaf_count;
-	uint32_t reserved;
+	/*! which build of the process this is (1, 2, ...): two structures with the same serial are the same tree, even when a
+		later one was built into the allocations that an earlier one has freed.  What the shading pass keeps from frame
+		to frame because the tree has not changed (the verdicts of its light shafts) is tied to it. */
+	uint32_t build_serial;
 } acceleration_structure_t;
 
 /*! reference scene.h:161-166 */

@@ -343,8 +343,13 @@ VKR_API void* get_next_frame_stream(const application_t* app);
 /*! Makes device->stream wait (on the device, the host does not block) for the frames
 	that are still in flight; a no-op without frames_in_flight >= 2 */
 VKR_API int finish_frames(application_t* app);
-/*! Tell a pass with frames in flight that work queued on device->stream by someone else
-	(not through this library) has changed its inputs - visibility buffer, mesh, tables */
+/*! Tell the pass that work queued on device->stream by someone else (not through this library) has changed
+	its inputs - visibility buffer, mesh, tables.  Frames in flight then wait for device->stream once.  The light
+	shafts rely on it as well, with or without frames in flight: a frame context keeps the verdicts of its previous
+	frame for as long as camera, lights, tree and launch are byte-equal to that frame's, and the CONTENTS of device
+	memory are not among the bytes it can compare.  A caller that rewrites the visibility buffer (or the mesh) in
+	place and does not say so gets shadows of the old contents; render_visibility_pass() and upload_visibility() say
+	so themselves. */
 VKR_API void mark_inputs_changed(application_t* app);
 /*! Number of pixels / floats of one rank's slab for the current schedule */
 VKR_API uint64_t get_slab_pixel_count(const application_t* app, uint32_t rank);

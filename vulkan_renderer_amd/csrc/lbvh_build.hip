@@ -10,6 +10,7 @@
 #include "lbvh.h"
 #include "host/vkr_internal.h"
 #include <hipcub/hipcub.hpp>
+#include <atomic>
 #include <stdlib.h>
 #include <time.h>
 
@@ -1114,6 +1115,9 @@ extern "C" int vkr_build_acceleration_structure(acceleration_structure_t* struct
 	clock_gettime(CLOCK_MONOTONIC, &end);
 	structure->builder = (uint32_t) builder;
 	structure->leaf_count = (structure->node_count + 1u) / 2u;
+	// (ranks of one process build their trees on threads of their own: vkr_multi_gpu)
+	static std::atomic<uint32_t> builds{0};
+	structure->build_serial = builds.fetch_add(1u) + 1u;
 	structure->build_milliseconds = (float) ((double) (end.tv_sec - start.tv_sec) * 1.0e3 + (double) (end.tv_nsec - start.tv_nsec) * 1.0e-6);
 	return 0;
 }

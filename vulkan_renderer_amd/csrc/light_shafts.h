@@ -104,6 +104,20 @@ enum { kShaftClear = 1, kShaftList = 2, kShaftNoPixels = 16, kShaftGeometry = 17
 // camera or light has freed gets its shaft back a few frames late, nothing more.  What the table holds before the first
 // frame is zeros (the host clears it), i.e. "walk".  VKR_SHAFT_REST=0 walks every pair in every frame.
 constexpr uint32_t kShaftRestFrames = 7;
+// Verdicts that are still true.  A verdict is a function of the launch's geometry, the tree, the visibility buffer, the
+// camera and that one light's record, and of nothing else that changes from frame to frame (the noise does, and no
+// verdict reads it).  The host keeps a byte copy of all of them per frame context (shading_pass.hip, shaft_arrangement) and
+// compares - memcmp, not a hash: a wrong "same" would keep a "clear" that is not - and hands the kernel
+//   arrangement_same   everything but the lights is byte-equal to the context's previous launch
+//   same_lights        bit i: so is the record of light i, too (lights beyond 32 never get a bit)
+// A pair whose light has its bit and whose word is kShaftClear, kShaftList or kShaftGeometry is KEPT: the word stays, the
+// occluder list stays where the previous launch wrote it, and the light is not walked.  So is, under the same arrangement,
+// a kShaftNoPixels word, which no light has a say in.  The words of a patch are the first thing its wave reads, and if all
+// of them are kept it leaves before it has loaded a single primitive: a camera that stands still under lights that do -
+// the reference renders hundreds of frames of every experiment that way - pays for a launch and four words per
+// patch.  Resting (above) follows the same bits, per light: a pair rests only on a verdict of the same arrangement and
+// the same light.  kShaftTooLong and kShaftQueueFull are walked again, with whatever lights of their patch are walked too;
+// in other company such a walk may end differently, but never wrongly (as the neighbours of resting lights always could).
 
 struct shaft_patch {
 	uint64_t valid;                     // lanes with a shading position
@@ -219,8 +233,10 @@ VKR_DEV f3 shaft_rectangle_corner(const light_ref& light, float4 rectangle, uint
 // work_counters (diagnostics, may be NULL): [0] steps of the walks, [1] batches of triangles, [2] walks
 // out_lists (may be NULL: then a walk ends at the first triangle in the way): kShaftListMax entries of kShaftListEntry
 // floats per (patch, light), in the order of out_clear - a vertex of the triangle and the two edges that leave it.
-// out_clear is read before it is written: the verdict that this patch and light got when the table was last used (see kShaftResting)
-__global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const uint4* __restrict__ wide_nodes, uint32_t* out_clear, float4* __restrict__ out_rectangles, float* __restrict__ out_lists, float extent, unsigned long long* work_counters, uint32_t rest_frames, uint32_t max_steps) {
+// out_clear is read before it is written: the verdict that this patch and light got when the table was last used (see
+// kShaftResting and "Verdicts that are still true"); arrangement_same / same_lights say which of those words may be leaned
+// on (both 0: none, every pair is walked), rest_frames for how many frames a failed pair rests
+__global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const uint4* __restrict__ wide_nodes, uint32_t* out_clear, float4* __restrict__ out_rectangles, float* __restrict__ out_lists, float extent, unsigned long long* work_counters, uint32_t arrangement_same, uint32_t same_lights, uint32_t rest_frames, uint32_t max_steps) {
 	__shared__ shaft_patch patch;
 	__shared__ shaft_state shafts[kShaftLights];
 	__shared__ uint32_t frontier[kShaftFrontier];
@@ -233,13 +249,7 @@ __global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const
 	const uint32_t b = blockIdx.x;
 	const uint32_t local_block = ((b >> 5) << 3) | (b & 7u);
 	const uint32_t thread = (((b >> 3) & 3u) << 6) | lane;
-	uint32_t px, py;
-	size_t out_index;
-	bool inside = local_block < p.block_count && locate_pixel(p, p.first_block + local_block, thread, px, py, out_index);
-	uint32_t primitive = inside ? p.visibility[(size_t) py * p.width + px] : 0xFFFFFFFFu;
-	bool shaded = primitive != 0xFFFFFFFFu;
 	uint32_t* clear = out_clear + (size_t) b * p.light_count;
-	const uint64_t valid = __ballot(shaded);
 	// What the tests below allow for: shading positions and triangle vertices are a few units in the last place of the
 	// scene's coordinates off the planes they lie on, and so is what the tracing kernels compute with them - 5e-7 of
 	// the extent is ten units in the last place of the largest coordinate.
@@ -248,6 +258,26 @@ __global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const
 		// the rectangles that the shading kernel tests its rays against (the same for every patch: one workgroup writes them)
 		for (uint32_t i = lane; i < p.light_count; i += 64u) out_rectangles[i] = shaft_rectangle(get_light(p, i), margin, 1.0f);
 	}
+	// ---- what the table still knows (one word per lane; bit i of `kept`: light i < 64 keeps its verdict) ----------
+	uint64_t kept = 0;
+	if (arrangement_same != 0u) {
+		bool keep = false;
+		if (lane < p.light_count) {
+			const uint32_t kind = clear[lane] & 0xFFu;
+			const bool same_light = lane < 32u && ((same_lights >> lane) & 1u) != 0u;
+			keep = kind == kShaftNoPixels || (same_light && (kind == kShaftClear || kind == kShaftList || kind == kShaftGeometry));
+		}
+		kept = __ballot(keep);
+		// nothing to find out: the table and the lists hold this frame's verdicts already
+		// (more than 64 lights: the others are never kept, and the patch is looked at)
+		if (p.light_count <= 64u && kept == (~0ull >> (64u - p.light_count))) return;
+	}
+	uint32_t px, py;
+	size_t out_index;
+	bool inside = local_block < p.block_count && locate_pixel(p, p.first_block + local_block, thread, px, py, out_index);
+	uint32_t primitive = inside ? p.visibility[(size_t) py * p.width + px] : 0xFFFFFFFFu;
+	bool shaded = primitive != 0xFFFFFFFFu;
+	const uint64_t valid = __ballot(shaded);
 	if (valid == 0) {
 		for (uint32_t i = lane; i < p.light_count; i += 64u) clear[i] = kShaftNoPixels;
 		return;
@@ -299,8 +329,13 @@ __global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const
 	for (uint32_t chunk = 0; chunk < p.light_count; chunk += kShaftLights) {
 		const uint32_t chunk_lights = min(kShaftLights, p.light_count - chunk);
 		uint32_t alive = 0;  // lights of the chunk whose shafts are still being walked (bit k: light chunk + k)
+		// (bit k: light chunk + k keeps its verdict / may rest on it)
+		const uint32_t chunk_kept = chunk < 64u ? (uint32_t) (kept >> chunk) & ((1u << kShaftLights) - 1u) : 0u;
+		const uint32_t chunk_same = (chunk < 32u && rest_frames != 0u) ? (same_lights >> chunk) & ((1u << kShaftLights) - 1u) : 0u;
 		__syncthreads();    // (the previous chunk's walk is over: the shared state may change)
 		for (uint32_t k = 0; k != chunk_lights; ++k) {
+			// a light whose verdict is kept stays out of the walk, and its word and list stay as they are
+			if ((chunk_kept >> k) & 1u) continue;
 			shaft_state& s = shafts[k];
 			light_ref light = get_light(p, chunk + k);
 			constexpr uint32_t vertex_count = 4;
@@ -310,7 +345,7 @@ __global__ void __launch_bounds__(64) k_light_shafts(const shade_params p, const
 			bool possible = light_vertex_count(light) >= 3u && rectangle.z > rectangle.x && rectangle.w > rectangle.y;
 			// a pair whose last walk met too many triangles rests for a few frames (the same word for every lane)
 			uint32_t resting = 0u;
-			if (rest_frames != 0u) {
+			if ((chunk_same >> k) & 1u) {
 				const uint32_t before = clear[chunk + k], kind = before & 0xFFu, age = (before >> 8) & 0xFFu;
 				if (kind == kShaftTriangle) resting = kShaftResting | (1u << 8);
 				else if (kind == kShaftResting && age < rest_frames) resting = kShaftResting | ((age + 1u) << 8);

@@ -155,9 +155,11 @@ struct wavefront_buffers {
 	// light shafts (light_shafts.h): one word per shading workgroup and light, 1 = no ray of that patch toward that
 	// light can be blocked; allocated when the feature first runs
 	uint32_t* shaft_clear;
-	// which launch the verdicts in shaft_clear belong to (blocks, frame size, tiling, lights): the shaft kernel only leans on
-	// them when the next launch with these buffers is the same one (a band of another part of the frame is not)
-	uint64_t shaft_tag;
+	// what the verdicts in shaft_clear (and the lists in shaft_lists) were derived from: a byte image of the inputs of the
+	// most recent launch with these buffers (shaft_arrangement below), shaft_seen_size bytes of it; 0: the tables hold nothing
+	// to lean on.  The shaft kernel keeps a verdict only while these bytes are the next launch's, too.
+	uint8_t* shaft_seen;
+	size_t shaft_seen_size, shaft_seen_capacity;
 	size_t shaft_words;
 	// ... and per light the plane-space rectangle that the shading kernel tests its rays against
 	float4* shaft_rectangles;
@@ -178,6 +180,7 @@ static void free_wavefront_buffers(wavefront_buffers* w) {
 	(void) hipFree(w->shaft_clear);
 	(void) hipFree(w->shaft_rectangles);
 	(void) hipFree(w->shaft_lists);
+	free(w->shaft_seen);
 	(void) hipFree(w->psa_table_memory);
 	memset(w, 0, sizeof(*w));
 }
@@ -207,8 +210,11 @@ struct frame_pipeline {
 	hipEvent_t readers_done;
 	uint32_t readers_generation;
 	// bumped whenever an input that the frames read from device memory has been rewritten (visibility buffer, scene):
-	// part of the light shafts' tag
+	// part of what the light shafts' verdicts are derived from (shaft_arrangement)
 	uint32_t inputs_generation;
+	// where run_light_shafts() puts the inputs of a launch together before it compares them with the context's copy
+	uint8_t* shaft_scratch;
+	size_t shaft_scratch_capacity;
 	// the polygon tables in device memory (wavefront_buffers::psa_table_memory) of the frames without wavefront rays, which
 	// own no context
 	wavefront_buffers device_stream_buffers;
@@ -249,6 +255,7 @@ static void destroy_wavefront(shading_pass_t* pass) {
 	free_wavefront_buffers(&frames->device_stream_buffers);
 	if (frames->inputs_ready) (void) hipEventDestroy(frames->inputs_ready);
 	if (frames->readers_done) (void) hipEventDestroy(frames->readers_done);
+	free(frames->shaft_scratch);
 	free(frames);
 	pass->wavefront = NULL;
 }
@@ -299,9 +306,10 @@ constexpr uint32_t kRefillThreshold = 0;
 
 static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light_count, bool lists, hipStream_t stream) {
 	size_t list_words = lists ? words * kShaftListMax * kShaftListEntry : 0;
+	// (the tables carry state from frame to frame: whichever of them is allocated anew, the copy of the inputs is forgotten)
 	if (list_words > w->shaft_list_words) {
 		(void) hipFree(w->shaft_lists);
-		w->shaft_lists = NULL; w->shaft_list_words = 0;
+		w->shaft_lists = NULL; w->shaft_list_words = 0; w->shaft_seen_size = 0;
 		if (hipMalloc(&w->shaft_lists, list_words * sizeof(float)) != hipSuccess) {
 			printf("Failed to allocate %.1f MiB for the occluder lists of the light shafts.\n", list_words * 4.0 / 1048576.0);
 			return 1;
@@ -310,7 +318,7 @@ static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light
 	}
 	if (light_count > w->shaft_rectangle_count) {
 		(void) hipFree(w->shaft_rectangles);
-		w->shaft_rectangles = NULL; w->shaft_rectangle_count = 0;
+		w->shaft_rectangles = NULL; w->shaft_rectangle_count = 0; w->shaft_seen_size = 0;
 		if (hipMalloc(&w->shaft_rectangles, sizeof(float4) * light_count) != hipSuccess) {
 			printf("Failed to allocate the rectangles of the light shafts.\n");
 			return 1;
@@ -319,7 +327,7 @@ static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light
 	}
 	if (words <= w->shaft_words) return 0;
 	(void) hipFree(w->shaft_clear);
-	w->shaft_clear = NULL; w->shaft_words = 0; w->shaft_tag = 0;
+	w->shaft_clear = NULL; w->shaft_words = 0; w->shaft_seen_size = 0;
 	if (hipMalloc(&w->shaft_clear, words * sizeof(uint32_t)) != hipSuccess) {
 		printf("Failed to allocate %.1f MiB for the light shafts.\n", words * 4.0 / 1048576.0);
 		return 1;
@@ -1217,31 +1225,71 @@ static bool light_shafts_apply(const application_t* app, const frame_plan* f, co
 		&& aims_at_light_polygon(f->technique);
 }
 
-// The tag of the launch: its geometry AND what its verdicts were derived from - the tree (address, sizes,
-// build time: a scene loaded into the same allocation differs in one of them), the contents of the visibility buffer
-// (a generation counter, bumped by render_visibility_pass / upload_visibility / mark_inputs_changed), the camera and the
-// bytes of the light array in the constants.  When any of them changes no pair rests on a verdict of the old
-// arrangement: ray counts and shaft statistics are then a function of the frame and of how long it has stood still,
-// not of what was rendered before.
-static uint64_t light_shaft_tag(const shading_pass_t* pass, const shade_params& p, const acceleration_structure_t* structure, bool lists, uint32_t inputs_generation) {
-	uint64_t tag = 0xcbf29ce484222325ull;
-	uint32_t build_bits;
-	memcpy(&build_bits, &structure->build_milliseconds, sizeof(build_bits));
-	for (uint64_t word : {(uint64_t) p.first_block, (uint64_t) p.block_count, (uint64_t) p.width, (uint64_t) p.height, (uint64_t) p.tile_size, (uint64_t) p.rank, (uint64_t) p.rank_count,
-			(uint64_t) p.slab_layout, (uint64_t) p.light_count, (uint64_t) (uintptr_t) p.visibility, (uint64_t) lists,
-			(uint64_t) (uintptr_t) structure->wide_nodes, (uint64_t) structure->wide_node_count, (uint64_t) structure->node_count, (uint64_t) build_bits, (uint64_t) inputs_generation})
-		tag = (tag ^ word) * 0x100000001b3ull;
-	const uint8_t* bytes = (const uint8_t*) pass->constants_host;
-	const size_t ranges[3][2] = {{offsetof(per_frame_constants_t, world_to_projection_space), offsetof(per_frame_constants_t, mis_visibility_estimate)},
-		{offsetof(per_frame_constants_t, mesh_dequantization_factor), offsetof(per_frame_constants_t, error_factor)},
-		{sizeof(per_frame_constants_t), pass->constants_size}};
-	for (const size_t* range : ranges)
-		for (size_t i = range[0]; i + 4 <= range[1]; i += 4) {
-			uint32_t word;
-			memcpy(&word, bytes + i, sizeof(word));
-			tag = (tag ^ word) * 0x100000001b3ull;
+// What the verdicts of a launch are derived from, as bytes (light_shafts.h "Verdicts that are still true"): a frame context
+// keeps the image of its most recent launch (wavefront_buffers::shaft_seen) and the next launch is compared with it by
+// memcmp - exactly, not through a hash: "the same" now keeps a "clear" or a list, and a collision would keep a wrong one.
+// The image has two parts.  The ARRANGEMENT is this struct and, behind it, the ranges of the constants that the shading
+// positions are computed from (the camera's, the mesh's de-quantisation); then comes one record per LIGHT, its bytes in
+// the constants.
+// Who changes an input and how that shows here: a BVH build (scene load) gives the tree a new build_serial; whoever
+// rewrites the visibility buffer or another input in device memory - render_visibility_pass, upload_visibility, a caller
+// on its own through mark_inputs_changed() (INTEGRATION.md obliges it to) - bumps inputs_generation; camera, lights and
+// the de-quantisation reach the kernels through write_constants() alone, whose bytes are compared themselves.
+struct shaft_arrangement {
+	uint32_t first_block, block_count, width, height, tile_size, rank, rank_count, tiles_x, tile_count, slab_layout;
+	uint32_t light_count, max_light_vertex_count, lists, groups, max_steps;
+	uint32_t inputs_generation, build_serial, build_bits, node_count, wide_node_count;
+	float extent;
+	uint32_t light_stride;
+	const void *visibility, *positions, *nodes, *triangles, *wide_nodes;
+	float grid_origin[3], grid_inverse_cell[3];
+};
+static_assert(sizeof(shaft_arrangement) == 22 * 4 + 5 * sizeof(void*) + 6 * 4, "no padding: the struct is compared as bytes");
+
+static int grow_bytes(uint8_t** buffer, size_t* capacity, size_t size) {
+	if (*capacity >= size) return 0;
+	uint8_t* grown = (uint8_t*) realloc(*buffer, size);
+	if (!grown) return 1;
+	*buffer = grown;
+	*capacity = size;
+	return 0;
+}
+
+// Puts the image of this launch's inputs together, compares it with the context's copy and keeps it as the new copy.
+// -> arrangement_same, same_lights (bit i: arrangement and light i < 32 are byte-equal to the previous launch's)
+static int compare_shaft_inputs(frame_pipeline* frames, wavefront_buffers* w, const shading_pass_t* pass, const shaft_arrangement& arrangement, bool& arrangement_same, uint32_t& same_lights) {
+	arrangement_same = false;
+	same_lights = 0u;
+	const uint8_t* constants = (const uint8_t*) pass->constants_host;
+	const size_t ranges[2][2] = {{offsetof(per_frame_constants_t, world_to_projection_space), offsetof(per_frame_constants_t, mis_visibility_estimate)},
+		{offsetof(per_frame_constants_t, mesh_dequantization_factor), offsetof(per_frame_constants_t, error_factor)}};
+	const size_t light_bytes = (size_t) arrangement.light_stride * arrangement.light_count;
+	size_t arrangement_bytes = sizeof(shaft_arrangement);
+	for (const size_t* range : ranges) arrangement_bytes += range[1] - range[0];
+	const size_t size = arrangement_bytes + light_bytes;
+	if (grow_bytes(&frames->shaft_scratch, &frames->shaft_scratch_capacity, size) || grow_bytes(&w->shaft_seen, &w->shaft_seen_capacity, size)) {
+		printf("Failed to allocate %zu bytes for the inputs of the light shafts.\n", size);
+		w->shaft_seen_size = 0;
+		return 1;
+	}
+	uint8_t* now = frames->shaft_scratch;
+	memcpy(now, &arrangement, sizeof(arrangement));
+	size_t cursor = sizeof(arrangement);
+	for (const size_t* range : ranges) {
+		memcpy(now + cursor, constants + range[0], range[1] - range[0]);
+		cursor += range[1] - range[0];
+	}
+	memcpy(now + cursor, constants + sizeof(per_frame_constants_t), light_bytes);
+	if (w->shaft_seen_size == size && memcmp(now, w->shaft_seen, arrangement_bytes) == 0) {
+		arrangement_same = true;
+		for (uint32_t i = 0; i != arrangement.light_count && i != 32u; ++i) {
+			const size_t at = arrangement_bytes + (size_t) arrangement.light_stride * i;
+			if (memcmp(now + at, w->shaft_seen + at, arrangement.light_stride) == 0) same_lights |= 1u << i;
 		}
-	return tag;
+	}
+	memcpy(w->shaft_seen, now, size);
+	w->shaft_seen_size = size;
+	return 0;
 }
 
 // Band step 4: the shaft kernel of the band where light_shafts_apply(), its tables in p
@@ -1255,7 +1303,7 @@ static int run_light_shafts(application_t* app, frame_plan* f, frame_context* fr
 		pass->last_shaft_groups = 0;
 		return 0;
 	}
-	const frame_pipeline* frames = f->frames;
+	frame_pipeline* frames = f->frames;
 	const acceleration_structure_t* structure = &app->scene.acceleration_structure;
 	uint32_t shaft_groups = shade_grid_size(p.block_count);
 	const bool lists = frames->shaft_lists != 0u && kShaftListMax != 0u;
@@ -1269,13 +1317,42 @@ static int run_light_shafts(application_t* app, frame_plan* f, frame_context* fr
 		work = (unsigned long long*) (frame->buffers.shaft_clear + (((size_t) shaft_groups * p.light_count + 1u) & ~(size_t) 1u));
 		(void) hipMemsetAsync(work, 0, 3 * sizeof(unsigned long long), stream);
 	}
-	const uint64_t tag = light_shaft_tag(pass, p, structure, lists, frames->inputs_generation);
-	const bool same_launch = frame->buffers.shaft_tag == tag;
-	frame->buffers.shaft_tag = tag;
-	k_light_shafts<<<shaft_groups, 64, 0, stream>>>(p, (const uint4*) structure->wide_nodes, frame->buffers.shaft_clear, frame->buffers.shaft_rectangles, lists ? frame->buffers.shaft_lists : NULL, extent, work, same_launch ? frames->shaft_rest : 0u,
-		// (a small launch lasts as long as its longest walk: plan_bands(), at trace_blocks)
-		frames->shaft_max_steps ? frames->shaft_max_steps : (shaft_groups < 12288u ? kShaftSmallLaunchSteps : kShaftMaxSteps));
-	if (hip_failed(hipGetLastError(), "launching the light shaft kernel")) return 1;
+	// (a small launch lasts as long as its longest walk: plan_bands(), at trace_blocks)
+	const uint32_t max_steps = frames->shaft_max_steps ? frames->shaft_max_steps : (shaft_groups < 12288u ? kShaftSmallLaunchSteps : kShaftMaxSteps);
+	shaft_arrangement arrangement;
+	memset(&arrangement, 0, sizeof(arrangement));
+	arrangement.first_block = p.first_block; arrangement.block_count = p.block_count;
+	arrangement.width = p.width; arrangement.height = p.height;
+	arrangement.tile_size = p.tile_size; arrangement.rank = p.rank; arrangement.rank_count = p.rank_count;
+	arrangement.tiles_x = p.tiles_x; arrangement.tile_count = p.tile_count; arrangement.slab_layout = p.slab_layout;
+	arrangement.light_count = p.light_count; arrangement.max_light_vertex_count = p.max_light_vertex_count;
+	arrangement.lists = lists ? 1u : 0u; arrangement.groups = shaft_groups; arrangement.max_steps = max_steps;
+	arrangement.inputs_generation = frames->inputs_generation;
+	arrangement.build_serial = structure->build_serial;
+	memcpy(&arrangement.build_bits, &structure->build_milliseconds, sizeof(arrangement.build_bits));
+	arrangement.node_count = structure->node_count; arrangement.wide_node_count = structure->wide_node_count;
+	arrangement.extent = extent;
+	arrangement.light_stride = (uint32_t) ((pass->constants_size - sizeof(per_frame_constants_t)) / p.light_count);
+	arrangement.visibility = p.visibility; arrangement.positions = p.positions;
+	arrangement.nodes = p.bvh.nodes; arrangement.triangles = p.bvh.triangles; arrangement.wide_nodes = structure->wide_nodes;
+	for (int j = 0; j != 3; ++j) {
+		arrangement.grid_origin[j] = structure->grid_origin[j];
+		arrangement.grid_inverse_cell[j] = structure->grid_inverse_cell[j];
+	}
+	bool arrangement_same;
+	uint32_t same_lights;
+	if (compare_shaft_inputs(frames, &frame->buffers, pass, arrangement, arrangement_same, same_lights)) return 1;
+	// VKR_SHAFT_REST=0, "every pair is walked in every frame": nothing rests and nothing is kept
+	if (frames->shaft_rest == 0u) { arrangement_same = false; same_lights = 0u; }
+	// (The kernel is launched even when the host expects every verdict to be kept: which pairs still rest, and which walks are
+	// due again, only the table on the device knows.  A launch whose waves read their words and leave: DESIGN.md 4.3.)
+	k_light_shafts<<<shaft_groups, 64, 0, stream>>>(p, (const uint4*) structure->wide_nodes, frame->buffers.shaft_clear, frame->buffers.shaft_rectangles, lists ? frame->buffers.shaft_lists : NULL, extent, work,
+		arrangement_same ? 1u : 0u, same_lights, frames->shaft_rest, max_steps);
+	if (hip_failed(hipGetLastError(), "launching the light shaft kernel")) {
+		// (what the tables hold now is anybody's guess)
+		frame->buffers.shaft_seen_size = 0;
+		return 1;
+	}
 	p.shaft_clear = frame->buffers.shaft_clear;
 	p.shaft_rectangles = frame->buffers.shaft_rectangles;
 	p.shaft_lists = lists ? frame->buffers.shaft_lists : NULL;

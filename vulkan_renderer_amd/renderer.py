@@ -349,6 +349,19 @@ class Renderer(HostScene):
                 # pairs whose rays the shading kernel decides against a handful of triangles, and those triangles
                 "list_pairs": int(out[10]), "listed_triangles": int(out[11])}
 
+    def light_shaft_words(self):
+        """The verdict words of the last launch as a (patches, lights) uint32 array (include/vkr_shading_pass.h
+        read_back_light_shafts); empty when that launch ran without the shaft test"""
+        lights = int(self.app.scene_specification.polygonal_light_count)
+        words = np.zeros(int(self.app.shading_pass.last_shaft_groups) * lights, np.uint32)
+        got = int(self.lib.read_back_light_shafts(C.byref(self.app), words.ctypes.data, words.size)) if words.size else 0
+        return words[:got].reshape(-1, max(lights, 1))
+
+    def mark_inputs_changed(self):
+        """An input of the pass in device memory was rewritten by someone else: frames in flight wait for device->stream
+        once, and no light shaft verdict of an earlier frame is kept"""
+        self.lib.mark_inputs_changed(C.byref(self.app))
+
     # -- multi-GPU exchange (include/vkr_slab_exchange.h) ---------------------------------
     def exchange_id(self):
         """The rendezvous token of a new communicator as 128 bytes (call on one rank, broadcast)."""
