@@ -474,7 +474,7 @@ VKR_API int compare_device_division(const device_t* device, uint32_t first_signi
 	materials_t, acceleration_structure_t, scene_t, scene_specification_t,
 	render_settings_t, per_frame_constants_t, swapchain_t, render_targets_t,
 	screenshot_t, tile_schedule_t, shading_pass_t, application_t, experiment_t,
-	experiment_list_t, slab_exchange_id_t, slab_exchange_t) so that bindings can
+	experiment_list_t, slab_exchange_id_t, slab_exchange_t, frame_statistics_t) so that bindings can
 	check their mirrors.  Returns the number of structs. */
 VKR_API uint32_t get_abi_struct_sizes(uint64_t* sizes, uint32_t capacity);
 

@@ -183,10 +183,19 @@ class SlabExchange(C.Structure):
 
 SLAB_FORMAT = {"rgba32f": 0, "rgb8": 1}
 
+MAX_ACCUMULATED_FRAMES = 8  # VKR_MAX_ACCUMULATED_FRAMES
+
+
+class FrameStatistics(C.Structure):
+    _fields_ = [("pixel_count", C.c_uint64), ("frame_count", C.c_uint64), ("sums", C.c_void_p), ("stream", C.c_void_p),
+                ("source_ready", C.c_void_p), ("resolved", C.c_void_p), ("accumulated", C.c_void_p * (MAX_ACCUMULATED_FRAMES * 2)),
+                ("next_event", C.c_uint32), ("pending", C.c_uint32)]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
-               SlabExchangeId, SlabExchange]
+               SlabExchangeId, SlabExchange, FrameStatistics]
 
 # every symbol include/*.h declares, with (restype, argtypes)
 P = C.POINTER
@@ -282,6 +291,14 @@ SIGNATURES = {
     "all_gather_slabs": (C.c_int, [P(SlabExchange), C.c_void_p, C.c_void_p, C.c_void_p]),
     "finish_slab_exchange": (C.c_int, [P(Application), P(SlabExchange)]),
     "get_slab_exchange_milliseconds": (C.c_uint32, [P(SlabExchange), P(C.c_float)]),
+    "create_frame_statistics": (C.c_int, [P(FrameStatistics), P(Application), C.c_uint64]),
+    "destroy_frame_statistics": (None, [P(FrameStatistics), P(Application)]),
+    "reset_frame_statistics": (C.c_int, [P(FrameStatistics), P(Application)]),
+    "accumulate_frames": (C.c_int, [P(FrameStatistics), P(Application), P(C.c_void_p), C.c_uint32]),
+    "resolve_frame_statistics": (C.c_int, [P(FrameStatistics), P(Application), C.c_void_p, C.c_void_p]),
+    "read_back_frame_statistics": (C.c_int, [P(FrameStatistics), P(Application), C.c_void_p, C.c_void_p]),
+    "sum_squared_differences": (C.c_int, [P(Application), C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_double)]),
+    "sum_frame": (C.c_int, [P(Application), C.c_void_p, C.c_uint64, P(C.c_double)]),
 }
 
 _lib = None

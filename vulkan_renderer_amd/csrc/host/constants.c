@@ -2,6 +2,7 @@
  * src/main.c that feed the shading pass (write_constants :2114-2188, vertex-count
  * helpers :173-216, defaults :232-249, quick_save/quick_load :49-130). */
 #include "vkr_internal.h"
+#include "vkr_frame_statistics.h"
 #include "vkr_experiments.h"
 #include "vkr_slab_exchange.h"
 
@@ -291,7 +292,7 @@ VKR_API uint32_t get_abi_struct_sizes(uint64_t* sizes, uint32_t capacity) {
 		sizeof(scene_t), sizeof(scene_specification_t), sizeof(render_settings_t), sizeof(per_frame_constants_t),
 		sizeof(swapchain_t), sizeof(render_targets_t), sizeof(screenshot_t), sizeof(tile_schedule_t), sizeof(light_textures_t),
 		sizeof(shading_pass_t), sizeof(application_t), sizeof(experiment_t), sizeof(experiment_list_t),
-		sizeof(slab_exchange_id_t), sizeof(slab_exchange_t)};
+		sizeof(slab_exchange_id_t), sizeof(slab_exchange_t), sizeof(frame_statistics_t)};
 	uint32_t count = (uint32_t) VKR_COUNT_OF(all);
 	for (uint32_t i = 0; i != count && i != capacity; ++i) sizes[i] = all[i];
 	return count;

@@ -668,6 +668,23 @@ static void wait_for_read_backs_of(shading_pass_t* pass, const void* target, siz
 	}
 }
 
+// For csrc/frame_statistics.hip, whose kernels read and write targets on streams of their own
+extern "C" void vkr_order_target_write(application_t* app, const void* target, size_t bytes, void* stream) {
+	wait_for_read_backs_of(&app->shading_pass, target, bytes, (hipStream_t) stream);
+}
+
+// Makes `stream` wait for the frames in flight: the most recent frame of every context (earlier frames of a context precede
+// it on the context's stream).  begin_read_back() waits for the most recent frame only, which covers the one buffer that
+// frame wrote; a reader of several frames' targets - an accumulation of a ring - needs them all, and frames that wrote
+// different targets do not wait for each other.
+extern "C" int vkr_order_behind_frames_in_flight(application_t* app, void* stream) {
+	frame_pipeline* frames = (frame_pipeline*) app->shading_pass.wavefront;
+	if (!frames || !app->shading_pass.last_frame_in_flight) return 0;
+	for (frame_context& c : frames->contexts)
+		if (c.recorded && hip_failed(hipStreamWaitEvent((hipStream_t) stream, c.done, 0), "ordering a reader behind the frames in flight")) return 1;
+	return 0;
+}
+
 extern "C" int begin_read_back(application_t* app, uint32_t slot, const void* device_source, uint64_t bytes) {
 	shading_pass_t* pass = &app->shading_pass;
 	if (slot >= kReadBackSlots) {

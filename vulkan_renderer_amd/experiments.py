@@ -4,6 +4,7 @@ experiment, advance_experiments :1948-2016 renders, times and takes the screensh
 
     python -m vulkan_renderer_amd.experiments -e 25 --data-root /path/with/data
     python -m vulkan_renderer_amd.experiments -e 25 --synthetic /tmp/vkr_data
+    python -m vulkan_renderer_amd.experiments -e 25 --data-root /path/with/data --accumulate 1024
 
 Scene files, quicksaves, LTC fits and noise tables are looked up below the data root
 with the reference's relative paths (data/attic.vks, data/quicksaves/..., data/ggx_ltc_fit,
@@ -13,6 +14,7 @@ whole procedure can be exercised without the downloaded assets.  The table, the 
 handling, the screenshot encoders and the file writers are C code in libvkr_shading.so;
 this module only sequences the calls."""
 import argparse
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -50,9 +52,10 @@ def write_synthetic_data_root(root, grid=128, box_count=32):
     return {"fresnel_count": made["fresnel_count"]}
 
 
-def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True):
-    """Renders experiment `index` and stores its screenshot.  Returns a dict with the
-    frame time and the screenshot path, or raises with the library's message."""
+@contextlib.contextmanager
+def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=51, hip_device=0):
+    """A Renderer with experiment `index` applied, its scene, tables, targets and pass created and the visibility pass
+    rendered: yields (renderer, experiment) and closes both afterwards"""
     lib = capi.load()
     table = experiment_table(lib)
     try:
@@ -72,7 +75,6 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
                     r.set_lights(synthetic.config_lights(2))
                     cam = synthetic.DEFAULT_CAMERA
                     r.set_camera(cam["position"], cam["rotation_x"], cam["rotation_z"], cam["vertical_fov"], cam["near"], cam["far"])
-            wants_rays = bool(settings.trace_shadow_rays)
             r.load_scene(C.string_at(spec.file_path).decode(), C.string_at(spec.texture_path).decode(), acceleration_structure=True)
             r.load_ltc_table(os.path.join(data_root, "data", "ggx_ltc_fit"), fresnel_count)
             cwd = os.getcwd()
@@ -87,33 +89,61 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
             r.create_targets()
             r.create_pass()
             r.render_visibility()
-            for _ in range(warmup):
-                r.render()
-            r.sync()
-            for _ in range(frames):
-                r.render()
-            r.sync()
-            times = sorted(r.dispatch_ms(frames))
-            frame_ms = times[len(times) // 2]
-            screenshot = C.string_at(experiment.screenshot_path).decode()
-            if hdr:
-                screenshot = screenshot[:-3] + "hdr"
-            pointer = lib.format_screenshot_path(os.path.join(data_root, screenshot).encode(), frame_ms)
-            path = C.string_at(pointer).decode()
-            C.CDLL(None).free(C.c_void_p(pointer))
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            if lib.take_screenshot(C.byref(r.app), None if hdr else path.encode(), path.encode() if hdr else None):
-                raise RuntimeError("take_screenshot failed for %s" % path)
-            result = {"index": index, "frame_ms": frame_ms, "screenshot": path, "width": r.app.swapchain.extent.width,
-                      "height": r.app.swapchain.extent.height, "rays": bool(wants_rays and r.app.shading_pass.use_ray_tracing),
-                      "Msamples_per_s": r.app.swapchain.extent.width * r.app.swapchain.extent.height * settings.sample_count / (frame_ms * 1e-3) / 1e6}
-            if verbose:
-                print(result)
-            return result
+            yield r, experiment
         finally:
             r.close()
     finally:
         lib.destroy_experiment_list(C.byref(table))
+
+
+def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0):
+    """Renders experiment `index` and stores its screenshot.  Returns a dict with the
+    frame time and the screenshot path, or raises with the library's message.
+    accumulate = n > 0: the screenshot holds the mean of n further frames with animated noise (summed on the device,
+    include/vkr_frame_statistics.h) instead of the last frame; "accumulate_seed" of the result is the noise seed
+    (noise_table_t.random_seed) of the first of them."""
+    lib = capi.load()
+    with experiment_renderer(index, data_root, synthetic_inputs, fresnel_count, hip_device) as (r, experiment):
+        settings = r.app.render_settings
+        wants_rays = bool(settings.trace_shadow_rays)
+        for _ in range(warmup):
+            r.render()
+        r.sync()
+        for _ in range(frames):
+            r.render()
+        r.sync()
+        times = sorted(r.dispatch_ms(frames))
+        frame_ms = times[len(times) // 2]
+        accumulate_seed = None
+        if accumulate > 0:
+            accumulate_seed = int(r.app.noise_table.random_seed)
+            animate_before = settings.animate_noise
+            settings.animate_noise = 1
+            statistics = r.create_statistics()
+            for _ in range(accumulate):
+                r.render()
+                statistics.accumulate()
+            # the converged image takes the place of the last frame: the screenshot path below is the usual one
+            statistics.resolve(r.app.render_targets.radiance, None)
+            statistics.close()
+            settings.animate_noise = animate_before
+        screenshot = C.string_at(experiment.screenshot_path).decode()
+        if hdr:
+            screenshot = screenshot[:-3] + "hdr"
+        pointer = lib.format_screenshot_path(os.path.join(data_root, screenshot).encode(), frame_ms)
+        path = C.string_at(pointer).decode()
+        C.CDLL(None).free(C.c_void_p(pointer))
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        if lib.take_screenshot(C.byref(r.app), None if hdr else path.encode(), path.encode() if hdr else None):
+            raise RuntimeError("take_screenshot failed for %s" % path)
+        result = {"index": index, "frame_ms": frame_ms, "screenshot": path, "width": r.app.swapchain.extent.width,
+                  "height": r.app.swapchain.extent.height, "rays": bool(wants_rays and r.app.shading_pass.use_ray_tracing),
+                  "Msamples_per_s": r.app.swapchain.extent.width * r.app.swapchain.extent.height * settings.sample_count / (frame_ms * 1e-3) / 1e6}
+        if accumulate > 0:
+            result.update({"accumulated_frames": int(accumulate), "accumulate_seed": accumulate_seed})
+        if verbose:
+            print(result)
+        return result
 
 
 def main(argv=None):
@@ -123,6 +153,7 @@ def main(argv=None):
     ap.add_argument("--synthetic", metavar="DIR", default=None, help="write a generated stand-in data root to DIR and use it")
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--hdr", action="store_true", help="store *.hdr instead of *.png (take_hdr_screenshots of the reference)")
+    ap.add_argument("--accumulate", type=int, default=0, metavar="N", help="store the mean of N frames with animated noise instead of the last frame")
     args = ap.parse_args(argv)
     lib = capi.load()
     if args.experiment is None:
@@ -136,7 +167,7 @@ def main(argv=None):
     if args.synthetic:
         root = args.synthetic
         fresnel_count = write_synthetic_data_root(root)["fresnel_count"]
-    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr)
+    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate)
     return 0
 
 

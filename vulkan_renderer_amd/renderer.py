@@ -503,6 +503,108 @@ class Renderer(HostScene):
         if self.lib.assemble_frame_from_slabs(C.byref(self.app), gathered_pointer, out_pointer):
             raise RuntimeError("assemble_frame_from_slabs failed")
 
+    # -- frame statistics (include/vkr_frame_statistics.h) ---------------------------------
+    def create_statistics(self, pixel_count=None):
+        """Per-pixel sums of frames on the device; pixel_count None: the frame of the swapchain extent"""
+        return FrameStatistics(self, pixel_count)
+
+    def squared_error(self, a, b, pixel_count):
+        """Sum over pixels of (a - b)^2 per R, G, B for two RGBA32F device buffers, as three doubles"""
+        out = (C.c_double * 3)()
+        if self.lib.sum_squared_differences(C.byref(self.app), a, b, pixel_count, out):
+            raise RuntimeError("sum_squared_differences failed")
+        return np.array(out[:], np.float64)
+
+    def frame_sum(self, a, pixel_count):
+        """Sum over pixels per R, G, B of an RGBA32F device buffer, as three doubles"""
+        out = (C.c_double * 3)()
+        if self.lib.sum_frame(C.byref(self.app), a, pixel_count, out):
+            raise RuntimeError("sum_frame failed")
+        return np.array(out[:], np.float64)
+
+    def close(self):
+        for statistics in list(getattr(self, "_statistics", ())):
+            statistics.close()
+        super().close()
+
+
+class FrameStatistics:
+    """Renderer.create_statistics(): sums of frames in binary64 on the device, mean and variance from them.  mean() and
+    variance() return numpy arrays (pixels, 4); mean_into() / variance_into() write device buffers instead."""
+
+    def __init__(self, owner, pixel_count=None):
+        self.owner = owner
+        self.lib = owner.lib
+        self.stats = capi.FrameStatistics()
+        if self.lib.create_frame_statistics(C.byref(self.stats), C.byref(owner.app), int(pixel_count or 0)):
+            raise RuntimeError("create_frame_statistics failed")
+        if not hasattr(owner, "_statistics"):
+            owner._statistics = []
+        owner._statistics.append(self)
+        self._hip = C.CDLL("libamdhip64.so")
+        self._scratch = C.c_void_p()
+
+    @property
+    def pixel_count(self):
+        return int(self.stats.pixel_count)
+
+    @property
+    def frame_count(self):
+        return int(self.stats.frame_count)
+
+    def accumulate(self, pointers=None):
+        """Adds the RGBA32F device buffers `pointers` (1 ... 8 addresses, in that order) with one kernel; None: the
+        radiance target.  Returns at once."""
+        if pointers is None:
+            array, count = None, 1
+        else:
+            values = [int(getattr(p, "value", p) or 0) for p in pointers]
+            array, count = (C.c_void_p * len(values))(*values), len(values)
+        if self.lib.accumulate_frames(C.byref(self.stats), C.byref(self.owner.app), array, count):
+            raise RuntimeError("accumulate_frames failed")
+
+    def resolve(self, mean_pointer=None, variance_pointer=None):
+        """Writes mean and / or variance into RGBA32F device buffers (resolve_frame_statistics)"""
+        if self.lib.resolve_frame_statistics(C.byref(self.stats), C.byref(self.owner.app), mean_pointer, variance_pointer):
+            raise RuntimeError("resolve_frame_statistics failed")
+
+    def _resolved(self, want_variance):
+        nbytes = 16 * self.pixel_count
+        if not self._scratch and self._hip.hipMalloc(C.byref(self._scratch), C.c_size_t(nbytes)):
+            raise RuntimeError("out of device memory for the resolved statistics")
+        self.resolve(None if want_variance else self._scratch, self._scratch if want_variance else None)
+        out = np.zeros((self.pixel_count, 4), np.float32)
+        # (ordered behind the resolve on the device's stream)
+        if self.lib.wait_for_device(C.byref(self.owner.app.device)) or self._hip.hipMemcpy(C.c_void_p(out.ctypes.data), self._scratch, C.c_size_t(nbytes), 2):
+            raise RuntimeError("reading the resolved statistics back failed")
+        return out
+
+    def mean(self):
+        return self._resolved(False)
+
+    def variance(self):
+        return self._resolved(True)
+
+    def sums(self):
+        """(S, Q): the accumulators as float64 arrays (pixels, 3)"""
+        sums, squares = np.zeros((self.pixel_count, 3), np.float64), np.zeros((self.pixel_count, 3), np.float64)
+        if self.lib.read_back_frame_statistics(C.byref(self.stats), C.byref(self.owner.app), sums.ctypes.data, squares.ctypes.data):
+            raise RuntimeError("read_back_frame_statistics failed")
+        return sums, squares
+
+    def reset(self):
+        if self.lib.reset_frame_statistics(C.byref(self.stats), C.byref(self.owner.app)):
+            raise RuntimeError("reset_frame_statistics failed")
+
+    def close(self):
+        if self.stats.sums:
+            self.lib.destroy_frame_statistics(C.byref(self.stats), C.byref(self.owner.app))
+        if self._scratch:
+            self._hip.hipFree(self._scratch)
+            self._scratch = C.c_void_p()
+        if self in getattr(self.owner, "_statistics", ()):
+            self.owner._statistics.remove(self)
+
 
 def frames_in_flight_for(rank_count):
     """Depth of the frame pipeline that bench.py and profiles/tools/predict_scaling.py use when the frame is tiled over
