@@ -36,4 +36,53 @@ VKR_API void destroy_noise_table(noise_table_t* noise, const device_t* device);
 /*! reference noise_table.h:89 / noise_table.c:161-168 */
 VKR_API void set_noise_constants(uint32_t resolution_mask[2], uint32_t* texture_index_mask, uint32_t random_numbers[4], noise_table_t* noise, VkBool32 animate_noise);
 
+/* ---- tables generated on the device (no reference counterpart: the reference reads these tables from downloaded blobs) ----
+
+   generate_noise_table() fills device_data by HIP kernels (csrc/noise_generators.hip, on device->stream), host_data by one
+   read-back, sets resolution and random_seed = 3124705 like load_noise_table() and returns 0.  It returns 1 after printing
+   one line, with the struct zeroed, for: device == NULL (there is no host build of the generators), noise_type_white
+   (load_noise_table() generates it), noise_type_ahmed and noise_type_blue_noise_dithered (blob types), and resolutions
+   outside the ranges below.  The rules that follow, the order of operations included, are the interface: the numpy
+   restatement vulkan_renderer_amd/noise_tables.py gives the same bytes.  wang() is vkr_wang_random_number (reference
+   math_utilities.h:50-57); all integers are uint32_t.
+
+   noise_type_sobol, noise_type_owen, noise_type_burley_owen (W = H = 2^m, 2 <= m <= 12, D a power of two,
+   2 D W H <= 2^32): layer k, channel pair p (0: RG, 1: BA) holds the points i = (2 k + p) W H + j, j = 0 ... W H - 1, of the
+   4D Sobol sequence in plain index order: c_d = XOR of v_d[b] over the set bits b of i.  Dimension 0 is van der Corput,
+   v[b] = 2^(31 - b); dimensions 1 ... 3 take Joe and Kuo's (s, a, m) = (1, 0, {1}), (2, 1, {1, 3}), (3, 1, {1, 3, 1}):
+   v[b] = m_b 2^(31 - b) for b < s, else v[b] = v[b - s] ^ (v[b - s] >> s) ^ XOR over j = 1 ... s - 1 of a_j v[b - j], a_1 the
+   most significant of the s - 1 bits of a.  With c'_d the scrambled coordinate, the point is written to the texel
+   x = c'_0 >> (32 - m), y = c'_1 >> (32 - m): first channel of the pair c'_2 >> 16, second c'_3 >> 16.  Dimensions 0 and 1
+   are a (0,2)-sequence and both scramblings keep that, so a block of W H points writes every texel exactly once.
+   Scrambling, with seed_d = wang(generator_seed + 0x9E3779B9 * (d + 1)):
+     sobol        c' = c (the seed is ignored)
+     owen         nested uniform scrambling: bit b of c', counted from the most significant (b = 0), is bit b of c, flipped
+                  iff the top bit of wang(wang((1 << b) | (c >> (32 - b))) ^ seed_d) is set (c >> 32 is 0)
+     burley_owen  c' = reverse_bits(laine_karras(reverse_bits(c), seed_d)) with laine_karras(x, s): x += s;
+                  x ^= x * 0x6c50b47c; x ^= x * 0xb82f1e52; x ^= x * 0xc7afe638; x ^= x * 0x8d22f6e6.  The index is not
+                  shuffled: that would move points between the blocks of W H indices.
+
+   noise_type_blue (W and H powers of two in 4 ... 128, D a power of two): channel c of layer k is the void-and-cluster
+   dither array number a = 4 k + c; arrays are independent.  N = W H, n1 = N / 10 (rounded down).  Energies are float32;
+   a pixel set or cleared adds or subtracts K[(y - py) mod H][(x - px) mod W] at every pixel (x, y), one operation per
+   pixel, nothing contracted or reordered, where K[dy][dx] = (float) exp(-(tx^2 + ty^2) / (2 * 1.5^2)) in double with the
+   toroidal distances tx = min(dx, W - dx), ty = min(dy, H - dy).  The tightest cluster is the one with the largest energy,
+   the largest void the zero with the smallest; ties go to the lowest pixel index y W + x.
+     1. The ones are the n1 pixels with the smallest (key, pixel), key = wang(wang(wang(generator_seed) + a) + pixel); their
+        energy is added in ascending pixel order, starting from 0.
+     2. Relax: the tightest cluster is removed, then the largest void is looked for.  If it is the pixel just removed, or
+        this was round N, the pixel is put back (its energy added again) and the relaxation ends; otherwise the void is set.
+     3. On a copy of pattern and energies, for r = n1 - 1 ... 0: the tightest cluster gets rank r and is removed.
+     4. From the relaxed pattern, for r = n1 ... N / 2 - 1: the largest void gets rank r and is set.
+     5. The pattern is inverted, the energy of the new ones added in ascending pixel order starting from 0; for
+        r = N / 2 ... N - 1: the tightest cluster gets rank r and is removed.
+   The texel is (rank * 65536 + 32768) / N, rounded down.  (At 4x4 n1 is 1 and step 2 moves the single one to pixel 0:
+   all arrays of a 4x4 table are equal.) */
+VKR_API int generate_noise_table(noise_table_t* noise, const device_t* device, VkExtent3D resolution,
+                                 noise_type_t noise_type, uint32_t generator_seed);
+/* raw RGBA16 layer-major blob, the reference's format (src/noise_table.c:96-105); path NULL: the reference's own
+   file name for this type and resolution below the working directory (data/noise/..., the directories are created), so
+   that load_noise_table() - and the reference itself - can read it back.  Returns 0 on success, 1 after printing one line */
+VKR_API int write_noise_table(const noise_table_t* noise, noise_type_t noise_type, const char* file_path);
+
 #endif

@@ -218,6 +218,8 @@ SIGNATURES = {
     "get_default_noise_resolution": (Extent3D, [C.c_int32]),
     "load_noise_table": (C.c_int, [P(NoiseTable), P(Device), Extent3D, C.c_int32]),
     "destroy_noise_table": (None, [P(NoiseTable), P(Device)]),
+    "generate_noise_table": (C.c_int, [P(NoiseTable), P(Device), Extent3D, C.c_int32, C.c_uint32]),
+    "write_noise_table": (C.c_int, [P(NoiseTable), C.c_int32, C.c_char_p]),
     "set_noise_constants": (None, [P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(NoiseTable), C.c_uint32]),
     "get_material_texture_suffix": (C.c_char_p, [C.c_int32]),
     "load_scene": (C.c_int, [P(Scene), P(Device), C.c_char_p, C.c_char_p, C.c_uint32]),

@@ -3,7 +3,8 @@
     python -m vulkan_renderer_amd.convergence --config 3 --frames 256 --reference-frames 4096 \\
         --strategy diffuse_specular_mis diffuse_specular_separately --heuristic balance optimal_clamped
 
-renders, for every requested combination of sampling technique, strategy, MIS heuristic and arithmetic mode, `--frames`
+renders, for every requested combination of sampling technique, strategy, MIS heuristic, arithmetic mode and noise table
+(`--noise white owen blue ...`: every type but white is generated on the device, include/vkr_noise_table.h), `--frames`
 frames with animated noise and prints one JSON line: milliseconds per frame, the mean sample variance over pixels and
 channels and the RMSE of the mean of those frames against a converged image (`--reference-frames` frames of the
 configuration's own settings, from another seed).  Frames never leave the GPU: they are summed per pixel in binary64
@@ -19,6 +20,7 @@ import time
 
 import numpy as np
 
+from . import noise_tables
 from . import renderer as renderer_module
 from . import synthetic
 
@@ -106,10 +108,12 @@ def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False)
         app.render_settings.animate_noise = animate_before
 
 
-def _make_renderer(args, dataset, arithmetic, **overrides):
+def _make_renderer(args, dataset, arithmetic, noise="white", **overrides):
     r = renderer_module.Renderer(hip_device=args.device, frames_in_flight=args.frames_in_flight, timing_stride=1 << 30, arithmetic=arithmetic)
     try:
         renderer_module.setup_config(r, args.config, dataset, width=args.width, height=args.height, **overrides)
+        if noise != "white":
+            r.generate_noise_table(noise, seed=args.noise_seed)
         r.create_targets()
         r.create_pass()
         r.render_visibility()
@@ -128,6 +132,8 @@ def main(argv=None):
     ap.add_argument("--strategy", nargs="+", default=[None], choices=sorted(renderer_module.STRATEGY))
     ap.add_argument("--heuristic", nargs="+", default=[None], choices=sorted(renderer_module.MIS))
     ap.add_argument("--arithmetic", nargs="+", default=["libm"], choices=sorted(renderer_module.ARITHMETIC_MODES))
+    ap.add_argument("--noise", nargs="+", default=["white"], choices=["white"] + list(noise_tables.GENERATED_TYPES), help="noise tables; all but white are generated on the device at their default resolution")
+    ap.add_argument("--noise-seed", type=int, default=0, help="generator seed of the generated tables")
     ap.add_argument("--sample-count", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -146,15 +152,15 @@ def main(argv=None):
                 reference = measure(r, args.reference_frames, seed=args.reference_seed, return_mean=True)["mean"]
             finally:
                 r.close()
-        for technique, strategy, heuristic, arithmetic in itertools.product(args.technique, args.strategy, args.heuristic, args.arithmetic):
+        for technique, strategy, heuristic, arithmetic, noise in itertools.product(args.technique, args.strategy, args.heuristic, args.arithmetic, args.noise):
             overrides = dict(common)
             for key, value in (("polygon_technique", technique), ("sampling_strategies", strategy), ("mis_heuristic", heuristic)):
                 if value is not None:
                     overrides[key] = value
-            line = {"config": args.config, "technique": technique, "strategy": strategy, "heuristic": heuristic, "arithmetic": arithmetic}
+            line = {"config": args.config, "technique": technique, "strategy": strategy, "heuristic": heuristic, "arithmetic": arithmetic, "noise": noise}
             r = None
             try:
-                r = _make_renderer(args, dataset, arithmetic, **overrides)
+                r = _make_renderer(args, dataset, arithmetic, noise, **overrides)
                 extent = r.app.swapchain.extent
                 line.update({"width": extent.width, "height": extent.height, "sample_count": int(r.app.render_settings.sample_count), "reference_frames": args.reference_frames})
                 line.update(measure(r, args.frames, reference, seed=args.seed))

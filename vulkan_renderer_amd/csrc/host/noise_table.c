@@ -1,5 +1,7 @@
 /* Noise tables: reference src/noise_table.c:23-168. */
 #include "vkr_internal.h"
+#include <errno.h>
+#include <sys/stat.h>
 
 uint32_t vkr_wang_random_number(uint32_t seed) {
 	seed = (seed ^ 61u) ^ (seed >> 16);
@@ -66,6 +68,40 @@ int load_noise_table(noise_table_t* noise, const device_t* device, VkExtent3D re
 	}
 	if (device && vkr_device_upload(&noise->device_data, device, noise->host_data, sizeof(uint16_t) * cell_count, "the noise table")) {
 		destroy_noise_table(noise, device);
+		return 1;
+	}
+	return 0;
+}
+
+int write_noise_table(const noise_table_t* noise, noise_type_t noise_type, const char* file_path) {
+	const char* stem = NULL;
+	switch (noise_type) {
+	case noise_type_blue: stem = "data/noise/blue_noise_rgba_%02dx%02d_%02d.blob"; break;
+	case noise_type_sobol: stem = "data/noise/sobol_2d_rgba_%02dx%02d_%02d.blob"; break;
+	case noise_type_owen: stem = "data/noise/owen_2d_rgba_%02dx%02d_%02d.blob"; break;
+	case noise_type_burley_owen: stem = "data/noise/burley_owen_2d_rgba_%02dx%02d_%02d.blob"; break;
+	case noise_type_ahmed: stem = "data/noise/ahmed_2d_rgba_%02dx%02d_%02d.blob"; break;
+	case noise_type_blue_noise_dithered: stem = "data/noise/dithered_2d_rgba_%02dx%02d_%02d.blob"; break;
+	default: break;
+	}
+	if (!noise->host_data || (!file_path && !stem)) {
+		printf("Failed to write a noise table: it needs host data and, without a path, a type that load_noise_table() reads from a file.\n");
+		return 1;
+	}
+	char path[256];
+	if (!file_path) {
+		snprintf(path, sizeof(path), stem, noise->resolution.width, noise->resolution.height, noise->resolution.depth);
+		if ((mkdir("data", 0777) && errno != EEXIST) || (mkdir("data/noise", 0777) && errno != EEXIST)) {
+			printf("Failed to create the directory data/noise below the working directory.\n");
+			return 1;
+		}
+		file_path = path;
+	}
+	size_t cell_count = (size_t) noise->resolution.width * noise->resolution.height * noise->resolution.depth * 4;
+	FILE* file = fopen(file_path, "wb");
+	size_t written = file ? fwrite(noise->host_data, sizeof(uint16_t), cell_count, file) : 0;
+	if (!file || fclose(file) || written != cell_count) {
+		printf("Failed to write the noise file at path %s. Please check path and permissions?\n", file_path);
 		return 1;
 	}
 	return 0;

@@ -5,12 +5,14 @@ experiment, advance_experiments :1948-2016 renders, times and takes the screensh
     python -m vulkan_renderer_amd.experiments -e 25 --data-root /path/with/data
     python -m vulkan_renderer_amd.experiments -e 25 --synthetic /tmp/vkr_data
     python -m vulkan_renderer_amd.experiments -e 25 --data-root /path/with/data --accumulate 1024
+    python -m vulkan_renderer_amd.experiments -e 25 --synthetic /tmp/vkr_data --noise owen
 
 Scene files, quicksaves, LTC fits and noise tables are looked up below the data root
 with the reference's relative paths (data/attic.vks, data/quicksaves/..., data/ggx_ltc_fit,
 data/noise/...).  --synthetic writes a generated stand-in data set (one synthetic scene
 under every scene name, white noise instead of the Ahmed table, default light) so the
-whole procedure can be exercised without the downloaded assets.  The table, the path
+whole procedure can be exercised without the downloaded assets.  --noise TYPE replaces the experiment's noise table by
+one generated on the device (blue, sobol, owen, burley_owen: include/vkr_noise_table.h generate_noise_table).  The table, the path
 handling, the screenshot encoders and the file writers are C code in libvkr_shading.so;
 this module only sequences the calls."""
 import argparse
@@ -53,9 +55,10 @@ def write_synthetic_data_root(root, grid=128, box_count=32):
 
 
 @contextlib.contextmanager
-def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=51, hip_device=0):
+def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=51, hip_device=0, noise=None):
     """A Renderer with experiment `index` applied, its scene, tables, targets and pass created and the visibility pass
-    rendered: yields (renderer, experiment) and closes both afterwards"""
+    rendered: yields (renderer, experiment) and closes both afterwards.  noise: a type that is generated on the device
+    instead of the experiment's table"""
     lib = capi.load()
     table = experiment_table(lib)
     try:
@@ -80,7 +83,11 @@ def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=
             cwd = os.getcwd()
             os.chdir(data_root)  # noise tables are addressed relative to the working directory (noise_table.c)
             try:
-                r.load_noise_table(int(settings.noise_type))
+                if noise is None:
+                    r.load_noise_table(int(settings.noise_type))
+                else:
+                    settings.noise_type = renderer.NOISE[noise]
+                    r.generate_noise_table(noise)
                 # the quicksave may hold textured lights (reference update_application, main.c:1879);
                 # their paths are relative to the working directory too
                 r.create_light_textures()
@@ -96,14 +103,14 @@ def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=
         lib.destroy_experiment_list(C.byref(table))
 
 
-def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0):
+def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None):
     """Renders experiment `index` and stores its screenshot.  Returns a dict with the
     frame time and the screenshot path, or raises with the library's message.
     accumulate = n > 0: the screenshot holds the mean of n further frames with animated noise (summed on the device,
     include/vkr_frame_statistics.h) instead of the last frame; "accumulate_seed" of the result is the noise seed
     (noise_table_t.random_seed) of the first of them."""
     lib = capi.load()
-    with experiment_renderer(index, data_root, synthetic_inputs, fresnel_count, hip_device) as (r, experiment):
+    with experiment_renderer(index, data_root, synthetic_inputs, fresnel_count, hip_device, noise) as (r, experiment):
         settings = r.app.render_settings
         wants_rays = bool(settings.trace_shadow_rays)
         for _ in range(warmup):
@@ -139,6 +146,8 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
         result = {"index": index, "frame_ms": frame_ms, "screenshot": path, "width": r.app.swapchain.extent.width,
                   "height": r.app.swapchain.extent.height, "rays": bool(wants_rays and r.app.shading_pass.use_ray_tracing),
                   "Msamples_per_s": r.app.swapchain.extent.width * r.app.swapchain.extent.height * settings.sample_count / (frame_ms * 1e-3) / 1e6}
+        if noise is not None:
+            result["noise"] = noise
         if accumulate > 0:
             result.update({"accumulated_frames": int(accumulate), "accumulate_seed": accumulate_seed})
         if verbose:
@@ -154,6 +163,7 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--hdr", action="store_true", help="store *.hdr instead of *.png (take_hdr_screenshots of the reference)")
     ap.add_argument("--accumulate", type=int, default=0, metavar="N", help="store the mean of N frames with animated noise instead of the last frame")
+    ap.add_argument("--noise", default=None, choices=["blue", "sobol", "owen", "burley_owen"], help="generate this noise table on the device instead of loading the experiment's")
     args = ap.parse_args(argv)
     lib = capi.load()
     if args.experiment is None:
@@ -167,7 +177,7 @@ def main(argv=None):
     if args.synthetic:
         root = args.synthetic
         fresnel_count = write_synthetic_data_root(root)["fresnel_count"]
-    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate)
+    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise)
     return 0
 
 

@@ -20,7 +20,8 @@ TECHNIQUE = {"baseline": 0, "area_turk": 1, "rectangle_solid_angle_urena": 2, "s
              "biquadratic_cosine_warp_hart": 8, "biquadratic_cosine_warp_clipping_hart": 9,
              "projected_solid_angle_arvo": 10, "solid_angle": 4, "clipped_solid_angle": 5, "projected_solid_angle": 11,
              "projected_solid_angle_biased": 12}
-NOISE = {"white": 0, "blue": 1, "ahmed": 2}
+# noise_type_t (include/vkr_noise_table.h; 3 is noise_type_count)
+NOISE = {"white": 0, "blue": 1, "ahmed": 2, "sobol": 4, "owen": 5, "burley_owen": 6, "blue_noise_dithered": 7}
 # arithmetic_mode_t; and the math mode of the CPU oracle that evaluates the same operations
 ARITHMETIC_MODES = {"libm": 0, "fast": 1, "exact": 2}
 ORACLE_MATH_MODE = {"libm": 0, "fast": 0, "exact": 1}
@@ -269,6 +270,43 @@ class Renderer(HostScene):
     def set_tiles(self, tile_size=16, rank=0, rank_count=1, slab_layout=False):
         t = self.app.tile_schedule
         t.tile_size, t.rank, t.rank_count, t.slab_layout = tile_size, rank, rank_count, int(slab_layout)
+
+    def generate_noise_table(self, noise_type, resolution=None, seed=0):
+        """Replaces the noise table by one generated on the device (include/vkr_noise_table.h generate_noise_table):
+        "blue", "sobol", "owen" or "burley_owen"; resolution None: the default of the type.  Returns the milliseconds
+        the call took (allocation, kernels and read-back).  Frames in flight are finished first: they read the old table."""
+        import time
+        t = _enum(NOISE, noise_type)
+        if self.app.shading_pass.constants_device:
+            self.finish_frames()
+            self.sync()
+        res = self.lib.get_default_noise_resolution(t) if resolution is None else capi.Extent3D(*resolution)
+        self.lib.destroy_noise_table(C.byref(self.app.noise_table), self._dev())
+        start = time.perf_counter()
+        if self.lib.generate_noise_table(C.byref(self.app.noise_table), self._dev(), res, t, int(seed) & 0xFFFFFFFF):
+            raise RuntimeError("generate_noise_table failed")
+        return (time.perf_counter() - start) * 1.0e3
+
+    def write_noise_table(self, noise_type, data_root=None, path=None):
+        """Writes the table as a blob: to `path`, or under the reference's file name below data_root (default: the
+        working directory), where load_noise_table() looks for it.  Returns the path."""
+        import os
+        t = _enum(NOISE, noise_type)
+        cwd = os.getcwd()
+        if path is None and data_root is not None:
+            os.makedirs(data_root, exist_ok=True)
+            os.chdir(data_root)
+        try:
+            if self.lib.write_noise_table(C.byref(self.app.noise_table), t, path.encode() if path else None):
+                raise RuntimeError("write_noise_table failed")
+        finally:
+            os.chdir(cwd)
+        if path is not None:
+            return path
+        from . import noise_tables
+        n = self.app.noise_table.resolution
+        names = {v: k for k, v in NOISE.items()}
+        return os.path.join(data_root or cwd, noise_tables.file_name(names[t], (n.width, n.height, n.depth)))
 
     def upload_visibility(self, visibility):
         v = np.ascontiguousarray(visibility, np.uint32)
