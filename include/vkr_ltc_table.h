@@ -32,4 +32,108 @@ VKR_API int load_ltc_table(ltc_table_t* table, const device_t* device, const cha
 /*! reference ltc_table.h:72 */
 VKR_API void destroy_ltc_table(ltc_table_t* table, const device_t* device);
 
+/* ---- tables fitted on the device (no reference counterpart: the reference reads fit<i>.dat files of its download) ----
+
+   fit_ltc_table() fits a linearly transformed cosine to the specular lobe of every texel by one HIP kernel
+   (csrc/ltc_fit.hip, on device->stream, one wave per chain), reads the fits back and fills *table from them through the
+   code load_ltc_table() uses: a fitted table equals the table loaded from the files write_ltc_table() writes in every
+   uint16_t.  settings NULL: get_default_ltc_fit_settings().  If out_fits is not NULL it receives a malloc'ed array of
+   fresnel_count * R * R * 5 floats in the order of the files (free_ltc_fits() frees it): texel (x, y, i), x the roughness
+   axis, y the inclination axis, i the slice, is at index ((i R + y) R + x) 5.  Its five floats are, with M[row][col] the
+   cosine-to-shading matrix scaled to M[2][2] = 1, (M[0][0], M[2][0], M[1][1], M[0][2], albedo), each the binary64 value
+   rounded to nearest.  Returns 0, or 1 after printing one line, with *table zeroed and *out_fits NULL, for: device == NULL
+   (there is no host build of the fit), resolution or fresnel_count outside 2 ... 256, sample_count not a power of two in
+   8 ... 128, max_iterations == 0, and failures of the device.
+
+   The rules that follow, the order of operations included, are the interface: the numpy restatement
+   vulkan_renderer_amd/ltc_fit.py gives the same bits.  All arithmetic is binary64 with + - * / sqrt, comparisons and fabs,
+   nothing contracted; max(a, b) is a if a > b, else b (so a NaN gives b).  Sums and products of three terms associate to the
+   left: a + b + c is (a + b) + c.  No transcendental function runs on the device: the host computes sin and cos of theta_y and
+   of 2 pi t_b with the C library in binary64 and uploads them.  R = resolution, F = fresnel_count, N = sample_count.
+
+   Texel (x, y, i): t = x / (R - 1), alpha = max(t t, 0.0064) (the GGX roughness; the table axis is sqrt(alpha).  The shader
+   clamps the roughness to 0.0064 and more, so the texels below that only carry interpolation weight, and the float32 BRDF
+   of the shader has no albedo to compare with down there: at 0.0016 its quadrature gives 1.034 for f0 = 1),
+   theta = y / (R - 1) * (pi / 2), replaced by 1.57 unless it is smaller, f0 = i / (F - 1), s = sin(theta), c = cos(theta),
+   V = (s, 0, c), a2 = alpha alpha.  g = sqrt((c - c a2) c + a2), mk = 2 / (c + g).
+
+   f(L) and p(L), reference brdfs.glsl:73-85 and :180-191 with the normal (0, 0, 1):
+     h = (L.x + s, L.y, L.z + c), r = 1 / sqrt(h.x h.x + h.y h.y + h.z h.z), Hx = h.x r, Hz = h.z r, vh = s Hx + c Hz,
+     t = (Hz a2 - Hz) Hz + 1, ggx = a2 / (t t), smith = 0.5 / (L.z g + c sqrt((L.z - L.z a2) L.z + a2)),
+     ch = vh clamped to [0, 1] (1 unless vh < 1, else max(vh, 0)), fl = 1 - ch, fl2 = fl fl,
+     fresnel = f0 + (1 - f0) ((fl2 fl) fl2),
+     f = (((ggx smith) fresnel) (1 / pi)) L.z if L.z > 0, else 0 (the specular term with its 1 / pi, times the cosine),
+     p = (mk (ggx (1 / pi))) 0.25 (the density of the visible normal over 4 V.H; the V.H of :190 cancels).
+
+   Sample grid: t_j = (j + 0.5) / N; sample k = a N + b, k = 0 ... N N - 1, uses (t_a, t_b).  The radial coordinate is warped,
+   u = 1 - (1 - t_a)^2 with the weight W = 2 (1 - t_a) in every sum: with u = t_a the last ring of samples holds the whole
+   tail of the lobe at medium roughness and the albedo is off by up to 8e-3.  q = 1 - t_a:
+     cx = sqrt(1 - q q) cos(2 pi t_b), cy = sqrt(1 - q q) sin(2 pi t_b), cz = q, W = 2 q, the angle being (2 pi) t_b.
+
+   BRDF set, sample_ggx_visible_normal_distribution (brdfs.glsl:122-162) with roughness (alpha, alpha):
+     e = (alpha s, c) / sqrt(alpha s alpha s + c c) (x and z; y is 0), lerp = 0.5 e.z + 0.5,
+     sy = sqrt(1 - cx cx) (1 - lerp) + cy lerp, sz = sqrt(max(1 - (cx cx + sy sy), 0)),
+     n = (e.x sz - e.z sy, cx, e.x sy + e.z sz) if y > 0, else (cx, sy, sz),
+     m = (alpha n.x, alpha n.y, n.z) times 1 / sqrt of its squared length, two = 2 (m.x s + m.z c),
+     L = (two m.x - s, two m.y, two m.z - c).
+   Albedo A = sum((f(L) / p(L)) W) / (N N) over the BRDF set: this is the fifth float of the texel.
+   The objective is normalised by a second estimate, An, that also takes the cosine set, the directions c = (cx, cy, cz),
+   under the balance heuristic: the BRDF set hardly samples the Fresnel ring that is all there is to the lobe at f0 = 0
+   (A is 30 times too small at alpha = 0.02, theta = 0, absolutely 3e-7), and a lobe divided by such an albedo fits nothing.
+   An alone would not do for the albedo: the grid of the cosine set resolves a narrow lobe badly (9e-3 at alpha = 0.0064).
+     wb = (f(L) / (p(L) + max(L.z, 0) (1 / pi))) W per sample of the BRDF set, wc = (f(c) / (p(c) + cz (1 / pi))) W,
+     An = (sum(wb) + sum(wc)) / (N N), ax = (sum(wb L.x) + sum(wc cx)) / (N N), az = (sum(wb L.z) + sum(wc cz)) / (N N),
+   Z = (ax, az) / sqrt(ax ax + az az) if y > 0, else (0, 1) (x and z).
+
+   LTC of a vertex v = (v0, v1, v2): m11 = max(v0, 1e-7); at y = 0 m22 = m11 and m13 = 0, else m22 = max(v1, 1e-7) and
+   m13 = v2: (m11, m22, m13) are the parameters of v.  With X = (Z.z, 0, -Z.x), Y = (0, 1, 0):
+     M00 = m11 Z.z, M02 = m13 Z.z + Z.x, M20 = -(m11 Z.x), M22 = Z.z - m13 Z.x, M11 = m22 (the other entries are 0),
+     det2 = M00 M22 - M02 M20, i00 = M22 / det2, i02 = -M02 / det2, i20 = -M20 / det2, i22 = M00 / det2, i11 = 1 / m22,
+     idet = 1 / fabs(m22 det2),
+     D(L): w = (i00 L.x + i02 L.z, i11 L.y, i20 L.x + i22 L.z), l2 = w.x w.x + w.y w.y + w.z w.z,
+           D = (max(w.z, 0) idet) / (pi (l2 l2)).
+   LTC set: L = (M00 cx + M02 cz, m22 cy, M20 cx + M22 cz) times 1 / sqrt of its squared length.
+   Term of a sample L of either set: den = p(L) + D(L), d = fabs(f(L) / An - D(L)); (((d d) d) / den) W if L.z > 0 and
+   den != 0, else 0.  Objective E(v) = (sum over the BRDF set + sum over the LTC set) / (N N).
+   The fit of v: (M00 / M22, M20 / M22, m22 / M22, M02 / M22, A).
+
+   Every sum (the seven of A, An, ax and az, and of the terms of each set): partial j of 64 adds its samples k = j, j + 64, ... in
+   ascending order, starting from 0; then p[j] += p[j + h] for j < h, h = 32, 16 ... 1; the sum is p[0].  (N >= 8 makes N N a
+   multiple of 64.)
+
+   Minimiser (Nelder and Mead) over v, from a start x0: vertices x0, x0 + 0.05 e_0, x0 + 0.05 e_1, x0 + 0.05 e_2 with their
+   values E, in this order.  Repeat:
+     order: for k = 1, 2, 3, for j = k ... 1: vertices j - 1 and j trade places if E_j < E_(j-1) (ties keep their order);
+     stop if max_iterations iterations were made or E_3 - E_0 < 1e-12;
+     c = (v_0 + v_1 + v_2) / 3, r = c + (c - v_3);
+     if E(r) < E_0: x = c + 2 (c - v_3); v_3 becomes x if E(x) < E(r), else r;
+     else if E(r) < E_2: v_3 becomes r;
+     else if E(r) < E_3: x = c + 0.5 (r - c); v_3 becomes x if E(x) <= E(r), else shrink;
+     else: x = c + 0.5 (v_3 - c); v_3 becomes x if E(x) < E_3, else shrink;
+     shrink: v_k = v_0 + 0.5 (v_k - v_0) for k = 1, 2, 3, each evaluated anew.
+   The result is v_0 after the last ordering.
+
+   Chains: the texels (x, y, i), y = 0 ... R - 1, form one chain.  y = 0 starts from x0 = (alpha, alpha, 0), every other y from
+   the parameters of the result of y - 1; but if E((1, 1, 0)) < E(x0), the plain cosine lobe (1, 1, 0) is the start (at
+   f0 = 0 and small alpha the chain's start lies in the basin of a lobe that is disjoint from the ring).  Chains do not
+   depend on each other. */
+typedef struct ltc_fit_settings_s {
+	/*! R: roughness_count = inclination_count of the table, 2 ... 256 */
+	uint32_t resolution;
+	/*! F: 2 ... 256 */
+	uint32_t fresnel_count;
+	/*! N: each of the two sample sets of the objective has N * N samples; a power of two in 8 ... 128 */
+	uint32_t sample_count;
+	/*! iterations of the minimiser per texel, at least 1 */
+	uint32_t max_iterations;
+} ltc_fit_settings_t;
+/*! 32, 51, 32, 200: the size of the reference's table */
+VKR_API ltc_fit_settings_t get_default_ltc_fit_settings(void);
+VKR_API int fit_ltc_table(ltc_table_t* table, float** out_fits, const device_t* device, const ltc_fit_settings_t* settings);
+VKR_API void free_ltc_fits(float* fits);
+/*! Writes <directory>/fit<i>.dat, i < fresnel_count, in the format load_ltc_table() and the reference read (u64 resolution,
+	then resolution^2 times five floats); the directory is created if its parent exists.  fits as returned by
+	fit_ltc_table().  Returns 0, or 1 after printing one line. */
+VKR_API int write_ltc_table(const float* fits, uint32_t resolution, uint32_t fresnel_count, const char* directory);
+
 #endif

@@ -48,6 +48,10 @@ class LtcTable(C.Structure):
                 ("device_rgba", C.c_void_p), ("device_rg", C.c_void_p), ("constants", LtcConstants)]
 
 
+class LtcFitSettings(C.Structure):
+    _fields_ = [("resolution", C.c_uint32), ("fresnel_count", C.c_uint32), ("sample_count", C.c_uint32), ("max_iterations", C.c_uint32)]
+
+
 class Extent2D(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -215,6 +219,10 @@ SIGNATURES = {
     "get_world_to_projection_space": (None, [P((C.c_float * 4) * 4), P(Camera), C.c_float]),
     "load_ltc_table": (C.c_int, [P(LtcTable), P(Device), C.c_char_p, C.c_uint32]),
     "destroy_ltc_table": (None, [P(LtcTable), P(Device)]),
+    "get_default_ltc_fit_settings": (LtcFitSettings, []),
+    "fit_ltc_table": (C.c_int, [P(LtcTable), P(P(C.c_float)), P(Device), P(LtcFitSettings)]),
+    "free_ltc_fits": (None, [P(C.c_float)]),
+    "write_ltc_table": (C.c_int, [P(C.c_float), C.c_uint32, C.c_uint32, C.c_char_p]),
     "get_default_noise_resolution": (Extent3D, [C.c_int32]),
     "load_noise_table": (C.c_int, [P(NoiseTable), P(Device), Extent3D, C.c_int32]),
     "destroy_noise_table": (None, [P(NoiseTable), P(Device)]),

@@ -4,8 +4,9 @@
         --strategy diffuse_specular_mis diffuse_specular_separately --heuristic balance optimal_clamped
 
 renders, for every requested combination of sampling technique, strategy, MIS heuristic, arithmetic mode and noise table
-(`--noise white owen blue ...`: every type but white is generated on the device, include/vkr_noise_table.h), `--frames`
-frames with animated noise and prints one JSON line: milliseconds per frame, the mean sample variance over pixels and
+(`--noise white owen blue ...`: every type but white is generated on the device, include/vkr_noise_table.h)
+and LTC table (`--ltc synthetic fitted`: `fitted` replaces the data set's placeholder fits by a table fitted on the device,
+include/vkr_ltc_table.h fit_ltc_table), frames with animated noise and prints one JSON line: milliseconds per frame, the mean sample variance over pixels and
 channels and the RMSE of the mean of those frames against a converged image (`--reference-frames` frames of the
 configuration's own settings, from another seed).  Frames never leave the GPU: they are summed per pixel in binary64
 there, and the error sums are reduced there."""
@@ -108,12 +109,17 @@ def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False)
         app.render_settings.animate_noise = animate_before
 
 
-def _make_renderer(args, dataset, arithmetic, noise="white", **overrides):
+def _make_renderer(args, dataset, arithmetic, noise="white", ltc="synthetic", **overrides):
     r = renderer_module.Renderer(hip_device=args.device, frames_in_flight=args.frames_in_flight, timing_stride=1 << 30, arithmetic=arithmetic)
     try:
         renderer_module.setup_config(r, args.config, dataset, width=args.width, height=args.height, **overrides)
         if noise != "white":
             r.generate_noise_table(noise, seed=args.noise_seed)
+        if ltc == "fitted":
+            # (the size of the data set's table)
+            r.fit_ltc_table(int(r.app.ltc_table.roughness_count), int(r.app.ltc_table.fresnel_count), args.ltc_sample_count)
+        if args.roughness_factor is not None:
+            r.app.render_settings.roughness_factor = args.roughness_factor
         r.create_targets()
         r.create_pass()
         r.render_visibility()
@@ -133,6 +139,9 @@ def main(argv=None):
     ap.add_argument("--heuristic", nargs="+", default=[None], choices=sorted(renderer_module.MIS))
     ap.add_argument("--arithmetic", nargs="+", default=["libm"], choices=sorted(renderer_module.ARITHMETIC_MODES))
     ap.add_argument("--noise", nargs="+", default=["white"], choices=["white"] + list(noise_tables.GENERATED_TYPES), help="noise tables; all but white are generated on the device at their default resolution")
+    ap.add_argument("--ltc", nargs="+", default=["synthetic"], choices=["synthetic", "fitted"], help="LTC tables: the placeholder fits of the synthetic data set, or a table fitted on the device")
+    ap.add_argument("--ltc-sample-count", type=int, default=None, help="sample_count of the fit (default: that of fit_ltc_table)")
+    ap.add_argument("--roughness-factor", type=float, default=None, help="render_settings.roughness_factor (below 1: a glossy variant of the configuration)")
     ap.add_argument("--noise-seed", type=int, default=0, help="generator seed of the generated tables")
     ap.add_argument("--sample-count", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
@@ -152,15 +161,15 @@ def main(argv=None):
                 reference = measure(r, args.reference_frames, seed=args.reference_seed, return_mean=True)["mean"]
             finally:
                 r.close()
-        for technique, strategy, heuristic, arithmetic, noise in itertools.product(args.technique, args.strategy, args.heuristic, args.arithmetic, args.noise):
+        for technique, strategy, heuristic, arithmetic, noise, ltc in itertools.product(args.technique, args.strategy, args.heuristic, args.arithmetic, args.noise, args.ltc):
             overrides = dict(common)
             for key, value in (("polygon_technique", technique), ("sampling_strategies", strategy), ("mis_heuristic", heuristic)):
                 if value is not None:
                     overrides[key] = value
-            line = {"config": args.config, "technique": technique, "strategy": strategy, "heuristic": heuristic, "arithmetic": arithmetic, "noise": noise}
+            line = {"config": args.config, "technique": technique, "strategy": strategy, "heuristic": heuristic, "arithmetic": arithmetic, "noise": noise, "ltc": ltc}
             r = None
             try:
-                r = _make_renderer(args, dataset, arithmetic, noise, **overrides)
+                r = _make_renderer(args, dataset, arithmetic, noise, ltc, **overrides)
                 extent = r.app.swapchain.extent
                 line.update({"width": extent.width, "height": extent.height, "sample_count": int(r.app.render_settings.sample_count), "reference_frames": args.reference_frames})
                 line.update(measure(r, args.frames, reference, seed=args.seed))

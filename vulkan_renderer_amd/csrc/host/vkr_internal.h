@@ -33,6 +33,11 @@ void vkr_host_free_pinned(void* pointer);
 int vkr_copy_to_device_async(void* device_pointer, const void* host, size_t size, const device_t* device);
 int vkr_copy_to_host(void* host, const void* device_pointer, size_t size, const device_t* device);
 
+/*! ltc_table.c: what load_ltc_table() and fit_ltc_table() share.  Quantises fresnel_count * resolution^2 fits of five
+	floats (the layout of the fit<i>.dat files) to host_rgba / host_rg, uploads them and sets the lookup constants.
+	Overwrites *table; on failure prints the reason, leaves it zeroed and returns 1. */
+int vkr_fill_ltc_table(ltc_table_t* table, const device_t* device, const float* fits, uint32_t resolution, uint32_t fresnel_count);
+
 /*! textures.c: a material texture decoded to RGBA8, all mip levels one after the other */
 typedef struct vkr_host_texture_s {
 	uint32_t width, height, mip_count, srgb;

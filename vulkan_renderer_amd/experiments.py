@@ -55,10 +55,11 @@ def write_synthetic_data_root(root, grid=128, box_count=32):
 
 
 @contextlib.contextmanager
-def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=51, hip_device=0, noise=None):
+def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=51, hip_device=0, noise=None, ltc="synthetic"):
     """A Renderer with experiment `index` applied, its scene, tables, targets and pass created and the visibility pass
     rendered: yields (renderer, experiment) and closes both afterwards.  noise: a type that is generated on the device
-    instead of the experiment's table"""
+    instead of the experiment's table; ltc "fitted": the LTC table is fitted on the device (fit_ltc_table, default size
+    with fresnel_count slices) instead of read from data/ggx_ltc_fit"""
     lib = capi.load()
     table = experiment_table(lib)
     try:
@@ -79,7 +80,10 @@ def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=
                     cam = synthetic.DEFAULT_CAMERA
                     r.set_camera(cam["position"], cam["rotation_x"], cam["rotation_z"], cam["vertical_fov"], cam["near"], cam["far"])
             r.load_scene(C.string_at(spec.file_path).decode(), C.string_at(spec.texture_path).decode(), acceleration_structure=True)
-            r.load_ltc_table(os.path.join(data_root, "data", "ggx_ltc_fit"), fresnel_count)
+            if ltc == "fitted":
+                r.fit_ltc_table(fresnel_count=fresnel_count)
+            else:
+                r.load_ltc_table(os.path.join(data_root, "data", "ggx_ltc_fit"), fresnel_count)
             cwd = os.getcwd()
             os.chdir(data_root)  # noise tables are addressed relative to the working directory (noise_table.c)
             try:
@@ -103,14 +107,14 @@ def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=
         lib.destroy_experiment_list(C.byref(table))
 
 
-def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None):
+def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None, ltc="synthetic"):
     """Renders experiment `index` and stores its screenshot.  Returns a dict with the
     frame time and the screenshot path, or raises with the library's message.
     accumulate = n > 0: the screenshot holds the mean of n further frames with animated noise (summed on the device,
     include/vkr_frame_statistics.h) instead of the last frame; "accumulate_seed" of the result is the noise seed
     (noise_table_t.random_seed) of the first of them."""
     lib = capi.load()
-    with experiment_renderer(index, data_root, synthetic_inputs, fresnel_count, hip_device, noise) as (r, experiment):
+    with experiment_renderer(index, data_root, synthetic_inputs, fresnel_count, hip_device, noise, ltc) as (r, experiment):
         settings = r.app.render_settings
         wants_rays = bool(settings.trace_shadow_rays)
         for _ in range(warmup):
@@ -148,6 +152,8 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
                   "Msamples_per_s": r.app.swapchain.extent.width * r.app.swapchain.extent.height * settings.sample_count / (frame_ms * 1e-3) / 1e6}
         if noise is not None:
             result["noise"] = noise
+        if ltc != "synthetic":
+            result["ltc"] = ltc
         if accumulate > 0:
             result.update({"accumulated_frames": int(accumulate), "accumulate_seed": accumulate_seed})
         if verbose:
@@ -164,6 +170,7 @@ def main(argv=None):
     ap.add_argument("--hdr", action="store_true", help="store *.hdr instead of *.png (take_hdr_screenshots of the reference)")
     ap.add_argument("--accumulate", type=int, default=0, metavar="N", help="store the mean of N frames with animated noise instead of the last frame")
     ap.add_argument("--noise", default=None, choices=["blue", "sobol", "owen", "burley_owen"], help="generate this noise table on the device instead of loading the experiment's")
+    ap.add_argument("--ltc", default="synthetic", choices=["synthetic", "fitted"], help="fitted: fit the LTC table on the device instead of reading data/ggx_ltc_fit (synthetic: the files of the data root, which --synthetic fills with placeholder fits)")
     args = ap.parse_args(argv)
     lib = capi.load()
     if args.experiment is None:
@@ -177,7 +184,7 @@ def main(argv=None):
     if args.synthetic:
         root = args.synthetic
         fresnel_count = write_synthetic_data_root(root)["fresnel_count"]
-    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise)
+    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise, ltc=args.ltc)
     return 0
 
 

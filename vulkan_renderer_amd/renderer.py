@@ -54,6 +54,8 @@ class HostScene:
             raise RuntimeError("load_scene failed for %s" % path)
 
     def load_ltc_table(self, directory, fresnel_count=51):
+        # (the fits of an earlier fit_ltc_table() belong to the table that this call replaces)
+        self._free_ltc_fits()
         if self.lib.load_ltc_table(C.byref(self.app.ltc_table), self._dev(), directory.encode(), fresnel_count):
             raise RuntimeError("load_ltc_table failed for %s" % directory)
 
@@ -205,6 +207,11 @@ class HostScene:
                 "trace_shadow_rays": bool(s.trace_shadow_rays), "show_polygonal_lights": bool(s.show_polygonal_lights),
                 "error_display": int(s.error_display)}
 
+    def _free_ltc_fits(self):
+        if getattr(self, "_ltc_fits", None):
+            self.lib.free_ltc_fits(self._ltc_fits)
+        self._ltc_fits = None
+
     def close(self):
         app = self.app
         dev = self._dev()
@@ -217,6 +224,7 @@ class HostScene:
         self.lib.destroy_light_textures(C.byref(app.light_textures), dev)
         self.lib.destroy_scene(C.byref(app.scene), dev)
         self.lib.destroy_ltc_table(C.byref(app.ltc_table), dev)
+        self._free_ltc_fits()
         self.lib.destroy_noise_table(C.byref(app.noise_table), dev)
         spec = app.scene_specification
         for i in range(spec.polygonal_light_count):
@@ -307,6 +315,44 @@ class Renderer(HostScene):
         n = self.app.noise_table.resolution
         names = {v: k for k, v in NOISE.items()}
         return os.path.join(data_root or cwd, noise_tables.file_name(names[t], (n.width, n.height, n.depth)))
+
+    def fit_ltc_table(self, resolution=None, fresnel_count=None, sample_count=None, max_iterations=None):
+        """Replaces the LTC table by one fitted on the device (include/vkr_ltc_table.h fit_ltc_table); None: the default
+        of the setting (32, 51, 32, 200).  The fits stay with the renderer for ltc_fits() and write_ltc_table().  Returns
+        the milliseconds the call took (kernel, read-back, quantisation and upload).  Frames in flight are finished
+        first: they read the old table."""
+        import time
+        if self.app.shading_pass.constants_device:
+            self.finish_frames()
+            self.sync()
+        settings = self.lib.get_default_ltc_fit_settings()
+        for name, value in (("resolution", resolution), ("fresnel_count", fresnel_count), ("sample_count", sample_count), ("max_iterations", max_iterations)):
+            if value is not None:
+                setattr(settings, name, int(value))
+        self._free_ltc_fits()
+        self.lib.destroy_ltc_table(C.byref(self.app.ltc_table), self._dev())
+        fits = C.POINTER(C.c_float)()
+        start = time.perf_counter()
+        if self.lib.fit_ltc_table(C.byref(self.app.ltc_table), C.byref(fits), self._dev(), C.byref(settings)):
+            raise RuntimeError("fit_ltc_table failed")
+        # (the size goes with the pointer: the table of the application may be replaced behind this object's back)
+        self._ltc_fits, self._ltc_fit_size = fits, (int(settings.resolution), int(settings.fresnel_count))
+        return (time.perf_counter() - start) * 1.0e3
+
+    def ltc_fits(self):
+        """The fits of the last fit_ltc_table(): (fresnel_count, R, R, 5) float32, [i, y, x], the order of the files"""
+        if not getattr(self, "_ltc_fits", None):
+            raise RuntimeError("no fitted LTC table: call fit_ltc_table() first")
+        resolution, fresnel_count = self._ltc_fit_size
+        return np.ctypeslib.as_array(self._ltc_fits, (fresnel_count, resolution, resolution, 5)).copy()
+
+    def write_ltc_table(self, directory):
+        """Writes the fits of the last fit_ltc_table() as <directory>/fit<i>.dat, which load_ltc_table() reads"""
+        if not getattr(self, "_ltc_fits", None):
+            raise RuntimeError("no fitted LTC table: call fit_ltc_table() first")
+        resolution, fresnel_count = self._ltc_fit_size
+        if self.lib.write_ltc_table(self._ltc_fits, resolution, fresnel_count, directory.encode()):
+            raise RuntimeError("write_ltc_table failed for %s" % directory)
 
     def upload_visibility(self, visibility):
         v = np.ascontiguousarray(visibility, np.uint32)

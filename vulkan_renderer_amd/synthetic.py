@@ -485,9 +485,12 @@ def write_light_texture(path, image, vk_format=VK_FORMAT_R16G16B16A16_SFLOAT, mi
 
 def write_ltc_fits(directory, resolution=32, fresnel_count=51):
     """Writes fit<i>.dat files with a smooth synthetic GGX-like fit.  NOT a real
-    LTC fit (those are downloads, reference README.md:9-13): the matrix is
-    diag-dominant with a lobe that narrows with roughness and tilts away from the
-    viewer at grazing angles, which is all the parity tests need.  File layout:
+    LTC fit: the matrix is diag-dominant with a lobe that narrows with roughness
+    and tilts away from the viewer at grazing angles, which is all the parity
+    tests need.  Real fits are the reference's downloads (README.md:9-13) or come
+    from the device: fit_ltc_table() of include/vkr_ltc_table.h fits the table and
+    write_ltc_table() stores it in this format (Renderer.fit_ltc_table(),
+    `python -m vulkan_renderer_amd.ltc_fit DIR`).  File layout:
     u64 resolution, then resolution^2 x (d0, d1, d2, d3, albedo) float32 with
     index y * R + x, x = roughness axis, y = inclination axis."""
     os.makedirs(directory, exist_ok=True)
