@@ -448,6 +448,14 @@ VKR_API int get_traversal_statistics_of_tree(application_t* app, VkBool32 wide_t
 	12 inversesqrt as 1 / sqrt (inverse_square_root_ieee).  a, b (may be NULL for unary operations) and out are host arrays of
 	`count` floats.  0 on success. */
 VKR_API int evaluate_device_arithmetic(const device_t* device, uint32_t operation, const float* a, const float* b, float* out, uint32_t count);
+/*! Diagnostics for the material texture sampler (sample_texture() of csrc/shading_kernel.h, mirrored by
+	oracle_sample_texture): samples one RGBA8 texture on the device, with the kernel of the arithmetic mode
+	`arithmetic_mode` (an arithmetic_mode_t) and the sRGB table of the pass.  texels_rgba8: `mip_count` levels, finest first,
+	each half as wide and as high as the one before (rounded down, at least 1), row-major, tightly packed.  inputs: six floats
+	per sample - the texture coordinate and its two screen-space derivatives, (u, v, du/dx, dv/dx, du/dy, dv/dy), what
+	resolve_material() hands to the sampler -, out_rgba: four floats per sample; host arrays for `count` samples.
+	0 on success.  No reference counterpart (the reference leaves the filter to the driver). */
+VKR_API int evaluate_device_texture_sampler(const device_t* device, int32_t arithmetic_mode, const uint8_t* texels_rgba8, uint32_t width, uint32_t height, uint32_t mip_count, VkBool32 srgb, const float* inputs, float* out_rgba, uint32_t count);
 /*! Two one-argument operations of evaluate_device_arithmetic (1 square_root, 4 the compiler's sqrtf, 5 atanf,
 	12 inversesqrt as the kernels evaluate it, plus 16: the compiler's 1 / sqrtf, 17: atanf with its argument
 	range from the LDS table, as the libm kernels evaluate it) evaluated on the device

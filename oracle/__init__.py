@@ -99,6 +99,9 @@ def lib():
         L.oracle_shading_data.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, fp]
         L.oracle_evaluate_brdf.argtypes = [fp, fp, C.c_int, C.c_int, fp]
         L.oracle_noise_stream.argtypes = [C.POINTER(Frame), C.c_uint32, C.c_uint32, C.c_uint32, fp]
+        L.oracle_sample_texture_batch.argtypes = [C.POINTER(Texture), C.c_void_p, C.c_void_p, C.c_uint64]
+        L.oracle_texture_footprint_batch.argtypes = [C.POINTER(Texture), C.c_void_p, C.c_void_p, C.c_uint64]
+        L.oracle_texture_sampler_inputs.argtypes = [C.POINTER(Frame), C.c_void_p]
         L.oracle_libm_evaluate.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.oracle_libm_count_mismatches.restype = C.c_size_t
         L.oracle_libm_count_mismatches.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, C.c_float, C.POINTER(C.c_uint32)]
@@ -298,6 +301,42 @@ def shade(frame, y0=0, y1=None, threads=0):
     """Returns (height, width, 4) float32; rows outside [y0, y1) stay zero."""
     out = np.zeros((frame.height, frame.width, 4), np.float32)
     lib().oracle_shade_rows(C.byref(frame), out.ctypes.data, y0, frame.height if y1 is None else y1, threads)
+    return out
+
+
+def _texture(texture):
+    t = Texture()
+    t._texels = np.ascontiguousarray(texture["texels"], np.uint8)
+    t.texels = t._texels.ctypes.data
+    t.width, t.height, t.mip_count, t.srgb = int(texture["width"]), int(texture["height"]), int(texture["mip_count"]), int(texture["srgb"])
+    return t
+
+
+def sample_texture_batch(texture, inputs):
+    """oracle_sample_texture, in the current math mode, of one texture - a dict with "texels" (uint8, all levels, RGBA8),
+    "width", "height", "mip_count", "srgb" - for inputs (n, 6): uv, duv_dx, duv_dy.  -> (n, 4) float32"""
+    t = _texture(texture)
+    inputs = np.ascontiguousarray(inputs, np.float32).reshape(-1, 6)
+    out = np.zeros((inputs.shape[0], 4), np.float32)
+    lib().oracle_sample_texture_batch(C.byref(t), inputs.ctypes.data, out.ctypes.data, inputs.shape[0])
+    return out
+
+
+def texture_footprint_batch(texture, inputs):
+    """What oracle_sample_texture makes of the same inputs: -> (n, 4) uint32 - tap count, the two levels, 1 if the footprint
+    is longer along x"""
+    t = _texture(texture)
+    inputs = np.ascontiguousarray(inputs, np.float32).reshape(-1, 6)
+    out = np.zeros((inputs.shape[0], 4), np.uint32)
+    lib().oracle_texture_footprint_batch(C.byref(t), inputs.ctypes.data, out.ctypes.data, inputs.shape[0])
+    return out
+
+
+def texture_sampler_inputs(frame):
+    """What the texture reads of every pixel of a textured frame are given: (height, width, 6) float32 - uv, duv_dx,
+    duv_dy -, NaN where nothing is visible"""
+    out = np.zeros((frame.height, frame.width, 6), np.float32)
+    lib().oracle_texture_sampler_inputs(C.byref(frame), out.ctypes.data)
     return out
 
 

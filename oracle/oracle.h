@@ -101,6 +101,14 @@ typedef struct oracle_frame_s {
  * chain, averaged in order; N = 1 is plain trilinear.  Bilinear weights in exact fp32, x first; sRGB texels are decoded
  * before filtering.  (Rounds 1 - 4: isotropic trilinear.) */
 void oracle_sample_texture(const oracle_texture_t* texture, const float uv[2], const float duv_dx[2], const float duv_dy[2], float out_rgba[4]);
+/* the same for count samples of one texture: six floats per sample in (uv, duv_dx, duv_dy), four out; an OpenMP loop */
+void oracle_sample_texture_batch(const oracle_texture_t* texture, const float* inputs, float* out_rgba, uint64_t count);
+/* what oracle_sample_texture makes of each input: four words per sample - the tap count, the two levels it blends, 1 if the
+ * footprint is longer along x.  For tests that ask which paths of the sampler a set of inputs takes. */
+void oracle_texture_footprint_batch(const oracle_texture_t* texture, const float* inputs, uint32_t* out, uint64_t count);
+/* the inputs of oracle_sample_texture at every pixel of a textured frame: six floats per pixel (uv, duv_dx, duv_dy), NaNs where
+ * nothing is visible.  For tests that ask what a frame makes the sampler do. */
+void oracle_texture_sampler_inputs(const oracle_frame_t* frame, float* out);
 /* textureLod(g_light_textures[i], uv, 0) of this build (sampler of main.c:611-621: linear filter,
  * u repeats, v clamps to the edge): bilinear in exact fp32, x first.  u is wrapped to [0,1) before
  * scaling; non-finite coordinates read texel column / row 0. */

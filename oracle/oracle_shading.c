@@ -312,6 +312,15 @@ static void fetch_texel(const oracle_texture_t* t, const uint8_t* level, int wid
 	out[3] = (float) texel[3] * (1.0f / 255.0f);
 }
 
+/* The texel that the floored coordinate x0 = floor(u * width - 1 / 2) addresses, before the repeat: x0 itself wherever an int
+ * holds it.  At or beyond +-2^31, and for a NaN, the conversion is undefined in C (and differs between an x86 host and the
+ * device), so the rule is stated: such a coordinate addresses texel 0 of its axis.  A float that large has no fractional
+ * part - x - x0 is 0 and texel 0 alone is returned -, an infinite or NaN coordinate gives NaN weights and a NaN sample.
+ * (x0 + 1 cannot overflow: the largest float below 2^31 is 2^31 - 128.) */
+static int texel_index(float x0) {
+	return (x0 >= -2147483648.0f && x0 < 2147483648.0f) ? (int) x0 : 0;
+}
+
 static void sample_level(const oracle_texture_t* t, uint32_t level, float u, float v, float out[4]) {
 	const uint8_t* texels = t->texels;
 	int width = (int) t->width, height = (int) t->height;
@@ -323,11 +332,12 @@ static void sample_level(const oracle_texture_t* t, uint32_t level, float u, flo
 	float x = u * (float) width - 0.5f, y = v * (float) height - 0.5f;
 	float x0 = floorf(x), y0 = floorf(y);
 	float fx = x - x0, fy = y - y0;
+	int ix = texel_index(x0), iy = texel_index(y0);
 	float t00[4], t10[4], t01[4], t11[4];
-	fetch_texel(t, texels, width, height, (int) x0, (int) y0, t00);
-	fetch_texel(t, texels, width, height, (int) x0 + 1, (int) y0, t10);
-	fetch_texel(t, texels, width, height, (int) x0, (int) y0 + 1, t01);
-	fetch_texel(t, texels, width, height, (int) x0 + 1, (int) y0 + 1, t11);
+	fetch_texel(t, texels, width, height, ix, iy, t00);
+	fetch_texel(t, texels, width, height, ix + 1, iy, t10);
+	fetch_texel(t, texels, width, height, ix, iy + 1, t01);
+	fetch_texel(t, texels, width, height, ix + 1, iy + 1, t11);
 	for (int c = 0; c != 4; ++c) {
 		float top = t00[c] * (1.0f - fx) + t10[c] * fx;
 		float bottom = t01[c] * (1.0f - fx) + t11[c] * fx;
@@ -340,8 +350,12 @@ static void sample_level(const oracle_texture_t* t, uint32_t level, float u, flo
  * example of GL_EXT_texture_filter_anisotropic): the footprint's longer axis P_max and shorter axis P_min in texels,
  * N = min(ceil(P_max / P_min), 16) taps - never more than the footprint is texels long -, each a trilinear sample at
  * level log2(P_max / N), spread evenly along the longer axis at uv + (i / (N + 1) - 1 / 2) d(uv), i = 1 ... N, and averaged
- * in that order.  N = 1 is the isotropic trilinear sample of rounds 1 - 4 in every bit. */
+ * in that order.  N = 1 is the isotropic trilinear sample of rounds 1 - 4 in every bit.
+ * Every input has a defined result: texel coordinates that no int holds (|floor(u * width - 1 / 2)| >= 2^31, NaN) address
+ * texel 0 of their axis, see texel_index(). */
 #define ORACLE_MAX_ANISOTROPY 16.0f
+/* where oracle_sample_texture() of this thread leaves its tap count and its two levels (oracle_texture_footprint_batch), or NULL */
+static _Thread_local uint32_t* g_footprint_out = NULL;
 void oracle_sample_texture(const oracle_texture_t* t, const float uv[2], const float duv_dx[2], const float duv_dy[2], float out_rgba[4]) {
 	float w = (float) t->width, h = (float) t->height;
 	float ax = duv_dx[0] * w, ay = duv_dx[1] * h, bx = duv_dy[0] * w, by = duv_dy[1] * h;
@@ -361,6 +375,9 @@ void oracle_sample_texture(const oracle_texture_t* t, const float uv[2], const f
 	uint32_t l0 = (uint32_t) level_0;
 	uint32_t l1 = (l0 + 1 < t->mip_count) ? l0 + 1 : l0;
 	uint32_t count = (uint32_t) taps;
+	if (g_footprint_out) {
+		g_footprint_out[0] = count; g_footprint_out[1] = l0; g_footprint_out[2] = l1; g_footprint_out[3] = (uint32_t) x_major;
+	}
 	float du = x_major ? duv_dx[0] : duv_dy[0], dv = x_major ? duv_dx[1] : duv_dy[1];
 	float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 	for (uint32_t i = 0; i != count; ++i) {
@@ -379,6 +396,28 @@ void oracle_sample_texture(const oracle_texture_t* t, const float uv[2], const f
 		}
 	}
 	for (int c = 0; c != 4; ++c) out_rgba[c] = (count > 1) ? sum[c] / taps : sum[c];
+}
+
+/* count samples of one texture, inputs: six floats per sample (uv, duv_dx, duv_dy), out_rgba: four per sample */
+void oracle_sample_texture_batch(const oracle_texture_t* t, const float* inputs, float* out_rgba, uint64_t count) {
+	/* (the table is filled on first use: not from inside the loop's threads) */
+	(void) oracle_srgb_table();
+#pragma omp parallel for schedule(static)
+	for (int64_t i = 0; i < (int64_t) count; ++i)
+		oracle_sample_texture(t, inputs + 6 * i, inputs + 6 * i + 2, inputs + 6 * i + 4, out_rgba + 4 * i);
+}
+
+/* what oracle_sample_texture makes of each input: four words per sample - tap count, the two levels, 1 if the footprint is
+ * longer along x */
+void oracle_texture_footprint_batch(const oracle_texture_t* t, const float* inputs, uint32_t* out, uint64_t count) {
+	(void) oracle_srgb_table();
+#pragma omp parallel for schedule(static)
+	for (int64_t i = 0; i < (int64_t) count; ++i) {
+		float rgba[4];
+		g_footprint_out = out + 4 * i;
+		oracle_sample_texture(t, inputs + 6 * i, inputs + 6 * i + 2, inputs + 6 * i + 4, rgba);
+		g_footprint_out = NULL;
+	}
 }
 
 void oracle_sample_light_texture(const oracle_light_texture_t* t, const float uv[2], float out_rgba[4]) {
@@ -404,6 +443,9 @@ void oracle_sample_light_texture(const oracle_light_texture_t* t, const float uv
 		out_rgba[c] = top * (1.0f - wy) + bottom * wy;
 	}
 }
+
+/* where get_shading_data() of this thread leaves what it hands to the sampler (oracle_texture_sampler_inputs), or NULL */
+static _Thread_local float* g_sampler_inputs_out = NULL;
 
 static shading_data_t get_shading_data(const oracle_frame_t* f, const frame_constants_t* k, uint32_t primitive, v3 ray_direction) {
 	shading_data_t r;
@@ -453,6 +495,11 @@ static shading_data_t get_shading_data(const oracle_frame_t* f, const frame_cons
 			for (int j = 0; j != 3; ++j) tex_derivs[i] = add2(tex_derivs[i], scale2(uv[j], weights[j]));
 		}
 		const float uv_[2] = {tex_coord.x, tex_coord.y}, dx_[2] = {tex_derivs[0].x, tex_derivs[0].y}, dy_[2] = {tex_derivs[1].x, tex_derivs[1].y};
+		if (g_sampler_inputs_out) {
+			memcpy(g_sampler_inputs_out, uv_, 8);
+			memcpy(g_sampler_inputs_out + 2, dx_, 8);
+			memcpy(g_sampler_inputs_out + 4, dy_, 8);
+		}
 		for (int type = 0; type != 3; ++type) {
 			const oracle_texture_t* texture = &f->material_textures[3 * material + type];
 			/* width 0: this texture is a constant (half / float *.vkt or absent file) */
@@ -2406,6 +2453,22 @@ void oracle_shading_data(const oracle_frame_t* frame, uint32_t x, uint32_t y, fl
 	if (primitive == 0xFFFFFFFFu) return;
 	shading_data_t sd = get_shading_data(frame, &k, primitive, pixel_ray(&k, x, y));
 	memcpy(out, &sd, 17 * sizeof(float));
+}
+/* what the three texture reads of every pixel of a textured frame are given: six floats per pixel (uv, duv_dx, duv_dy),
+ * NaNs where nothing is visible */
+void oracle_texture_sampler_inputs(const oracle_frame_t* frame, float* out) {
+	frame_constants_t k = read_frame_constants(frame->constants);
+	for (uint32_t y = 0; y != frame->height; ++y) {
+		for (uint32_t x = 0; x != frame->width; ++x) {
+			float* pixel = out + 6 * ((size_t) y * frame->width + x);
+			for (int i = 0; i != 6; ++i) pixel[i] = NAN;
+			uint32_t primitive = frame->visibility[(size_t) y * frame->width + x];
+			if (primitive == 0xFFFFFFFFu || !frame->material_textures) continue;
+			g_sampler_inputs_out = pixel;
+			(void) get_shading_data(frame, &k, primitive, pixel_ray(&k, x, y));
+			g_sampler_inputs_out = NULL;
+		}
+	}
 }
 void oracle_evaluate_brdf(const float shading_data[17], const float incoming[3], int diffuse, int specular, float out_rgb[3]) {
 	shading_data_t sd;

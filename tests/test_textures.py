@@ -11,9 +11,11 @@ import pytest
 
 import golden_cases
 import oracle
+import sampler_cases
 from vulkan_renderer_amd import renderer, synthetic
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+SAMPLE_COUNT_RANGE = (1 << 16, 1 << 18)
 
 
 @pytest.fixture(scope="module")
@@ -195,6 +197,92 @@ def test_sampler_takes_its_taps_along_the_longer_axis_of_a_stretched_footprint()
     assert np.isfinite(sample(texture, uv, (0.0, 0.0), (0.0, 0.0))).all()
     # a round footprint is the plain trilinear sample
     assert abs(sample(texture, uv, (0.25, 0.0), (0.0, 0.25))[0] - 60 / 255) < 1e-6
+
+
+def test_sampler_defines_coordinates_that_no_int_holds():
+    """A texel coordinate floor(u * width - 1 / 2) at or beyond +-2^31 addresses texel 0 of its axis (the conversion to int is
+    undefined there); such a float has no fraction, so that texel comes back alone.  The last coordinates that an int holds
+    still wrap as every other one does.  Infinite and NaN coordinates give NaN."""
+    level0 = np.zeros((3, 6, 4), np.uint8)
+    level0[..., 0] = np.arange(18).reshape(3, 6) * 14
+    level0[..., 3] = 255
+    # (extents that are no powers of two: INT_MIN, what an x86 host makes of such a conversion, would wrap to texel 4 and row 1)
+    texture = {"texels": level0.reshape(-1, 4), "width": 6, "height": 3, "mip_count": 1, "srgb": 0}
+    tiny = (1e-4, 0.0), (0.0, 1e-4)
+    unorm = lambda byte: np.float32(byte) * np.float32(1.0 / 255.0)
+    row1 = 1.5 / 3  # the centre of row 1
+    for u in (2.0 ** 29, 2.0 ** 30, 1.0e20, 3.0e37, -2.0 ** 29, -1.0e20):
+        # (6 u - 1 / 2 rounds to 6 u: beyond 2^31, or below -2^31)
+        assert sample(texture, (u, row1), *tiny)[0] == unorm(6 * 14), u
+    for v in (2.0 ** 30, 1.0e20, -3.0e37):
+        assert sample(texture, (0.25, v), *tiny)[0] == unorm(14), v
+    assert sample(texture, (1.0e20, -1.0e20), *tiny)[0] == 0.0
+    # coordinates that an int still holds wrap as every other one does: 6 * 2^27 and 3 * 2^28 are multiples of the extents
+    assert sample(texture, (2.0 ** 27, row1), *tiny)[0] == unorm(6 * 14)
+    assert sample(texture, (0.25, -2.0 ** 28), *tiny)[0] == unorm(14)
+    for coordinate in (float("inf"), float("-inf"), float("nan")):
+        assert np.isnan(sample(texture, (coordinate, row1), *tiny)).all() and np.isnan(sample(texture, (0.3, coordinate), *tiny)).all()
+
+
+@pytest.mark.parametrize("name", sampler_cases.TEXTURE_IDS)
+def test_sampler_agrees_with_a_binary64_restatement_of_its_rule(name):
+    """The oracle's sampler (libm mode) against sampler_cases.restate(), on the inputs of tests/test_gpu_texture_sampler.py
+    with finite coordinates, linear and sRGB.  The two are compared wherever they take the same number of taps from the same
+    pair of levels; next to a step of the tap count or a power of two of P_max / N they may not, for at most 1 % of the
+    inputs.  The coverage that the GPU tests rely on is asserted here as well: it is a property of the inputs."""
+    texture, inputs = sampler_cases.make_texture(name), sampler_cases.make_inputs(name)
+    want, footprint = sampler_cases.restated(name)
+    finite = sampler_cases.finite_coordinates(inputs)
+    assert SAMPLE_COUNT_RANGE[0] <= len(inputs) <= SAMPLE_COUNT_RANGE[1] and 0.9 < finite.mean() < 1.0
+    # every tap count at every level, the clamp at the top of the chain, both major axes
+    sampler_cases.assert_coverage(name)
+    theirs = oracle.texture_footprint_batch(texture, inputs)
+    agree = (theirs[:, 0] == footprint["taps"]) & (theirs[:, 1] == footprint["l0"]) & (theirs[:, 2] == footprint["l1"])
+    print(name, "tap count or level pair differ for %.3f %% of the inputs" % (100.0 * (~agree & finite).sum() / finite.sum()))
+    assert (~agree & finite).sum() <= 0.01 * finite.sum()
+    tolerance = sampler_cases.tolerance(texture, inputs)[:, None]
+    for srgb in (0, 1):
+        got = oracle.sample_texture_batch(dict(texture, srgb=srgb), inputs).astype(np.float64)
+        both_nan = np.isnan(got) & np.isnan(want[:, srgb])
+        # (a NaN on one side only fails the comparison)
+        within = both_nan | (np.abs(got - want[:, srgb]) <= tolerance)
+        rows = finite & agree
+        print(name, "srgb", srgb, "largest error / tolerance %.3f" % np.nanmax((np.abs(got - want[:, srgb]) / tolerance)[rows]))
+        assert within[rows].all(), inputs[rows & ~within.all(axis=1)][:4]
+        # the special derivatives and the huge coordinates are part of it: they have defined, mostly finite results
+        assert np.isfinite(got[rows]).all(axis=1).mean() > 0.9
+
+
+def test_grazing_frame_loads_odd_truncated_chains_and_works_the_sampler(tmp_path):
+    """The dataset of the GPU frame test of tests/test_gpu_texture_sampler.py: the loader takes textures of 96x40 that stop at
+    6x2, every level decodes like the format definitions, and the frame reaches level 3 and 16 taps"""
+    dataset = synthetic.write_dataset(str(tmp_path), **sampler_cases.GRAZING_DATASET)
+    hs = renderer.HostScene()
+    sampler_cases.apply_grazing_case(hs, golden_cases.TEXTURED_CASES[2], dataset)
+    inputs = hs.host_inputs()
+    extents = sampler_cases.level_extents(96, 40, 5)
+    names = [hs.app.scene.materials.material_names[i].decode() for i in range(3)]
+    for m, name in enumerate(names):
+        for t, (suffix, srgb) in enumerate((("BaseColor", 1), ("Specular", 0), ("Normal", 0))):
+            vk_format, mips = read_vkt(os.path.join(dataset["textures"], "%s_%s.vkt" % (name, suffix)))
+            texture = inputs["material_textures"][3 * m + t]
+            assert [mip[:2] for mip in mips] == extents and (texture["width"], texture["height"], texture["mip_count"], texture["srgb"]) == (96, 40, 5, srgb)
+            expected = np.concatenate([decode_reference(vk_format, w, h, blob).reshape(-1, 4) for w, h, blob in mips])
+            assert np.array_equal(texture["texels"], expected), (name, suffix)
+    bvh = oracle.Bvh(inputs["quantized_positions"], inputs["dequantization_factor"], inputs["dequantization_summand"])
+    cam = synthetic.DEFAULT_CAMERA
+    inputs["visibility"] = oracle.primary_visibility(inputs["constants"], bvh, *sampler_cases.GRAZING_EXTENT, cam["near"], cam["far"])
+    frame = oracle.make_frame(inputs, hs.oracle_settings(), bvh)
+    sampler_cases.assert_frame_works_the_sampler(frame, inputs["material_textures"])
+    assert not np.isnan(oracle.shade(frame)).any()
+    hs.close()
+
+
+def test_batched_sampler_is_the_sampler():
+    texture, inputs = sampler_cases.make_texture("5x3"), sampler_cases.make_inputs("5x3")[::257]
+    batch = oracle.sample_texture_batch(dict(texture, srgb=1), inputs)
+    single = np.array([sample(dict(texture, srgb=1), row[0:2], row[2:4], row[4:6]) for row in inputs])
+    assert sampler_cases.same_bits(batch, single).all()
 
 
 @pytest.mark.parametrize("case", golden_cases.TEXTURED_CASES, ids=[c["key"] for c in golden_cases.TEXTURED_CASES])

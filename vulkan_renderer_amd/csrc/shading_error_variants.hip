@@ -9,12 +9,15 @@
 #if VKR_FAST_MATH
 #define VKR_ERROR_LAUNCH_NAME vkr_launch_error_display_fast
 #define VKR_RESOLVE_LAUNCH_NAME vkr_launch_resolve_materials_fast
+#define VKR_SAMPLER_LAUNCH_NAME vkr_launch_texture_sampler_fast
 #elif VKR_MATH_MODE == 2
 #define VKR_ERROR_LAUNCH_NAME vkr_launch_error_display_libm
 #define VKR_RESOLVE_LAUNCH_NAME vkr_launch_resolve_materials_libm
+#define VKR_SAMPLER_LAUNCH_NAME vkr_launch_texture_sampler_libm
 #else
 #define VKR_ERROR_LAUNCH_NAME vkr_launch_error_display_exact
 #define VKR_RESOLVE_LAUNCH_NAME vkr_launch_resolve_materials_exact
+#define VKR_SAMPLER_LAUNCH_NAME vkr_launch_texture_sampler_exact
 #endif
 
 using namespace vkr;
@@ -78,6 +81,26 @@ __global__ void __launch_bounds__(256) k_resolve_materials(const shade_params p,
 	out[0] = make_float4(values[0], values[1], values[2], values[3]);
 	out[1] = make_float4(values[4], values[5], values[6], values[7]);
 }
+
+// evaluate_device_texture_sampler(): sample_texture() as resolve_material() calls it, on inputs of the caller's choice.
+// One lane per sample; inputs: six floats per sample (uv, duv_dx, duv_dy), out_rgba: four.  descriptor: the four words of
+// a material's texture descriptor (first texel, width, height, mip count | srgb << 16), unpacked as resolve_material() does.
+__global__ void __launch_bounds__(256) k_sample_texture(const shade_params p, uint4 descriptor, const float* inputs, float4* out_rgba, uint32_t count) {
+	uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= count) return;
+	texture_view view;
+	view.texels = p.texels + descriptor.x;
+	view.width = descriptor.y; view.height = descriptor.z;
+	view.mip_count = descriptor.w & 0xFFFFu;
+	view.srgb = (descriptor.w >> 16) != 0;
+	const float* in = inputs + 6 * (size_t) i;
+	out_rgba[i] = sample_texture(p, view, mk2(in[0], in[1]), mk2(in[2], in[3]), mk2(in[4], in[5]));
+}
+}
+
+extern "C" int VKR_SAMPLER_LAUNCH_NAME(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream) {
+	k_sample_texture<<<(count + 255u) / 256u, 256, 0, (hipStream_t) stream>>>(*p, make_uint4(descriptor[0], descriptor[1], descriptor[2], descriptor[3]), inputs, (float4*) out_rgba, count);
+	return hipGetLastError() != hipSuccess;
 }
 
 extern "C" int VKR_RESOLVE_LAUNCH_NAME(const shade_params* p, float* pixel_materials, void* stream) {

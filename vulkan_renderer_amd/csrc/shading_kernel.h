@@ -341,6 +341,13 @@ VKR_DEV float4 fetch_texel(const shade_params& p, const texture_view& t, const u
 	return out;
 }
 
+// The texel that the floored coordinate x0 addresses, before the repeat: x0 itself wherever an int holds it, texel 0 at or
+// beyond +-2^31 and for a NaN (texel_index() of oracle/oracle_shading.c; the conversion instruction alone would saturate and
+// turn a NaN into 0, where the oracle's host returns INT_MIN)
+VKR_DEV int texel_index(float x0) {
+	return (x0 >= -2147483648.0f && x0 < 2147483648.0f) ? (int) x0 : 0;
+}
+
 VKR_DEV float4 sample_level(const shade_params& p, const texture_view& t, uint32_t level, float u, float v) {
 	const uint32_t* texels = t.texels;
 	int width = (int) t.width, height = (int) t.height;
@@ -352,10 +359,11 @@ VKR_DEV float4 sample_level(const shade_params& p, const texture_view& t, uint32
 	float x = u * (float) width - 0.5f, y = v * (float) height - 0.5f;
 	float x0 = floorf(x), y0 = floorf(y);
 	float fx = x - x0, fy = y - y0;
-	float4 t00 = fetch_texel(p, t, texels, width, height, (int) x0, (int) y0);
-	float4 t10 = fetch_texel(p, t, texels, width, height, (int) x0 + 1, (int) y0);
-	float4 t01 = fetch_texel(p, t, texels, width, height, (int) x0, (int) y0 + 1);
-	float4 t11 = fetch_texel(p, t, texels, width, height, (int) x0 + 1, (int) y0 + 1);
+	int ix = texel_index(x0), iy = texel_index(y0);
+	float4 t00 = fetch_texel(p, t, texels, width, height, ix, iy);
+	float4 t10 = fetch_texel(p, t, texels, width, height, ix + 1, iy);
+	float4 t01 = fetch_texel(p, t, texels, width, height, ix, iy + 1);
+	float4 t11 = fetch_texel(p, t, texels, width, height, ix + 1, iy + 1);
 	float4 out;
 	out.x = (t00.x * (1.0f - fx) + t10.x * fx) * (1.0f - fy) + (t01.x * (1.0f - fx) + t11.x * fx) * fy;
 	out.y = (t00.y * (1.0f - fx) + t10.y * fx) * (1.0f - fy) + (t01.y * (1.0f - fx) + t11.y * fx) * fy;
@@ -370,6 +378,9 @@ VKR_DEV float4 sample_level(const shade_params& p, const texture_view& t, uint32
 // axis of the footprint at uv + (i / (N + 1) - 1 / 2) d(uv) and averaged in order; N = 1 is the isotropic trilinear sample of
 // rounds 1 - 4 in every bit.  (The quotients may have any operands - a derivative of zero, a footprint of a thousand texels:
 // the full-range division.)
+// Every input has a defined result, the same on the host and on the device: a texel coordinate floor(u * width - 1 / 2) that
+// no int holds - at or beyond +-2^31, NaN - addresses texel 0 of its axis (texel_index()).  Such a float has no fractional
+// part, so a large finite coordinate returns that texel alone; an infinite or NaN coordinate gives a NaN sample.
 constexpr float kMaxAnisotropy = 16.0f;
 VKR_DEV float4 sample_texture(const shade_params& p, const texture_view& t, f2 uv, f2 duv_dx, f2 duv_dy) {
 	float w = (float) t.width, h = (float) t.height;

@@ -22,6 +22,10 @@ typedef int (*resolve_launch_function_t)(const shade_params* p, float* pixel_mat
 extern "C" int vkr_launch_resolve_materials_libm(const shade_params* p, float* pixel_materials, void* stream);
 extern "C" int vkr_launch_resolve_materials_fast(const shade_params* p, float* pixel_materials, void* stream);
 extern "C" int vkr_launch_resolve_materials_exact(const shade_params* p, float* pixel_materials, void* stream);
+typedef int (*sampler_launch_function_t)(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
+extern "C" int vkr_launch_texture_sampler_libm(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
+extern "C" int vkr_launch_texture_sampler_fast(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
+extern "C" int vkr_launch_texture_sampler_exact(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
 typedef int (*launch_function_t)(int, int, int, const shade_params*, unsigned int, void*);
 // [arithmetic_mode_t + 3 * light textures][strategy]
 #define VKR_LAUNCHER_ROW(mode) {vkr_launch_shade_##mode##_0, vkr_launch_shade_##mode##_1, vkr_launch_shade_##mode##_2, vkr_launch_shade_##mode##_3, vkr_launch_shade_##mode##_4}
@@ -31,6 +35,7 @@ static const launch_function_t g_launchers[6][5] = {
 };
 static const error_launch_function_t g_error_launchers[3] = {vkr_launch_error_display_libm, vkr_launch_error_display_fast, vkr_launch_error_display_exact};
 static const resolve_launch_function_t g_resolve_launchers[3] = {vkr_launch_resolve_materials_libm, vkr_launch_resolve_materials_fast, vkr_launch_resolve_materials_exact};
+static const sampler_launch_function_t g_sampler_launchers[3] = {vkr_launch_texture_sampler_libm, vkr_launch_texture_sampler_fast, vkr_launch_texture_sampler_exact};
 
 // Events that order streams of one device: a device-scope release is all they need.  The default
 // (system-scope fence: L2 write-back and invalidation at every record) is paid by whatever runs
@@ -1830,6 +1835,44 @@ extern "C" int evaluate_device_arithmetic(const device_t* device, uint32_t opera
 			|| hip_failed(hipStreamSynchronize(stream), "evaluating the arithmetic");
 	}
 	(void) hipFree(buffers);
+	return failed;
+}
+
+// evaluate_device_texture_sampler(): the chain, the sRGB table of the pass (vkr_fill_srgb_table, what create_scene uploads)
+// and the inputs go up, k_sample_texture of the chosen arithmetic mode runs, the samples come back
+extern "C" int evaluate_device_texture_sampler(const device_t* device, int32_t arithmetic_mode, const uint8_t* texels_rgba8, uint32_t width, uint32_t height, uint32_t mip_count, VkBool32 srgb, const float* inputs, float* out_rgba, uint32_t count) {
+	if (!device || !texels_rgba8 || !inputs || !out_rgba || arithmetic_mode < 0 || arithmetic_mode >= arithmetic_mode_count || width == 0 || height == 0 || width > 32768u || height > 32768u || mip_count == 0 || mip_count > 16u) {
+		printf("evaluate_device_texture_sampler() needs a device, an arithmetic mode, a texture of 1 ... 32768 texels a side with 1 ... 16 levels, inputs and an output.\n");
+		return 1;
+	}
+	if (!count) return 0;
+	size_t texel_count = 0;
+	for (uint32_t l = 0, w = width, h = height; l != mip_count; ++l) {
+		texel_count += (size_t) w * h;
+		w = w > 1 ? w / 2 : 1;
+		h = h > 1 ? h / 2 : 1;
+	}
+	hipStream_t stream = (hipStream_t) device->stream;
+	float table[256];
+	vkr_fill_srgb_table(table);
+	// one allocation: texels, table, inputs, outputs (each a multiple of 16 bytes long but the texels, which are padded)
+	size_t texel_bytes = (4 * texel_count + 15) & ~(size_t) 15, input_bytes = 6 * sizeof(float) * (size_t) count, output_bytes = 4 * sizeof(float) * (size_t) count;
+	size_t input_offset = texel_bytes + sizeof(table), output_offset = (input_offset + input_bytes + 15) & ~(size_t) 15;
+	uint8_t* buffer = NULL;
+	if (hip_failed(hipMalloc(&buffer, output_offset + output_bytes), "allocating the texture and the samples")) return 1;
+	int failed = hip_failed(hipMemcpyAsync(buffer, texels_rgba8, 4 * texel_count, hipMemcpyHostToDevice, stream), "uploading the texture")
+		|| hip_failed(hipMemcpyAsync(buffer + texel_bytes, table, sizeof(table), hipMemcpyHostToDevice, stream), "uploading the sRGB table")
+		|| hip_failed(hipMemcpyAsync(buffer + input_offset, inputs, input_bytes, hipMemcpyHostToDevice, stream), "uploading the sampler inputs");
+	if (!failed) {
+		shade_params p = {};  // (the sampler reads the texels and the table, nothing else)
+		p.texels = (const uint32_t*) buffer;
+		p.srgb_table = (const float*) (buffer + texel_bytes);
+		const uint32_t descriptor[4] = {0u, width, height, mip_count | (srgb ? 1u << 16 : 0u)};
+		failed = g_sampler_launchers[arithmetic_mode](&p, descriptor, (const float*) (buffer + input_offset), (float*) (buffer + output_offset), count, stream)
+			|| hip_failed(hipMemcpyAsync(out_rgba, buffer + output_offset, output_bytes, hipMemcpyDeviceToHost, stream), "reading the samples back")
+			|| hip_failed(hipStreamSynchronize(stream), "sampling the texture");
+	}
+	(void) hipFree(buffer);
 	return failed;
 }
 

@@ -257,6 +257,20 @@ class Renderer(HostScene):
         self.band_count = band_count
         self.inline_rays = inline_rays
 
+    def sample_texture(self, texture, inputs, arithmetic=None):
+        """The device's material texture sampler (evaluate_device_texture_sampler) on one texture - a dict with "texels"
+        (uint8, all levels, RGBA8), "width", "height", "mip_count", "srgb", as host_inputs() lists them - for inputs (n, 6):
+        uv, duv_dx, duv_dy.  -> (n, 4) float32, by the kernel of this renderer's arithmetic mode or the named one."""
+        texels = np.ascontiguousarray(texture["texels"], np.uint8)
+        inputs = np.ascontiguousarray(inputs, np.float32).reshape(-1, 6)
+        out = np.zeros((inputs.shape[0], 4), np.float32)
+        fp = C.POINTER(C.c_float)
+        if self.lib.evaluate_device_texture_sampler(self._dev(), ARITHMETIC_MODES[arithmetic or self.arithmetic], texels.ctypes.data,
+                                                    int(texture["width"]), int(texture["height"]), int(texture["mip_count"]), int(texture["srgb"]),
+                                                    inputs.ctypes.data_as(fp), out.ctypes.data_as(fp), inputs.shape[0]):
+            raise RuntimeError("evaluate_device_texture_sampler failed")
+        return out
+
     def create_targets(self):
         if self.app.render_targets.radiance:
             self.lib.destroy_render_targets(C.byref(self.app.render_targets), self._dev())

@@ -406,11 +406,14 @@ def encode_bc5(image):
 
 def procedural_textures(size=64, seed=3):
     """Base colour (sRGB), specular (occlusion, linear roughness, metalicity) and tangent-space
-    normal (xy in [0, 1]) images with features at several scales, so that every mip level matters."""
+    normal (xy in [0, 1]) images with features at several scales, so that every mip level matters.
+    size: the side of a square image, or (width, height)."""
+    width, height = (size, size) if np.isscalar(size) else size
     rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:size, 0:size].astype(np.float64) / size
+    y, x = np.mgrid[0:height, 0:width].astype(np.float64)
+    y, x = y / height, x / width
     checker = ((np.floor(x * 8) + np.floor(y * 8)) % 2)
-    noise = rng.random((size, size))
+    noise = rng.random((height, width))
     base = np.stack([0.25 + 0.6 * checker, 0.3 + 0.5 * x, 0.2 + 0.6 * noise], -1)
     specular = np.stack([np.ones_like(x), 0.25 + 0.5 * (0.5 + 0.5 * np.sin(12.0 * x) * np.cos(9.0 * y)), 0.3 * checker], -1)
     normal = np.stack([0.5 + 0.12 * np.sin(20.0 * x), 0.5 + 0.12 * np.cos(16.0 * y), np.ones_like(x)], -1)
@@ -418,15 +421,16 @@ def procedural_textures(size=64, seed=3):
     return to8(base), to8(specular), to8(normal)
 
 
-def write_textured_material_textures(directory, names, size=64, formats=("bc1_srgb", "rgba8", "bc5")):
+def write_textured_material_textures(directory, names, size=64, formats=("bc1_srgb", "rgba8", "bc5"), levels=None):
     """*.vkt files with real images for every material: BC1 sRGB base colour, RGBA8 specular,
-    BC5 normal by default (what the reference's converter produces); mip chains down to 1x1."""
+    BC5 normal by default (what the reference's converter produces); mip chains down to 1x1, or the
+    first `levels` levels of them.  size: the side of square images, or (width, height)."""
     os.makedirs(directory, exist_ok=True)
     for index, name in enumerate(names):
         base, specular, normal = procedural_textures(size, seed=3 + index)
         for image, suffix, kind in ((base, "BaseColor", formats[0]), (specular, "Specular", formats[1]), (normal, "Normal", formats[2])):
             rgba = np.concatenate([image, np.full(image.shape[:2] + (1,), 255, np.uint8)], -1)
-            chain = mip_chain(rgba)
+            chain = mip_chain(rgba)[:levels]
             extents = [(m.shape[1], m.shape[0]) for m in chain]
             if kind.startswith("bc1"):
                 payloads, vk_format = [encode_bc1(m) for m in chain], (VK_FORMAT_BC1_RGB_SRGB if kind.endswith("srgb") else VK_FORMAT_BC1_RGB_UNORM)
@@ -578,15 +582,16 @@ CONFIG_SETTINGS = {
 }
 
 
-def write_dataset(directory, grid=256, box_count=64, seed=1234, ltc_resolution=32, fresnel_count=51, textured=False, texture_size=64, shuffle_seed=None, large=None):
+def write_dataset(directory, grid=256, box_count=64, seed=1234, ltc_resolution=32, fresnel_count=51, textured=False, texture_size=64, shuffle_seed=None, large=None, texture_levels=None):
     """Writes scene.vks, textures/, ltc/ below `directory` and returns the paths.  textured:
-    real images (BC1 / RGBA8 / BC5 with mip chains) instead of constant material textures.
+    real images (BC1 / RGBA8 / BC5 with mip chains) instead of constant material textures, texture_size
+    a side or (width, height) across, the whole chains or their first texture_levels levels.
     large: a dict of make_large_scene_geometry() arguments ({} for its defaults: 2.7 M triangles, eight
     materials) instead of the benchmark scene of make_scene_geometry(grid, box_count)."""
     os.makedirs(directory, exist_ok=True)
     names = write_material_textures(os.path.join(directory, "textures"), LARGE_SCENE_MATERIALS if large is not None else None)
     if textured:
-        write_textured_material_textures(os.path.join(directory, "textures"), names, texture_size)
+        write_textured_material_textures(os.path.join(directory, "textures"), names, texture_size, levels=texture_levels)
     if large is not None:
         positions, normals, uvs, mats = make_large_scene_geometry(**dict({"seed": seed, "materials": len(names)}, **large))
     else:
