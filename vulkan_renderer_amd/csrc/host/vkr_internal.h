@@ -27,7 +27,7 @@ int vkr_device_upload(void** out, const device_t* device, const void* host, size
 int vkr_host_alloc_pinned(void** out, size_t size);
 /* lbvh_build.hip: an empty kernel on `stream` (create_hip_device() warms the queues up with it) */
 int vkr_launch_empty_kernel(void* stream);
-/* fills the per-device tables of the kernels (sRGB code thresholds) and waits for it (shading_pass.hip) */
+/* fills the per-device tables of the kernels (sRGB code thresholds) and waits for it (output_encoding.hip) */
 int vkr_fill_device_tables(void* stream);
 void vkr_host_free_pinned(void* pointer);
 int vkr_copy_to_device_async(void* device_pointer, const void* host, size_t size, const device_t* device);
@@ -64,7 +64,7 @@ int vkr_build_acceleration_structure(acceleration_structure_t* structure, const 
 int vkr_build_sah_bvh_host(const mesh_t* mesh, float pad, float** out_nodes, float** out_triangles, uint32_t* out_node_count);
 void vkr_destroy_acceleration_structure(acceleration_structure_t* structure, const device_t* device);
 
-/*! shading_pass.hip: scatters all-gathered slabs (format: slab_format_t of vkr_slab_exchange.h)
+/*! slab_assembly.hip: scatters all-gathered slabs (format: slab_format_t of vkr_slab_exchange.h)
 	into a frame on the given hipStream_t */
 int vkr_assemble_slabs_on_stream(application_t* app, const void* gathered_slabs, void* out_frame, int format, void* stream);
 /* (shading_pass.hip) `event`, a hipEvent_t, marks the end of a reader of [target, target + bytes): the next frame that

@@ -1,0 +1,38 @@
+// What the units of the shading pass's host side share (shading_pass.hip - the frame pipeline -, render_targets.hip,
+// output_encoding.hip, slab_assembly.hip, device_probes.hip): two small helpers and the functions that one unit calls in
+// another.  Functions only: the pipeline's structs stay private to shading_pass.hip.  The library is built with
+// -fvisibility=hidden, so none of these is exported.
+#pragma once
+#include "shading_kernel.h"
+#include "host/vkr_internal.h"
+
+inline int hip_failed(hipError_t error, const char* what) {
+	if (error == hipSuccess) return 0;
+	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
+	return 1;
+}
+
+inline vkr::bvh_view make_bvh_view(const acceleration_structure_t* structure) {
+	vkr::bvh_view view;
+	view.nodes = (const uint4*) structure->nodes;
+	view.triangles = (const float4*) structure->triangle_vertices;
+	view.node_count = structure->node_count;
+	view.grid_origin = vkr::f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]};
+	view.grid_inverse_cell = vkr::f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]};
+	return view;
+}
+
+// ---- shading_pass.hip ----
+// Call behind a kernel on device->stream that reads a buffer frames in flight write (the radiance
+// target, a caller's slab): the next frames wait for it before they resolve.
+void note_target_reader(application_t* app);
+// write_constants and, if the bytes changed, upload them into the next free slot on
+// `stream`; in any case `stream` is made to wait for the upload of the slot it will read
+int upload_constants(application_t* app, hipStream_t stream);
+// The tiling of `rank`'s slab (p: width, height and tile schedule); returns the slab's pixel count.  Rank 0 owns the most
+// tiles: its count is the stride of the slabs in a gathered buffer.
+uint64_t slab_tiling(const application_t* app, uint32_t rank, vkr::shade_params& p);
+
+// ---- output_encoding.hip ----
+// queues the kernel that encodes pixel_count pixels (a multiple of four) as packed RGB8
+void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream);

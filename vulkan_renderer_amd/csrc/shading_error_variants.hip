@@ -5,6 +5,7 @@
 // the combined diffuse + specular preparation (the other three strategies); no rays.
 // Built once per arithmetic mode.
 #include "shading_kernel.h"
+#include "shade_launchers.h"  // (the declarations that the callers of the three launchers below see)
 
 #if VKR_FAST_MATH
 #define VKR_ERROR_LAUNCH_NAME vkr_launch_error_display_fast

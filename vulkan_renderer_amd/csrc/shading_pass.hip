@@ -1,62 +1,27 @@
-// Host side of the shading pass: variant selection, constant upload, launches,
-// output encoding and read-back behind the reference's entry points
-// (create_shading_pass src/main.c:598, write_constants :2114, the vkCmdDraw of
-// record_render_frame_commands :1428-1434, implement_screenshot :1719).
+// The frame pipeline behind the reference's entry points (create_shading_pass src/main.c:598, write_constants :2114,
+// the vkCmdDraw of record_render_frame_commands :1428-1434): variant selection, constant upload, frame plan, band
+// steps, read-back ordering, timing, and the diagnostics that read the pipeline's private buffers (wavefront_kernels.h and
+// light_shafts.h define non-template kernels: one unit alone may include them).  The rest of the pass: pass_internal.h.
 #include "wavefront_kernels.h"
 #include "light_shafts.h"
-#include "host/vkr_internal.h"
-#include <hip/hip_fp16.h>
+#include "shade_launchers.h"
+#include "pass_internal.h"
 
 using namespace vkr;
 
-#define VKR_DECLARE_LAUNCH(mode, s) extern "C" int vkr_launch_shade_##mode##_##s(int technique, int capacity, int rays, const shade_params* p, unsigned int grid_x, void* stream);
-#define VKR_DECLARE_LAUNCHES(mode) VKR_DECLARE_LAUNCH(mode, 0) VKR_DECLARE_LAUNCH(mode, 1) VKR_DECLARE_LAUNCH(mode, 2) VKR_DECLARE_LAUNCH(mode, 3) VKR_DECLARE_LAUNCH(mode, 4)
-VKR_DECLARE_LAUNCHES(libm) VKR_DECLARE_LAUNCHES(fast) VKR_DECLARE_LAUNCHES(exact)
-VKR_DECLARE_LAUNCHES(textured_libm) VKR_DECLARE_LAUNCHES(textured_fast) VKR_DECLARE_LAUNCHES(textured_exact)
-
-typedef int (*error_launch_function_t)(int combined_path, int technique, int capacity, int error_mode, const shade_params* p, unsigned int grid_x, void* stream);
-extern "C" int vkr_launch_error_display_libm(int combined_path, int technique, int capacity, int error_mode, const shade_params* p, unsigned int grid_x, void* stream);
-extern "C" int vkr_launch_error_display_fast(int combined_path, int technique, int capacity, int error_mode, const shade_params* p, unsigned int grid_x, void* stream);
-extern "C" int vkr_launch_error_display_exact(int combined_path, int technique, int capacity, int error_mode, const shade_params* p, unsigned int grid_x, void* stream);
-typedef int (*resolve_launch_function_t)(const shade_params* p, float* pixel_materials, void* stream);
-extern "C" int vkr_launch_resolve_materials_libm(const shade_params* p, float* pixel_materials, void* stream);
-extern "C" int vkr_launch_resolve_materials_fast(const shade_params* p, float* pixel_materials, void* stream);
-extern "C" int vkr_launch_resolve_materials_exact(const shade_params* p, float* pixel_materials, void* stream);
-typedef int (*sampler_launch_function_t)(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
-extern "C" int vkr_launch_texture_sampler_libm(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
-extern "C" int vkr_launch_texture_sampler_fast(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
-extern "C" int vkr_launch_texture_sampler_exact(const shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream);
-typedef int (*launch_function_t)(int, int, int, const shade_params*, unsigned int, void*);
 // [arithmetic_mode_t + 3 * light textures][strategy]
 #define VKR_LAUNCHER_ROW(mode) {vkr_launch_shade_##mode##_0, vkr_launch_shade_##mode##_1, vkr_launch_shade_##mode##_2, vkr_launch_shade_##mode##_3, vkr_launch_shade_##mode##_4}
 static const launch_function_t g_launchers[6][5] = {
 	VKR_LAUNCHER_ROW(libm), VKR_LAUNCHER_ROW(fast), VKR_LAUNCHER_ROW(exact),
 	VKR_LAUNCHER_ROW(textured_libm), VKR_LAUNCHER_ROW(textured_fast), VKR_LAUNCHER_ROW(textured_exact),
 };
-static const error_launch_function_t g_error_launchers[3] = {vkr_launch_error_display_libm, vkr_launch_error_display_fast, vkr_launch_error_display_exact};
-static const resolve_launch_function_t g_resolve_launchers[3] = {vkr_launch_resolve_materials_libm, vkr_launch_resolve_materials_fast, vkr_launch_resolve_materials_exact};
-static const sampler_launch_function_t g_sampler_launchers[3] = {vkr_launch_texture_sampler_libm, vkr_launch_texture_sampler_fast, vkr_launch_texture_sampler_exact};
+static const error_launch_function_t g_error_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_error_display);
+static const resolve_launch_function_t g_resolve_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_resolve_materials);
 
 // Events that order streams of one device: a device-scope release is all they need.  The default
 // (system-scope fence: L2 write-back and invalidation at every record) is paid by whatever runs
 // next on the device, and a frame records several.
 constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
-
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
-static bvh_view make_bvh_view(const acceleration_structure_t* structure) {
-	bvh_view view;
-	view.nodes = (const uint4*) structure->nodes;
-	view.triangles = (const float4*) structure->triangle_vertices;
-	view.node_count = structure->node_count;
-	view.grid_origin = f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]};
-	view.grid_inverse_cell = f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]};
-	return view;
-}
 
 // The strategies that prepare a specular technique besides the diffuse one (the combined diffuse + specular path), and the
 // out-of-range strategies, which select the same preparation (validate_settings)
@@ -93,49 +58,12 @@ static bool aims_at_light_polygon(int technique) {
 	return technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniqueSolidAngle || technique == kTechniqueClippedSolidAngle;
 }
 
-// ---- render targets --------------------------------------------------------------
-
-extern "C" void destroy_render_targets(render_targets_t* targets, const device_t* device) {
-	vkr_device_free(targets->visibility_buffer, device);
-	vkr_device_free(targets->radiance, device);
-	vkr_device_free(targets->encoded, device);
-	memset(targets, 0, sizeof(*targets));
-}
-
-extern "C" int create_render_targets(render_targets_t* targets, const device_t* device, const swapchain_t* swapchain) {
-	memset(targets, 0, sizeof(*targets));
-	if (!device) {
-		printf("Render targets live in device memory; a HIP device is required.\n");
-		return 1;
-	}
-	size_t pixels = (size_t) swapchain->extent.width * swapchain->extent.height;
-	if (pixels == 0) return 2;  // reference main.c:1865: a minimised window is not an error
-	targets->extent = swapchain->extent;
-	// slabs are padded to whole tiles, so leave room for one extra row and column of 64-pixel tiles
-	size_t padded = ((size_t) swapchain->extent.width + 64) * ((size_t) swapchain->extent.height + 64);
-	if (vkr_device_alloc(&targets->visibility_buffer, device, sizeof(uint32_t) * pixels, "the visibility buffer")
-		|| vkr_device_alloc(&targets->radiance, device, sizeof(float) * 4 * padded, "the radiance target")
-		|| vkr_device_alloc(&targets->encoded, device, 4 * pixels, "the encoded output"))
-	{
-		destroy_render_targets(targets, device);
-		return 1;
-	}
-	hipStream_t stream = (hipStream_t) device->stream;
-	if (hip_failed(hipMemsetAsync(targets->visibility_buffer, 0xFF, sizeof(uint32_t) * pixels, stream), "clearing the visibility buffer")) {
-		destroy_render_targets(targets, device);
-		return 1;
-	}
-	return 0;
-}
-
 // ---- shading pass ----------------------------------------------------------------
 
 // events of a timed frame: its start, the start and the end of the (last band's) shading kernel, its end
 constexpr uint32_t kTimingFrameStart = 0, kTimingShadingStart = 1, kTimingShadingEnd = 2, kTimingFrameEnd = 3, kTimingEvents = 4;
 
 static hipEvent_t timing_event(const shading_pass_t* pass, uint32_t slot, uint32_t which) { return ((hipEvent_t*) pass->timing_ring)[kTimingEvents * slot + which]; }
-
-// device counter of traced shadow rays, shared by all passes of the process
 
 // Buffers of the wavefront ray path, sized for the worst case (every sample of every
 // light on every pixel produces a term and a ray) and owned by the pass.
@@ -151,8 +79,8 @@ struct wavefront_buffers {
 	uint32_t thread_count, max_terms, max_codes, queue_capacity, thread_bits;
 	// the streams that only some settings need are allocated when they first do: values of blocked
 	// terms (only the plain optimal MIS heuristic has non-zero ones), colour before the sampled terms
-	// (only the light display has one)
-	bool has_hidden_terms, has_base_color;
+	// (only the light display has one); their element counts, 0 while they do not exist
+	size_t hidden_term_count, base_color_count;
 	// stack entries beyond the LDS part of trace_shadow_rays_wide, [entry][thread of the trace grid];
 	// allocated only for trees that can need them
 	uint32_t* spill;
@@ -168,7 +96,7 @@ struct wavefront_buffers {
 	size_t shaft_words;
 	// ... and per light the plane-space rectangle that the shading kernel tests its rays against
 	float4* shaft_rectangles;
-	uint32_t shaft_rectangle_count;
+	size_t shaft_rectangle_count;
 	// ... and per pair kShaftListMax triangle slots: the occluder lists (VKR_SHAFT_LISTS)
 	float* shaft_lists;
 	size_t shaft_list_words;
@@ -309,65 +237,52 @@ static uint32_t ray_block_size(uint32_t max_terms) { return max_terms >= 8 ? 256
 constexpr uint32_t kLeafBatch = 16;
 constexpr uint32_t kRefillThreshold = 0;
 
-static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light_count, bool lists, hipStream_t stream) {
-	size_t list_words = lists ? words * kShaftListMax * kShaftListEntry : 0;
-	// (the tables carry state from frame to frame: whichever of them is allocated anew, the copy of the inputs is forgotten)
-	if (list_words > w->shaft_list_words) {
-		(void) hipFree(w->shaft_lists);
-		w->shaft_lists = NULL; w->shaft_list_words = 0; w->shaft_seen_size = 0;
-		if (hipMalloc(&w->shaft_lists, list_words * sizeof(float)) != hipSuccess) {
-			printf("Failed to allocate %.1f MiB for the occluder lists of the light shafts.\n", list_words * 4.0 / 1048576.0);
-			return 1;
-		}
-		w->shaft_list_words = list_words;
-	}
-	if (light_count > w->shaft_rectangle_count) {
-		(void) hipFree(w->shaft_rectangles);
-		w->shaft_rectangles = NULL; w->shaft_rectangle_count = 0; w->shaft_seen_size = 0;
-		if (hipMalloc(&w->shaft_rectangles, sizeof(float4) * light_count) != hipSuccess) {
-			printf("Failed to allocate the rectangles of the light shafts.\n");
-			return 1;
-		}
-		w->shaft_rectangle_count = light_count;
-	}
-	if (words <= w->shaft_words) return 0;
-	(void) hipFree(w->shaft_clear);
-	w->shaft_clear = NULL; w->shaft_words = 0; w->shaft_seen_size = 0;
-	if (hipMalloc(&w->shaft_clear, words * sizeof(uint32_t)) != hipSuccess) {
-		printf("Failed to allocate %.1f MiB for the light shafts.\n", words * 4.0 / 1048576.0);
-		return 1;
-	}
-	// (the shaft kernel reads the verdicts of the frame before: none yet)
-	if (hipMemsetAsync(w->shaft_clear, 0, words * sizeof(uint32_t), stream) != hipSuccess) return 1;
-	w->shaft_words = words;
+// host memory that grows on demand and keeps its content
+static int grow_bytes(uint8_t** buffer, size_t* capacity, size_t size) {
+	if (*capacity >= size) return 0;
+	uint8_t* grown = (uint8_t*) realloc(*buffer, size);
+	if (!grown) return 1;
+	*buffer = grown;
+	*capacity = size;
 	return 0;
 }
 
-static int ensure_psa_table_memory(wavefront_buffers* w, size_t bytes) {
-	if (bytes <= w->psa_table_bytes) return 0;
-	// (frees while other frames may be in flight: hipFree waits for the device)
-	(void) hipFree(w->psa_table_memory);
-	w->psa_table_memory = NULL; w->psa_table_bytes = 0;
-	if (hipMalloc(&w->psa_table_memory, bytes) != hipSuccess) {
-		printf("Failed to allocate %.1f MiB for the polygon tables that do not fit into LDS.\n", bytes / 1048576.0);
+// The same for a device buffer of `count` elements, whose content is not kept: a buffer that is too small is freed
+// (while other frames may be in flight: hipFree waits for the device) and allocated anew.  On failure pointer and count
+// are zero and `message` is printed, a format for the MiB that were asked for.
+template <typename T>
+static int grow_device_buffer(T** buffer, size_t* count, size_t wanted, size_t element_bytes, const char* message) {
+	if (wanted <= *count) return 0;
+	(void) hipFree(*buffer);
+	*buffer = NULL; *count = 0;
+	if (hipMalloc(buffer, wanted * element_bytes) != hipSuccess) {
+		printf(message, wanted * element_bytes / 1048576.0);
 		return 1;
 	}
-	w->psa_table_bytes = bytes;
+	*count = wanted;
+	return 0;
+}
+
+static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light_count, bool lists, hipStream_t stream) {
+	size_t list_words = lists ? words * kShaftListMax * kShaftListEntry : 0;
+	const bool fresh_words = words > w->shaft_words;
+	// (the tables carry state from frame to frame: whichever of them is allocated anew, the copy of the inputs is forgotten)
+	if (list_words > w->shaft_list_words || light_count > w->shaft_rectangle_count || fresh_words) w->shaft_seen_size = 0;
+	if (grow_device_buffer(&w->shaft_lists, &w->shaft_list_words, list_words, sizeof(float), "Failed to allocate %.1f MiB for the occluder lists of the light shafts.\n")
+		|| grow_device_buffer(&w->shaft_rectangles, &w->shaft_rectangle_count, light_count, sizeof(float4), "Failed to allocate the rectangles of the light shafts.\n")
+		|| grow_device_buffer(&w->shaft_clear, &w->shaft_words, words, sizeof(uint32_t), "Failed to allocate %.1f MiB for the light shafts.\n"))
+		return 1;
+	// (the shaft kernel reads the verdicts of the frame before: none yet)
+	if (fresh_words && hipMemsetAsync(w->shaft_clear, 0, words * sizeof(uint32_t), stream) != hipSuccess) {
+		w->shaft_words = 0;
+		return 1;
+	}
 	return 0;
 }
 
 static int ensure_spill(wavefront_buffers* w, uint32_t stack_need, uint32_t in_lds, uint32_t trace_threads) {
 	size_t entries = stack_need > in_lds ? (size_t) (stack_need - in_lds) * trace_threads : 0;
-	if (entries <= w->spill_entries) return 0;
-	// (frees while other frames may be in flight: hipFree waits for the device)
-	(void) hipFree(w->spill);
-	w->spill = NULL; w->spill_entries = 0;
-	if (hipMalloc(&w->spill, entries * sizeof(uint32_t)) != hipSuccess) {
-		printf("Failed to allocate %.1f MiB for the traversal stacks that do not fit into LDS.\n", entries * 4.0 / 1048576.0);
-		return 1;
-	}
-	w->spill_entries = entries;
-	return 0;
+	return grow_device_buffer(&w->spill, &w->spill_entries, entries, sizeof(uint32_t), "Failed to allocate %.1f MiB for the traversal stacks that do not fit into LDS.\n");
 }
 
 // Bytes per term slot of the streams every frame needs (visible value 12, code 1) and per ray slot (20)
@@ -396,15 +311,8 @@ static int ensure_wavefront(wavefront_buffers* w, uint32_t thread_count, uint32_
 	size_t terms = (size_t) max_terms * thread_count;
 	if (w->codes && w->thread_count == thread_count && w->max_terms == max_terms && w->max_codes == max_codes) {
 		// (frames in flight may still use the other streams of this context: allocating does not disturb them)
-		if (hidden_terms && !w->has_hidden_terms) {
-			if (hipMalloc(&w->terms_hidden, terms * 12) != hipSuccess) { printf("Failed to allocate %.1f MiB for the values of blocked terms.\n", terms * 12.0 / 1048576.0); return 1; }
-			w->has_hidden_terms = true;
-		}
-		if (base_color && !w->has_base_color) {
-			if (hipMalloc(&w->base_color, sizeof(float4) * (size_t) thread_count) != hipSuccess) { printf("Failed to allocate the colours of the light display.\n"); return 1; }
-			w->has_base_color = true;
-		}
-		return 0;
+		return (hidden_terms && grow_device_buffer(&w->terms_hidden, &w->hidden_term_count, terms, 12, "Failed to allocate %.1f MiB for the values of blocked terms.\n"))
+			|| (base_color && grow_device_buffer(&w->base_color, &w->base_color_count, thread_count, sizeof(float4), "Failed to allocate the colours of the light display.\n"));
 	}
 	free_wavefront_buffers(w);
 	w->thread_count = thread_count; w->max_terms = max_terms; w->max_codes = max_codes;
@@ -433,8 +341,8 @@ static int ensure_wavefront(wavefront_buffers* w, uint32_t thread_count, uint32_
 		free_wavefront_buffers(w);
 		return 1;
 	}
-	w->has_hidden_terms = hidden_terms;
-	w->has_base_color = base_color;
+	w->hidden_term_count = hidden_terms ? terms : 0;
+	w->base_color_count = base_color ? thread_count : 0;
 	return 0;
 }
 
@@ -466,9 +374,7 @@ extern "C" int finish_frames(application_t* app) {
 	return failed;
 }
 
-// Call behind a kernel on device->stream that reads a buffer frames in flight write (the radiance
-// target, a caller's slab): the next frames wait for it before they resolve.
-static void note_target_reader(application_t* app) {
+void note_target_reader(application_t* app) {
 	frame_pipeline* frames = (frame_pipeline*) app->shading_pass.wavefront;
 	if (!frames || !app->shading_pass.last_frame_in_flight) return;
 	if (hipEventRecord(frames->readers_done, (hipStream_t) app->device.stream) == hipSuccess) ++frames->readers_generation;
@@ -532,9 +438,7 @@ static int create_constants_ring(shading_pass_t* pass, const device_t* device) {
 	return 0;
 }
 
-// write_constants and, if the bytes changed, upload them into the next free slot on
-// `stream`; in any case `stream` is made to wait for the upload of the slot it will read
-static int upload_constants(application_t* app, hipStream_t stream) {
+int upload_constants(application_t* app, hipStream_t stream) {
 	shading_pass_t* pass = &app->shading_pass;
 	constants_ring* ring = (constants_ring*) pass->constants_ring;
 	// a frame stream that does not exist yet is marked by `present`: a NULL stream is a stream too
@@ -879,8 +783,8 @@ extern "C" int create_shading_pass(shading_pass_t* pass, application_t* app) {
 	return 0;
 }
 
-static void fill_tile_schedule(shade_params& p, const application_t* app, uint32_t& grid_blocks) {
-	tile_schedule_t schedule = app->tile_schedule;
+// (schedule: the caller's copy of the application's)
+static void fill_tile_schedule(shade_params& p, tile_schedule_t schedule, uint32_t& grid_blocks) {
 	if (schedule.rank_count <= 1) { schedule.rank = 0; schedule.rank_count = 1; }
 	// tile_size 0: automatic.  The blocks of a tile are consecutive in the launch, so the tile size decides which 16x16 blocks
 	// are in flight together: raster order of blocks (tile 16) spreads the resident waves over a band of the whole frame width,
@@ -904,39 +808,15 @@ static void fill_tile_schedule(shade_params& p, const application_t* app, uint32
 	grid_blocks = own_tiles * blocks_per_tile;
 }
 
-// The tiling of `rank`'s slab (p: width, height and tile schedule); returns the slab's pixel count.  Rank 0 owns the most
-// tiles: its count is the stride of the slabs in a gathered buffer.
-static uint64_t slab_tiling(const application_t* app, uint32_t rank, shade_params& p) {
+uint64_t slab_tiling(const application_t* app, uint32_t rank, shade_params& p) {
 	memset(&p, 0, sizeof(p));
 	p.width = app->swapchain.extent.width;
 	p.height = app->swapchain.extent.height;
-	application_t copy = *app;
-	copy.tile_schedule.rank = rank;
+	tile_schedule_t schedule = app->tile_schedule;
+	schedule.rank = rank;
 	uint32_t grid_blocks = 0;
-	fill_tile_schedule(p, &copy, grid_blocks);
+	fill_tile_schedule(p, schedule, grid_blocks);
 	return (uint64_t) grid_blocks * 256;
-}
-
-extern "C" uint64_t get_slab_pixel_count(const application_t* app, uint32_t rank) {
-	shade_params p;
-	return slab_tiling(app, rank, p);
-}
-
-static void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream);
-
-static int render_pass(application_t* app, void* out_radiance, void* out_rgb8);
-extern "C" int get_traversal_statistics_of_tree(application_t* app, VkBool32 wide_tree, uint64_t out_statistics[8]);
-
-extern "C" int render_shading_pass(application_t* app, void* out_radiance) {
-	return render_pass(app, out_radiance, NULL);
-}
-
-extern "C" int render_shading_pass_encoded(application_t* app, void* out_radiance, void* out_rgb8) {
-	if (!out_rgb8) {
-		printf("render_shading_pass_encoded() needs a target for the encoded pixels.\n");
-		return 1;
-	}
-	return render_pass(app, out_radiance, out_rgb8);
 }
 
 // What render_pass() decides about a frame before its first band (plan_frame, plan_bands); the band steps read it
@@ -1029,7 +909,7 @@ static int plan_frame(application_t* app, void* out_radiance, frame_plan* f) {
 		printf("The render targets do not match the swapchain extent.\n");
 		return 1;
 	}
-	fill_tile_schedule(p, app, f->grid_blocks);
+	fill_tile_schedule(p, app->tile_schedule, f->grid_blocks);
 	f->ray_mode = !pass->use_ray_tracing ? kRaysNone : (pass->inline_rays ? kRaysInline : kRaysDeferred);
 	plan_error_display(app, f);
 	if (f->error_mode == kErrorNone && f->strategy >= (int) sampling_strategies_count) {
@@ -1205,7 +1085,8 @@ static int take_frame_context(application_t* app, frame_plan* f, frame_context**
 	if (f->table_in_memory) {
 		// a region per workgroup of the launch, in the launch's own buffers (shading_kernel.h psa_table_in_memory)
 		wavefront_buffers* owner = frame ? &frame->buffers : &frames->device_stream_buffers;
-		if (ensure_psa_table_memory(owner, (size_t) shade_grid_size(f->blocks_per_band) * f->table_bytes_per_workgroup)) return 1;
+		const size_t bytes = (size_t) shade_grid_size(f->blocks_per_band) * f->table_bytes_per_workgroup;
+		if (grow_device_buffer(&owner->psa_table_memory, &owner->psa_table_bytes, bytes, 1, "Failed to allocate %.1f MiB for the polygon tables that do not fit into LDS.\n")) return 1;
 		p.psa_table_memory = owner->psa_table_memory;
 	}
 	app->shading_pass.last_frame_stream = *stream;
@@ -1267,15 +1148,6 @@ struct shaft_arrangement {
 	float grid_origin[3], grid_inverse_cell[3];
 };
 static_assert(sizeof(shaft_arrangement) == 22 * 4 + 5 * sizeof(void*) + 6 * 4, "no padding: the struct is compared as bytes");
-
-static int grow_bytes(uint8_t** buffer, size_t* capacity, size_t size) {
-	if (*capacity >= size) return 0;
-	uint8_t* grown = (uint8_t*) realloc(*buffer, size);
-	if (!grown) return 1;
-	*buffer = grown;
-	*capacity = size;
-	return 0;
-}
 
 // Puts the image of this launch's inputs together, compares it with the context's copy and keeps it as the new copy.
 // -> arrangement_same, same_lights (bit i: arrangement and light i < 32 are byte-equal to the previous launch's)
@@ -1528,6 +1400,18 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 	return 0;
 }
 
+extern "C" int render_shading_pass(application_t* app, void* out_radiance) {
+	return render_pass(app, out_radiance, NULL);
+}
+
+extern "C" int render_shading_pass_encoded(application_t* app, void* out_radiance, void* out_rgb8) {
+	if (!out_rgb8) {
+		printf("render_shading_pass_encoded() needs a target for the encoded pixels.\n");
+		return 1;
+	}
+	return render_pass(app, out_radiance, out_rgb8);
+}
+
 // timed frames whose events are still in the ring
 static uint32_t timed_frames(const shading_pass_t* pass) { return pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size; }
 
@@ -1698,184 +1582,6 @@ __global__ void __launch_bounds__(256) k_traversal_statistics_wide(bvh_view bvh,
 	if (blocked_visits) atomicAdd(out + 9, blocked_visits);
 }
 
-// evaluate_device_arithmetic(): the primitives as the shading kernels use them (this translation unit
-// is compiled in exact mode, -ffp-contract=off)
-__global__ void __launch_bounds__(256) k_evaluate_arithmetic(uint32_t operation, const float* a, const float* b, float* out, uint32_t count) {
-	uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= count) return;
-	float x = a[i], y = b ? b[i] : 0.0f;
-	switch (operation) {
-	case 0: out[i] = divide(x, y); break;
-	case 1: out[i] = square_root(x); break;
-	case 2: out[i] = rsqrt(x); break;
-	case 3: out[i] = x / y; break;
-	case 4: out[i] = sqrtf(x); break;
-	// the functions of the libm arithmetic mode (glibc_math.h with this file's divide / square_root)
-	case 5: out[i] = gm_atanf(x); break;
-	case 6: out[i] = gm_acosf(x); break;
-	case 7: out[i] = gm_sinf(x); break;
-	case 8: out[i] = gm_cosf(x); break;
-	case 9: out[i] = gm_log2f(x); break;
-	case 10: out[i] = gm_powf(x, y); break;
-	case 11: out[i] = gm_atan2f(x, y); break;
-	case 12: out[i] = inverse_square_root_ieee(x); break;
-	default: out[i] = rsqrt(x); break;  // (what the kernels of this unit's arithmetic mode use)
-	}
-}
-
-// compare_device_arithmetic(): two one-argument operations of k_evaluate_arithmetic over a range of bit
-// patterns, without moving the arguments through the host
-__device__ __forceinline__ float evaluate_unary(uint32_t operation, float x, const gm_atan_row_t* atan_rows) {
-	switch (operation) {
-	case 17: return gm_atanf_rows(x, atan_rows);
-	case 1: return square_root(x);
-	case 4: return sqrtf(x);
-	case 5: return gm_atanf(x);
-	case 12: return inverse_square_root_ieee(x);
-	case 16: return 1.0f / sqrtf(x);
-	default: return rsqrt(x);
-	}
-}
-__global__ void __launch_bounds__(256) k_compare_arithmetic(uint32_t operation_a, uint32_t operation_b, uint32_t first_bits, uint64_t count, unsigned long long* out) {
-	// (the table of the arctangent's argument ranges, in LDS as in the shading kernels)
-	__shared__ gm_atan_row_t atan_rows[GM_ATAN_ROW_COUNT];
-	for (uint32_t i = threadIdx.x; i < GM_ATAN_ROW_COUNT; i += 256u) atan_rows[i] = gm_atan_row(i);
-	__syncthreads();
-	unsigned long long mismatches = 0;
-	for (uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x; i < count; i += (uint64_t) gridDim.x * 256u) {
-		uint32_t bits = first_bits + (uint32_t) i;
-		float x = __uint_as_float(bits), a = evaluate_unary(operation_a, x, atan_rows), b = evaluate_unary(operation_b, x, atan_rows);
-		bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-		if (!same) { ++mismatches; atomicMin(out + 1, (unsigned long long) bits); }
-	}
-	if (mismatches) atomicAdd(out, mismatches);
-}
-
-extern "C" int compare_device_arithmetic(const device_t* device, uint32_t operation_a, uint32_t operation_b, uint32_t first_bits, uint64_t count, uint64_t out_mismatches_and_first[2]) {
-	if (!device || !out_mismatches_and_first || count > (1ull << 32)) {
-		printf("compare_device_arithmetic() needs a device, an output and at most 2^32 arguments.\n");
-		return 1;
-	}
-	unsigned long long* counters = NULL;
-	if (hip_failed(hipMalloc(&counters, 2 * sizeof(unsigned long long)), "allocating counters")) return 1;
-	hipStream_t stream = (hipStream_t) device->stream;
-	unsigned long long initial[2] = {0ull, ~0ull};
-	int failed = hip_failed(hipMemcpyAsync(counters, initial, sizeof(initial), hipMemcpyHostToDevice, stream), "clearing counters");
-	if (!failed) {
-		k_compare_arithmetic<<<8192, 256, 0, stream>>>(operation_a, operation_b, first_bits, count, counters);
-		failed = vkr_copy_to_host(out_mismatches_and_first, counters, 2 * sizeof(unsigned long long), device);
-	}
-	(void) hipFree(counters);
-	return failed;
-}
-
-// compare_device_division(): divide() against the compiler's IEEE a / b for a block of divisor
-// significands and EVERY dividend significand (blockIdx.y = divisor, the threads of its blocks share the dividends)
-__global__ void __launch_bounds__(256) k_compare_division(uint32_t first_significand, uint32_t stride, uint32_t dividend_exponent, uint32_t divisor_exponent, unsigned long long* out) {
-	const uint32_t b_bits = (divisor_exponent << 23) | ((first_significand + blockIdx.y * stride) & 0x7FFFFFu);
-	const float b = __uint_as_float(b_bits);
-	unsigned long long mismatches = 0;
-	for (uint32_t m = blockIdx.x * 256u + threadIdx.x; m < (1u << 23); m += gridDim.x * 256u) {
-		const uint32_t a_bits = (dividend_exponent << 23) | m;
-		const float a = __uint_as_float(a_bits);
-		float mine = divide(a, b), theirs = __fdiv_rn(a, b);
-		bool same = __float_as_uint(mine) == __float_as_uint(theirs) || (mine != mine && theirs != theirs);
-		if (!same) { ++mismatches; atomicMin(out + 1, ((unsigned long long) b_bits << 32) | a_bits); }
-	}
-	if (mismatches) atomicAdd(out, mismatches);
-}
-
-extern "C" int compare_device_division(const device_t* device, uint32_t first_significand, uint32_t divisor_count, uint32_t stride, uint32_t dividend_exponent, uint32_t divisor_exponent, uint64_t out_mismatches_and_first[2]) {
-	if (!device || !out_mismatches_and_first || divisor_count == 0 || divisor_count > 65535u || dividend_exponent > 254u || divisor_exponent > 254u) {
-		printf("compare_device_division() needs a device, an output, 1 ... 65535 divisors and biased exponents below 255.\n");
-		return 1;
-	}
-	unsigned long long* counters = NULL;
-	if (hip_failed(hipMalloc(&counters, 2 * sizeof(unsigned long long)), "allocating counters")) return 1;
-	hipStream_t stream = (hipStream_t) device->stream;
-	unsigned long long initial[2] = {0ull, ~0ull};
-	int failed = hip_failed(hipMemcpyAsync(counters, initial, sizeof(initial), hipMemcpyHostToDevice, stream), "clearing counters");
-	if (!failed) {
-		k_compare_division<<<dim3(32, divisor_count), 256, 0, stream>>>(first_significand, stride, dividend_exponent, divisor_exponent, counters);
-		failed = vkr_copy_to_host(out_mismatches_and_first, counters, 2 * sizeof(unsigned long long), device);
-	}
-	(void) hipFree(counters);
-	return failed;
-}
-
-__global__ void __launch_bounds__(256) k_copy_with_workgroups(uint4* destination, const uint4* source, uint64_t count) {
-	for (uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x; i < count; i += (uint64_t) gridDim.x * 256u) destination[i] = source[i];
-}
-
-extern "C" int copy_with_workgroups(void* destination, const void* source, uint64_t bytes, uint32_t workgroups, void* stream) {
-	if (!destination || !source || bytes % 16 != 0 || workgroups == 0) {
-		printf("copy_with_workgroups() needs two device buffers, a multiple of 16 bytes and at least one workgroup.\n");
-		return 1;
-	}
-	if (bytes == 0) return 0;
-	k_copy_with_workgroups<<<workgroups, 256, 0, (hipStream_t) stream>>>((uint4*) destination, (const uint4*) source, bytes / 16);
-	return hip_failed(hipGetLastError(), "launching the copy");
-}
-
-extern "C" int evaluate_device_arithmetic(const device_t* device, uint32_t operation, const float* a, const float* b, float* out, uint32_t count) {
-	if (!device || !a || !out || operation > 12 || ((operation == 0 || operation == 3 || operation == 10 || operation == 11) && !b)) {
-		printf("evaluate_device_arithmetic() needs a device, operands and an operation in 0 ... 12.\n");
-		return 1;
-	}
-	if (!count) return 0;
-	hipStream_t stream = (hipStream_t) device->stream;
-	float* buffers = NULL;
-	size_t bytes = sizeof(float) * (size_t) count;
-	if (hip_failed(hipMalloc(&buffers, 3 * bytes), "allocating the operands")) return 1;
-	int failed = hip_failed(hipMemcpyAsync(buffers, a, bytes, hipMemcpyHostToDevice, stream), "uploading the operands")
-		|| (b && hip_failed(hipMemcpyAsync(buffers + count, b, bytes, hipMemcpyHostToDevice, stream), "uploading the operands"));
-	if (!failed) {
-		k_evaluate_arithmetic<<<(count + 255u) / 256u, 256, 0, stream>>>(operation, buffers, b ? buffers + count : NULL, buffers + 2 * (size_t) count, count);
-		failed = hip_failed(hipMemcpyAsync(out, buffers + 2 * (size_t) count, bytes, hipMemcpyDeviceToHost, stream), "reading the results back")
-			|| hip_failed(hipStreamSynchronize(stream), "evaluating the arithmetic");
-	}
-	(void) hipFree(buffers);
-	return failed;
-}
-
-// evaluate_device_texture_sampler(): the chain, the sRGB table of the pass (vkr_fill_srgb_table, what create_scene uploads)
-// and the inputs go up, k_sample_texture of the chosen arithmetic mode runs, the samples come back
-extern "C" int evaluate_device_texture_sampler(const device_t* device, int32_t arithmetic_mode, const uint8_t* texels_rgba8, uint32_t width, uint32_t height, uint32_t mip_count, VkBool32 srgb, const float* inputs, float* out_rgba, uint32_t count) {
-	if (!device || !texels_rgba8 || !inputs || !out_rgba || arithmetic_mode < 0 || arithmetic_mode >= arithmetic_mode_count || width == 0 || height == 0 || width > 32768u || height > 32768u || mip_count == 0 || mip_count > 16u) {
-		printf("evaluate_device_texture_sampler() needs a device, an arithmetic mode, a texture of 1 ... 32768 texels a side with 1 ... 16 levels, inputs and an output.\n");
-		return 1;
-	}
-	if (!count) return 0;
-	size_t texel_count = 0;
-	for (uint32_t l = 0, w = width, h = height; l != mip_count; ++l) {
-		texel_count += (size_t) w * h;
-		w = w > 1 ? w / 2 : 1;
-		h = h > 1 ? h / 2 : 1;
-	}
-	hipStream_t stream = (hipStream_t) device->stream;
-	float table[256];
-	vkr_fill_srgb_table(table);
-	// one allocation: texels, table, inputs, outputs (each a multiple of 16 bytes long but the texels, which are padded)
-	size_t texel_bytes = (4 * texel_count + 15) & ~(size_t) 15, input_bytes = 6 * sizeof(float) * (size_t) count, output_bytes = 4 * sizeof(float) * (size_t) count;
-	size_t input_offset = texel_bytes + sizeof(table), output_offset = (input_offset + input_bytes + 15) & ~(size_t) 15;
-	uint8_t* buffer = NULL;
-	if (hip_failed(hipMalloc(&buffer, output_offset + output_bytes), "allocating the texture and the samples")) return 1;
-	int failed = hip_failed(hipMemcpyAsync(buffer, texels_rgba8, 4 * texel_count, hipMemcpyHostToDevice, stream), "uploading the texture")
-		|| hip_failed(hipMemcpyAsync(buffer + texel_bytes, table, sizeof(table), hipMemcpyHostToDevice, stream), "uploading the sRGB table")
-		|| hip_failed(hipMemcpyAsync(buffer + input_offset, inputs, input_bytes, hipMemcpyHostToDevice, stream), "uploading the sampler inputs");
-	if (!failed) {
-		shade_params p = {};  // (the sampler reads the texels and the table, nothing else)
-		p.texels = (const uint32_t*) buffer;
-		p.srgb_table = (const float*) (buffer + texel_bytes);
-		const uint32_t descriptor[4] = {0u, width, height, mip_count | (srgb ? 1u << 16 : 0u)};
-		failed = g_sampler_launchers[arithmetic_mode](&p, descriptor, (const float*) (buffer + input_offset), (float*) (buffer + output_offset), count, stream)
-			|| hip_failed(hipMemcpyAsync(out_rgba, buffer + output_offset, output_bytes, hipMemcpyDeviceToHost, stream), "reading the samples back")
-			|| hip_failed(hipStreamSynchronize(stream), "sampling the texture");
-	}
-	(void) hipFree(buffer);
-	return failed;
-}
-
 // the wavefront buffers of the most recent launch with wavefront rays (the last band of the last frame), or NULL
 static const wavefront_buffers* last_launch_buffers(const application_t* app) {
 	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
@@ -1984,289 +1690,4 @@ extern "C" uint64_t get_last_ray_count(const application_t* app) {
 	if (finish_frames((application_t*) app)) return 0;
 	if (vkr_copy_to_host(&rays, (const unsigned long long*) pass->ray_counter + (pass->frame_counter - 1u) % 16u, sizeof(rays), &app->device)) return 0;
 	return rays;
-}
-
-// ---- slabs -> frame ----------------------------------------------------------------
-
-template <typename PIXEL>
-__global__ void __launch_bounds__(256) k_assemble_frame(const PIXEL* slabs, PIXEL* frame, uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tiles_x, uint32_t rank_count, uint64_t slab_stride) {
-	uint32_t px = blockIdx.x * 16 + (threadIdx.x & 15), py = blockIdx.y * 16 + (threadIdx.x >> 4);
-	if (px >= width || py >= height) return;
-	uint32_t tx = px / tile_size, ty = py / tile_size;
-	uint32_t tile = ty * tiles_x + tx;
-	uint32_t rank = tile % rank_count, local_tile = tile / rank_count;
-	uint32_t ix = px - tx * tile_size, iy = py - ty * tile_size;
-	frame[(size_t) py * width + px] = slabs[rank * slab_stride + (size_t) local_tile * tile_size * tile_size + (size_t) iy * tile_size + ix];
-}
-
-template <typename PIXEL>
-static int assemble_slabs(application_t* app, const void* gathered_slabs, void* out_frame, hipStream_t stream) {
-	shade_params p;
-	uint64_t slab_stride = slab_tiling(app, 0, p);
-	dim3 grid((p.width + 15) / 16, (p.height + 15) / 16);
-	k_assemble_frame<PIXEL><<<grid, 256, 0, stream>>>((const PIXEL*) gathered_slabs, (PIXEL*) out_frame,
-		p.width, p.height, p.tile_size, p.tiles_x, p.rank_count, slab_stride);
-	return hip_failed(hipGetLastError(), "assembling the frame");
-}
-
-extern "C" int assemble_frame_from_slabs(application_t* app, const void* gathered_slabs, void* out_radiance) {
-	// (the radiance target may still be written by frames in flight)
-	if (finish_frames(app)) return 1;
-	return assemble_slabs<float4>(app, gathered_slabs, out_radiance ? out_radiance : app->render_targets.radiance, (hipStream_t) app->device.stream);
-}
-
-extern "C" int assemble_encoded_frame_from_slabs(application_t* app, const void* gathered_slabs, void* out_encoded) {
-	if (finish_frames(app)) return 1;
-	return assemble_slabs<uint32_t>(app, gathered_slabs, out_encoded ? out_encoded : app->render_targets.encoded, (hipStream_t) app->device.stream);
-}
-
-// slabs of packed RGB8 (encode_slab_rgb8) -> RGBA8 frame; alpha of the encoded output is always
-// 255.  A thread moves four pixels of one tile row: twelve bytes = three aligned dwords in
-// (tile sizes are multiples of four), four pixels out.
-__global__ void __launch_bounds__(256) k_assemble_frame_rgb8(const uint32_t* slabs, uint32_t* frame, uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tiles_x, uint32_t rank_count, uint64_t slab_stride) {
-	uint32_t px = 4u * (blockIdx.x * 64u + (threadIdx.x & 63u)), py = blockIdx.y * 4u + (threadIdx.x >> 6);
-	if (px >= width || py >= height) return;
-	uint32_t tx = px / tile_size, ty = py / tile_size;
-	uint32_t tile = ty * tiles_x + tx;
-	uint32_t rank = tile % rank_count, local_tile = tile / rank_count;
-	uint32_t ix = px - tx * tile_size, iy = py - ty * tile_size;
-	size_t pixel = rank * slab_stride + (size_t) local_tile * tile_size * tile_size + (size_t) iy * tile_size + ix;
-	const uint32_t* source = slabs + 3 * (pixel / 4);
-	uint32_t d0 = source[0], d1 = source[1], d2 = source[2];
-	uint32_t out[4] = {d0 | 0xFF000000u, (d0 >> 24) | (d1 << 8) | 0xFF000000u, (d1 >> 16) | (d2 << 16) | 0xFF000000u, (d2 >> 8) | 0xFF000000u};
-	uint32_t* target = frame + (size_t) py * width + px;
-	for (uint32_t i = 0; i != 4 && px + i < width; ++i) target[i] = out[i];
-}
-
-static int assemble_rgb8_slabs(application_t* app, const void* gathered_slabs, void* out_encoded, hipStream_t stream) {
-	shade_params p;
-	uint64_t slab_stride = slab_tiling(app, 0, p);
-	if (p.tile_size % 4 != 0) {
-		printf("assemble_rgb8_frame_from_slabs() needs a tile size that is a multiple of four.\n");
-		return 1;
-	}
-	dim3 grid((p.width + 255) / 256, (p.height + 3) / 4);
-	k_assemble_frame_rgb8<<<grid, 256, 0, stream>>>((const uint32_t*) gathered_slabs, (uint32_t*) (out_encoded ? out_encoded : app->render_targets.encoded),
-		p.width, p.height, p.tile_size, p.tiles_x, p.rank_count, slab_stride);
-	return hip_failed(hipGetLastError(), "assembling the frame");
-}
-
-extern "C" int assemble_rgb8_frame_from_slabs(application_t* app, const void* gathered_slabs, void* out_encoded) {
-	if (finish_frames(app)) return 1;
-	return assemble_rgb8_slabs(app, gathered_slabs, out_encoded, (hipStream_t) app->device.stream);
-}
-
-// For host/slab_exchange.c: the scatter of gathered slabs on a stream of the caller's choice
-// (the exchange stream, so that it does not wait for later frames), format as slab_format_t
-extern "C" int vkr_assemble_slabs_on_stream(application_t* app, const void* gathered_slabs, void* out_frame, int format, void* stream) {
-	if (format == 0) return assemble_slabs<float4>(app, gathered_slabs, out_frame ? out_frame : app->render_targets.radiance, (hipStream_t) stream);
-	return assemble_rgb8_slabs(app, gathered_slabs, out_frame, (hipStream_t) stream);
-}
-
-// ---- output encoding (shading_pass.frag.glsl:871-892, srgb_utility.glsl) --------------
-
-__device__ __forceinline__ float linear_to_srgb(float v) {
-	v = gclamp(v, 0.0f, 1.0f);
-	return (v <= 0.0031308f) ? (12.92f * v) : (1.055f * powf(v, 1.0f / 2.4f) - 0.055f);
-}
-__device__ __forceinline__ float srgb_to_linear(float v) {
-	v = gclamp(v, 0.0f, 1.0f);
-	return (v <= 0.04045f) ? ((1.0f / 12.92f) * v) : powf(fmaf(v, 1.0f / 1.055f, 0.055f / 1.055f), 2.4f);
-}
-__device__ __forceinline__ uint32_t to_unorm8(float v) {
-	v = gclamp(v, 0.0f, 1.0f);
-	return (uint32_t) (v * 255.0f + 0.5f);
-}
-
-// to_unorm8(linear_to_srgb(v)) without the pow: the code is the number of starts T[c], c = 1 ... 255, that v has
-// reached, where T[c] is the first float whose code is c in the oracle's float arithmetic (oracle_srgb8_code_starts:
-// gm_powf, no contraction, a code that never decreases over [0, 1]).  The starts lie up to 4 ulps away from the
-// exact thresholds srgb_to_linear((c - 0.5) / 255), on either side, at 171 of the 255 codes.  A hardware log2 / exp2
-// estimate is off by less than one code; the two neighbouring starts settle it.
-// (Three powf per pixel made the encode kernel as expensive as tracing config 2's shadow rays.)
-__device__ float g_srgb_code_thresholds[257];
-
-// the oracle's to_unorm8(linear_to_srgb(v)) for v in [0, 1], operation for operation (this file: -ffp-contract=off)
-__device__ uint32_t srgb_code_by_powf(float v) {
-	float s = (v <= 0.0031308f) ? (12.92f * v) : (1.055f * gm_powf(v, 1.0f / 2.4f) - 0.055f);
-	s = gclamp(s, 0.0f, 1.0f);
-	return (uint32_t) (s * 255.0f + 0.5f);
-}
-
-// thread c bisects the float bit patterns of [0, 1] for the start of code c (30 steps of one powf)
-__global__ void k_fill_srgb_code_thresholds() {
-	uint32_t c = threadIdx.x;
-	uint32_t below = 0u, start = 0x3F800000u;  // code(below) < c <= code(start)
-	while (c != 0 && start - below > 1u) {
-		uint32_t middle = below + (start - below) / 2u;
-		if (srgb_code_by_powf(__uint_as_float(middle)) >= c) start = middle;
-		else below = middle;
-	}
-	g_srgb_code_thresholds[c] = (c == 0) ? 0.0f : __uint_as_float(start);
-	if (c == 0) g_srgb_code_thresholds[256] = __builtin_inff();
-}
-
-// Called by create_hip_device() with the device selected: fills the table on THAT device and waits, so that
-// every stream of every thread that later encodes on the device finds it (the table is per device and its
-// content does not depend on who fills it: no host-side state, filling it again is harmless).
-extern "C" int vkr_fill_device_tables(void* stream) {
-	k_fill_srgb_code_thresholds<<<1, 256, 0, (hipStream_t) stream>>>();
-	if (hip_failed(hipGetLastError(), "filling the sRGB code starts")) return 1;
-	return hip_failed(hipStreamSynchronize((hipStream_t) stream), "filling the sRGB code starts");
-}
-
-__device__ __forceinline__ uint32_t srgb_code(float v) {
-	v = gclamp(v, 0.0f, 1.0f);  // (NaN -> 0 like to_unorm8(linear_to_srgb(NaN)))
-	float estimate = (v <= 0.0031308f) ? (12.92f * v) : fmaf(1.055f, __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(v) * (1.0f / 2.4f)), -0.055f);
-	uint32_t c = (uint32_t) fmaf(gclamp(estimate, 0.0f, 1.0f), 255.0f, 0.5f);
-	c = (v < g_srgb_code_thresholds[c]) ? c - 1u : c;
-	c = (v >= g_srgb_code_thresholds[c + 1u]) ? c + 1u : c;
-	return c;
-}
-
-// packHalf2x16 of one channel.  Which NaN a NaN becomes is left to the implementation by the reference; it is pinned
-// to the oracle's sign | 0x7E00 here (v_cvt_f16_f32 keeps the payload's upper bits).
-__device__ __forceinline__ uint32_t half_bits(float x) {
-	uint32_t h = __half_as_ushort(__float2half_rn(x));
-	return (x != x) ? (((__float_as_uint(x) >> 16) & 0x8000u) | 0x7E00u) : h;
-}
-
-__device__ __forceinline__ uint32_t encode_pixel(float4 c, uint32_t frame_bits, int output_linear_rgb) {
-	uint32_t r, g, b, a;
-	if (frame_bits == 0) {
-		// an *_SRGB target encodes in hardware, any other gets the transfer function in the shader
-		r = srgb_code(c.x); g = srgb_code(c.y); b = srgb_code(c.z);
-		a = to_unorm8(c.w);
-	}
-	else {
-		uint32_t mask = (frame_bits == 1) ? 0xFF : 0xFF00, shift = (frame_bits == 1) ? 0 : 8;
-		uint32_t h0 = half_bits(c.x) | (half_bits(c.y) << 16);
-		uint32_t h1 = half_bits(c.z);
-		float v[3] = {
-			(float) ((h0 & mask) >> shift) * (1.0f / 255.0f),
-			(float) ((((h0 & 0xFFFF0000u) >> 16) & mask) >> shift) * (1.0f / 255.0f),
-			(float) ((h1 & mask) >> shift) * (1.0f / 255.0f)};
-		uint32_t out[3];
-		for (int j = 0; j != 3; ++j) out[j] = to_unorm8(output_linear_rgb ? linear_to_srgb(srgb_to_linear(v[j])) : v[j]);
-		r = out[0]; g = out[1]; b = out[2];
-		a = 255;
-	}
-	return r | (g << 8) | (b << 16) | (a << 24);
-}
-
-__global__ void __launch_bounds__(256) k_encode_output(const float4* radiance, uint32_t* encoded, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb) {
-	uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= pixel_count) return;
-	encoded[i] = encode_pixel(radiance[i], frame_bits, output_linear_rgb);
-}
-
-// four pixels per thread: twelve bytes of packed RGB as three dwords
-__global__ void __launch_bounds__(256) k_encode_output_rgb8(const float4* radiance, uint32_t* packed, uint64_t quad_count, uint32_t frame_bits, int output_linear_rgb) {
-	uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= quad_count) return;
-	uint32_t p0 = encode_pixel(radiance[4 * i], frame_bits, output_linear_rgb) & 0xFFFFFFu, p1 = encode_pixel(radiance[4 * i + 1], frame_bits, output_linear_rgb) & 0xFFFFFFu;
-	uint32_t p2 = encode_pixel(radiance[4 * i + 2], frame_bits, output_linear_rgb) & 0xFFFFFFu, p3 = encode_pixel(radiance[4 * i + 3], frame_bits, output_linear_rgb) & 0xFFFFFFu;
-	packed[3 * i] = p0 | (p1 << 24);
-	packed[3 * i + 1] = (p1 >> 8) | (p2 << 16);
-	packed[3 * i + 2] = (p2 >> 16) | (p3 << 8);
-}
-
-static void launch_encode(const void* radiance, void* encoded, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream) {
-	k_encode_output<<<(uint32_t) ((pixel_count + 255) / 256), 256, 0, stream>>>((const float4*) radiance, (uint32_t*) encoded, pixel_count, frame_bits, output_linear_rgb);
-}
-
-// (pixel_count: a multiple of four)
-static void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream) {
-	k_encode_output_rgb8<<<(uint32_t) ((pixel_count / 4 + 255) / 256), 256, 0, stream>>>((const float4*) radiance, (uint32_t*) packed, pixel_count / 4, frame_bits, output_linear_rgb);
-}
-
-extern "C" int encode_output(application_t* app, VkBool32 output_linear_rgb) {
-	if (finish_frames(app)) return 1;
-	uint64_t pixels = (uint64_t) app->swapchain.extent.width * app->swapchain.extent.height;
-	if (!app->render_targets.radiance || !app->render_targets.encoded) return 1;
-	launch_encode(app->render_targets.radiance, app->render_targets.encoded, pixels, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0, (hipStream_t) app->device.stream);
-	note_target_reader(app);
-	return hip_failed(hipGetLastError(), "encoding the output");
-}
-
-extern "C" int encode_slab(application_t* app, const void* slab_radiance, void* slab_encoded, uint64_t pixel_count, VkBool32 output_linear_rgb) {
-	if (finish_frames(app)) return 1;
-	if (!slab_radiance || !slab_encoded) return 1;
-	launch_encode(slab_radiance, slab_encoded, pixel_count, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0, (hipStream_t) app->device.stream);
-	note_target_reader(app);
-	return hip_failed(hipGetLastError(), "encoding the slab");
-}
-
-extern "C" int encode_slab_rgb8(application_t* app, const void* slab_radiance, void* slab_rgb8, uint64_t pixel_count, VkBool32 output_linear_rgb) {
-	if (finish_frames(app)) return 1;
-	if (!slab_radiance || !slab_rgb8 || pixel_count % 4 != 0) {
-		printf("encode_slab_rgb8() needs buffers and a pixel count that is a multiple of four (slabs are).\n");
-		return 1;
-	}
-	launch_encode_rgb8(slab_radiance, slab_rgb8, pixel_count, app->screenshot.frame_bits, output_linear_rgb ? 1 : 0, (hipStream_t) app->device.stream);
-	note_target_reader(app);
-	return hip_failed(hipGetLastError(), "encoding the slab");
-}
-
-// ---- primary visibility ------------------------------------------------------------
-
-__global__ void __launch_bounds__(256) k_primary_visibility(const uint8_t* constants, bvh_view bvh, uint32_t* visibility, uint32_t width, uint32_t height, float near, float far) {
-	uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	uint32_t px = blockIdx.x * 16 + ((wave & 1) << 3) + (lane & 7);
-	uint32_t py = blockIdx.y * 16 + ((wave >> 1) << 3) + (lane >> 3);
-	if (px >= width || py >= height) return;
-	float fx = (float) px, fy = (float) py;
-	f3 ray = mk3(
-		(load_f(constants, 96) * fx + load_f(constants, 100) * fy) + load_f(constants, 104),
-		(load_f(constants, 112) * fx + load_f(constants, 116) * fy) + load_f(constants, 120),
-		(load_f(constants, 128) * fx + load_f(constants, 132) * fy) + load_f(constants, 136));
-	f3 origin = load_f3(constants, 144);
-	// The unnormalised ray direction has view-space depth 1 (it is the unprojection of
-	// clip-space w = 1), so the depth range [near, far] is the parameter range.
-	visibility[(size_t) py * width + px] = closest_front_hit(bvh, origin, ray, near, far);
-}
-
-extern "C" int render_visibility_pass(application_t* app) {
-	// frames in flight read the visibility buffer that this pass overwrites
-	if (finish_frames(app)) return 1;
-	mark_inputs_changed(app);
-	shading_pass_t* pass = &app->shading_pass;
-	const acceleration_structure_t* as = &app->scene.acceleration_structure;
-	if (!as->triangle_vertices || !pass->constants_device) {
-		printf("The visibility pass needs an acceleration structure and a shading pass.\n");
-		return 1;
-	}
-	if (upload_constants(app, (hipStream_t) app->device.stream)) return 1;
-	bvh_view bvh = make_bvh_view(as);
-	uint32_t width = app->swapchain.extent.width, height = app->swapchain.extent.height;
-	dim3 grid((width + 15) / 16, (height + 15) / 16);
-	k_primary_visibility<<<grid, 256, 0, (hipStream_t) app->device.stream>>>((const uint8_t*) pass->constants_device, bvh, (uint32_t*) app->render_targets.visibility_buffer,
-		width, height, app->scene_specification.camera.near, app->scene_specification.camera.far);
-	return hip_failed(hipGetLastError(), "rendering the visibility pass");
-}
-
-// ---- transfers -------------------------------------------------------------------
-
-extern "C" int read_back_radiance(application_t* app, float* host_rgba) {
-	if (finish_frames(app)) return 1;
-	size_t pixels = (size_t) app->swapchain.extent.width * app->swapchain.extent.height;
-	return vkr_copy_to_host(host_rgba, app->render_targets.radiance, sizeof(float) * 4 * pixels, &app->device);
-}
-extern "C" int read_back_encoded(application_t* app, uint8_t* host_rgba8) {
-	if (finish_frames(app)) return 1;
-	size_t pixels = (size_t) app->swapchain.extent.width * app->swapchain.extent.height;
-	return vkr_copy_to_host(host_rgba8, app->render_targets.encoded, 4 * pixels, &app->device);
-}
-extern "C" int read_back_visibility(application_t* app, uint32_t* host_primitives) {
-	if (finish_frames(app)) return 1;
-	size_t pixels = (size_t) app->swapchain.extent.width * app->swapchain.extent.height;
-	return vkr_copy_to_host(host_primitives, app->render_targets.visibility_buffer, sizeof(uint32_t) * pixels, &app->device);
-}
-extern "C" int upload_visibility(application_t* app, const uint32_t* host_primitives) {
-	// a blocking copy outside the streams: nothing may still be reading the old buffer
-	if (wait_for_device(&app->device)) return 1;
-	mark_inputs_changed(app);
-	size_t pixels = (size_t) app->swapchain.extent.width * app->swapchain.extent.height;
-	if (hip_failed(hipMemcpy(app->render_targets.visibility_buffer, host_primitives, sizeof(uint32_t) * pixels, hipMemcpyHostToDevice), "uploading the visibility buffer")) return 1;
-	return 0;
 }

@@ -3,6 +3,7 @@
 // translation units compile in parallel; the libm- and exact-mode units are compiled with
 // -ffp-contract=off, the fast-mode units with -ffp-contract=fast.
 #include "shading_kernel.h"
+#include "shade_launchers.h"  // (the declaration that the callers of VKR_LAUNCH_NAME see)
 
 #ifndef VKR_STRATEGY
 #error "define VKR_STRATEGY (0..4)"
