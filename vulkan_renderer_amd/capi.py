@@ -196,6 +196,12 @@ class FrameStatistics(C.Structure):
                 ("next_event", C.c_uint32), ("pending", C.c_uint32)]
 
 
+class ConvertedTexture(C.Structure):
+    _fields_ = [("format", C.c_int32), ("mipmap_count", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("payload_size", C.c_uint64), ("mipmap_sizes", C.c_uint64 * 32), ("mipmap_offsets", C.c_uint64 * 32),
+                ("payload", C.POINTER(C.c_uint8))]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -310,6 +316,12 @@ SIGNATURES = {
     "read_back_frame_statistics": (C.c_int, [P(FrameStatistics), P(Application), C.c_void_p, C.c_void_p]),
     "sum_squared_differences": (C.c_int, [P(Application), C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_double)]),
     "sum_frame": (C.c_int, [P(Application), C.c_void_p, C.c_uint64, P(C.c_double)]),
+    "convert_texture": (C.c_int, [P(ConvertedTexture), P(Device), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32]),
+    "write_converted_texture": (C.c_int, [P(ConvertedTexture), C.c_char_p]),
+    "free_converted_texture": (None, [P(ConvertedTexture)]),
+    "evaluate_texture_conversion_powf": (None, [P(C.c_float), P(C.c_float), C.c_float, C.c_uint64]),
+    "get_texture_conversion_tables": (None, [P(C.c_float)]),
+    "get_texture_filter_weights": (C.c_uint32, [P(C.c_float), C.c_uint32, C.c_uint32]),
 }
 
 _lib = None

@@ -52,6 +52,9 @@ void vkr_decode_bc5_block(const uint8_t block[16], uint8_t out_rgba[64]);
 /*! scene.c: the sRGB -> linear table of the texture samplers (identical to oracle_srgb_table) */
 void vkr_fill_srgb_table(float table[256]);
 
+/*! texture_conversion.c: the highest level convert_texture() filters (extents up to 4096) */
+#define VKR_TEXTURE_CONVERSION_MAX_LEVEL 12
+
 /*! 4x4 inverse with the operation order of reference math_utilities.h:24-47 */
 void vkr_matrix_inverse(float inverse[4][4], const float matrix[4][4]);
 /*! reference math_utilities.h:50-57 */

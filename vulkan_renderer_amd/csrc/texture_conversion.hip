@@ -1,0 +1,522 @@
+// Images converted to *.vkt textures on the device (include/vkr_texture_conversion.h convert_texture): the Gaussian mip
+// chain of reference tools/texture_conversion/main.c:297-345, one lane per texel channel, the quantisation to 8 bits,
+// halves and floats, one lane per texel, and the BC1 and BC4 block encoders, one lane per block.  Compiled without
+// contraction like noise_generators.hip; every payload is restated in numpy byte for byte
+// (vulkan_renderer_amd/texture_conversion.py).
+#include "vkr_texture_conversion.h"
+#include "host/vkr_internal.h"
+#include <hip/hip_runtime.h>
+#include "glibc_math.h"
+
+static int hip_failed(hipError_t error, const char* what) {
+	if (error == hipSuccess) return 0;
+	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
+	return 1;
+}
+
+constexpr uint32_t kBlock = 64;
+
+static inline uint32_t block_count(uint64_t lanes) { return (uint32_t) ((lanes + kBlock - 1) / kBlock); }
+
+// ---- linear image and mip chain --------------------------------------------------------------------------------------
+
+struct linearise_args {
+	// pixels as uploaded (uint8_t, or float for the float formats) with source_channels per texel
+	const void* source;
+	// the tables of get_texture_conversion_tables()
+	const float* tables;
+	float* linear;
+	uint64_t lane_count;
+	uint32_t source_channels, channels;
+	// float pixels pass through; colour channels of sRGB formats take the first table, everything else the second
+	uint32_t source_is_float, srgb;
+};
+
+// One lane per texel channel of the linear level 0
+__global__ void __launch_bounds__(kBlock) k_linearise(linearise_args a) {
+	uint64_t g = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+	if (g >= a.lane_count) return;
+	uint64_t texel = g / a.channels;
+	uint32_t l = (uint32_t) (g - texel * a.channels);
+	uint64_t index = texel * a.source_channels + l;
+	if (a.source_is_float) a.linear[g] = ((const float*) a.source)[index];
+	else a.linear[g] = a.tables[((a.srgb && l < 3) ? 0u : 256u) + ((const uint8_t*) a.source)[index]];
+}
+
+struct filter_args {
+	const float* linear;
+	// 2 * extent normalised weights of this level
+	const float* weights;
+	float* level;
+	uint32_t lane_count;
+	uint32_t width, height, channels;
+	// stride = 1 << shift; the level is (width >> shift) x (height >> shift), log2_level_width the logarithm of the former
+	uint32_t shift, log2_level_width, extent;
+};
+
+// One lane per texel channel of one level.  The chain of additions is the reference's (main.c:330-341), k outer and j
+// inner, from +0.0f: it cannot be split among lanes without changing bytes.  The weights are read from LDS (all lanes
+// the same address), the source through the cache.
+__global__ void __launch_bounds__(kBlock) k_filter_level(filter_args a) {
+	extern __shared__ __align__(16) float weights[];
+	const uint32_t taps = 2 * a.extent;
+	for (uint32_t j = threadIdx.x; j < taps; j += kBlock) weights[j] = a.weights[j];
+	__syncthreads();
+	uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+	if (g >= a.lane_count) return;
+	uint32_t texel = g / a.channels, l = g - texel * a.channels;
+	uint32_t x = texel & ((1u << a.log2_level_width) - 1u), y = texel >> a.log2_level_width;
+	uint32_t stride = 1u << a.shift, mask_x = a.width - 1u, mask_y = a.height - 1u;
+	// (two's complement: the mask makes the wrapped coordinate of a negative start)
+	uint32_t start_x = x * stride + stride / 2 - a.extent, start_y = y * stride + stride / 2 - a.extent;
+	float sum = 0.0f;
+	for (uint32_t k = 0; k != taps; ++k) {
+		const float* row = a.linear + (size_t) ((start_y + k) & mask_y) * a.width * a.channels + l;
+		float weight_k = weights[k];
+		// eight taps at a time: their loads do not depend on the sum and overlap, the additions keep their order
+		uint32_t j = 0;
+		for (; j + 8 <= taps; j += 8) {
+			float source[8], weight[8];
+#pragma unroll
+			for (uint32_t n = 0; n != 8; ++n) {
+				source[n] = row[(size_t) ((start_x + j + n) & mask_x) * a.channels];
+				weight[n] = weights[j + n];
+			}
+#pragma unroll
+			for (uint32_t n = 0; n != 8; ++n) sum += (weight[n] * weight_k) * source[n];
+		}
+		for (; j != taps; ++j) sum += (weights[j] * weight_k) * row[(size_t) ((start_x + j) & mask_x) * a.channels];
+	}
+	a.level[g] = sum;
+}
+
+// ---- quantisation ------------------------------------------------------------------------------------------------------
+
+// roundf(v * 255.0f), clamped (main.c:78-80)
+__device__ static inline uint32_t quantise_unorm(float v) {
+	float r = roundf(v * 255.0f);
+	return (uint32_t) (r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r));
+}
+
+// (main.c:70-74)
+__device__ static inline uint32_t quantise_srgb(float v) {
+	v = (v < 0.0f) ? 0.0f : v;
+	float s = (v <= 0.0031308f) ? (12.92f * v) : (1.055f * gm_powf(v, 1.0f / 2.4f) - 0.055f);
+	float r = roundf(s * 255.0f);
+	return (uint32_t) (r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r));
+}
+
+// The half rule of the header - the public float_to_half_fast3 of F. Giesen's "float->half variants", which the tool uses
+// too -: round by the first dropped bit, ties away from zero
+__device__ static inline uint32_t to_half(float value) {
+	uint32_t u = __float_as_uint(value);
+	uint32_t sign = u & 0x80000000u;
+	u ^= sign;
+	uint32_t half;
+	if (u >= 0x7F800000u) half = (u > 0x7F800000u) ? 0x7E00u : 0x7C00u;
+	else {
+		u &= ~0xFFFu;
+		u = __float_as_uint(__uint_as_float(u) * __uint_as_float(15u << 23));
+		u += 0x1000u;
+		if (u > (31u << 23)) u = 31u << 23;
+		half = u >> 13;
+	}
+	return half | (sign >> 16);
+}
+
+struct pack_args {
+	// the floats of one level, `channels` per texel
+	const float* level;
+	uint8_t* payload;
+	uint32_t texel_count, channels;
+	int32_t format;
+};
+
+// One lane per texel of one level of the formats without blocks
+__global__ void __launch_bounds__(kBlock) k_pack_level(pack_args a) {
+	uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+	if (g >= a.texel_count) return;
+	const float* texel = a.level + (size_t) g * a.channels;
+	switch (a.format) {
+	case texture_conversion_format_r8g8b8a8_unorm:
+		((uint32_t*) a.payload)[g] = quantise_unorm(texel[0]) | (quantise_unorm(texel[1]) << 8) | (quantise_unorm(texel[2]) << 16) | (quantise_unorm(texel[3]) << 24);
+		break;
+	case texture_conversion_format_r8g8b8a8_srgb:
+		((uint32_t*) a.payload)[g] = quantise_srgb(texel[0]) | (quantise_srgb(texel[1]) << 8) | (quantise_srgb(texel[2]) << 16) | (quantise_unorm(texel[3]) << 24);
+		break;
+	case texture_conversion_format_r16g16b16_sfloat:
+		for (uint32_t l = 0; l != 3; ++l) ((uint16_t*) a.payload)[(size_t) g * 3 + l] = (uint16_t) to_half(texel[l]);
+		break;
+	case texture_conversion_format_r16g16b16a16_sfloat:
+		((uint2*) a.payload)[g] = make_uint2(to_half(texel[0]) | (to_half(texel[1]) << 16), to_half(texel[2]) | (to_half(texel[3]) << 16));
+		break;
+	default:
+		for (uint32_t l = 0; l != a.channels; ++l) ((float*) a.payload)[(size_t) g * a.channels + l] = texel[l];
+		break;
+	}
+}
+
+// ---- BC4 ---------------------------------------------------------------------------------------------------------------
+
+struct encode_args {
+	const float* level;
+	uint8_t* payload;
+	uint32_t lane_count, log2_blocks_x, level_width;
+	uint32_t srgb;
+};
+
+// The palette of decode_bc4_block (host/textures.c)
+__device__ static inline void bc4_palette(uint32_t values[8], uint32_t e0, uint32_t e1) {
+	values[0] = e0; values[1] = e1;
+	if (e0 > e1) {
+#pragma unroll
+		for (uint32_t i = 1; i != 7; ++i) values[i + 1] = ((7 - i) * e0 + i * e1 + 3) / 7;
+	}
+	else {
+#pragma unroll
+		for (uint32_t i = 1; i != 5; ++i) values[i + 1] = ((5 - i) * e0 + i * e1 + 2) / 5;
+		values[6] = 0; values[7] = 255;
+	}
+}
+
+// One lane per block and channel: the sixteen values and the palette stay in registers
+__global__ void __launch_bounds__(kBlock) k_encode_bc4(encode_args a) {
+	uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+	if (g >= a.lane_count) return;
+	uint32_t block = g >> 1, channel = g & 1u;
+	uint32_t bx = block & ((1u << a.log2_blocks_x) - 1u), by = block >> a.log2_blocks_x;
+	int32_t t[16];
+	int32_t low = 255, high = 0;
+#pragma unroll
+	for (uint32_t i = 0; i != 16; ++i) {
+		t[i] = (int32_t) quantise_unorm(a.level[((size_t) (4 * by + (i >> 2)) * a.level_width + 4 * bx + (i & 3u)) * 2 + channel]);
+		low = min(low, t[i]); high = max(high, t[i]);
+	}
+	uint32_t best_error = 0xFFFFFFFFu, best_key = 0;
+	for (int32_t hi = high; hi >= max(low, high - 4); --hi)
+		for (int32_t lo = low; lo <= min(high, low + 4); ++lo)
+			for (uint32_t order = 0; order != 2; ++order) {
+				uint32_t e0 = (uint32_t) (order ? lo : hi), e1 = (uint32_t) (order ? hi : lo);
+				uint32_t values[8];
+				bc4_palette(values, e0, e1);
+				uint32_t error = 0;
+#pragma unroll
+				for (uint32_t i = 0; i != 16; ++i) {
+					uint32_t least = 0xFFFFFFFFu;
+#pragma unroll
+					for (uint32_t p = 0; p != 8; ++p) {
+						int32_t d = t[i] - (int32_t) values[p];
+						least = min(least, (uint32_t) (d * d));
+					}
+					error += least;
+				}
+				uint32_t key = (e0 << 8) | e1;
+				if (error < best_error || (error == best_error && key < best_key)) { best_error = error; best_key = key; }
+			}
+	uint32_t values[8];
+	bc4_palette(values, best_key >> 8, best_key & 255u);
+	uint64_t indices = 0;
+#pragma unroll
+	for (uint32_t i = 0; i != 16; ++i) {
+		uint32_t least = 0xFFFFFFFFu, index = 0;
+#pragma unroll
+		for (uint32_t p = 0; p != 8; ++p) {
+			int32_t d = t[i] - (int32_t) values[p];
+			if ((uint32_t) (d * d) < least) { least = (uint32_t) (d * d); index = p; }
+		}
+		indices |= (uint64_t) index << (3 * i);
+	}
+	uint64_t packed = best_key >> 8 | ((best_key & 255u) << 8) | (indices << 16);
+	((uint2*) a.payload)[g] = make_uint2((uint32_t) packed, (uint32_t) (packed >> 32));
+}
+
+// ---- BC1 ---------------------------------------------------------------------------------------------------------------
+
+struct bc1_texels { int32_t r[16], g[16], b[16]; };
+
+// The state (r0, g0, b0, r1, g1, b1) is packed into 32 bits, component k at bit 5 k + (k >= 2) + (k >= 5)
+__device__ static inline uint32_t bc1_offset(uint32_t k) { return 5 * k + (k >= 2 ? 1u : 0u) + (k >= 5 ? 1u : 0u); }
+__device__ static inline uint32_t bc1_limit(uint32_t k) { return (k == 1 || k == 4) ? 63u : 31u; }
+__device__ static inline uint32_t bc1_state(uint32_t r0, uint32_t g0, uint32_t b0, uint32_t r1, uint32_t g1, uint32_t b1) {
+	return r0 | (g0 << 5) | (b0 << 11) | (r1 << 16) | (g1 << 21) | (b1 << 27);
+}
+// (r << 11) | (g << 5) | b of colour 0 and 1, the larger one in the high half: what the block stores
+__device__ static inline uint32_t bc1_colours(uint32_t e) {
+	uint32_t c0 = ((e & 31u) << 11) | (((e >> 5) & 63u) << 5) | ((e >> 11) & 31u);
+	uint32_t c1 = (((e >> 16) & 31u) << 11) | (((e >> 21) & 63u) << 5) | (e >> 27);
+	return c0 < c1 ? (c1 << 16 | c0) : (c0 << 16 | c1);
+}
+
+// E(e) of the header; INDICES: the index of texel t at bit 2 t as well
+template <bool INDICES> __device__ static inline uint32_t bc1_error(const bc1_texels& t, uint32_t e, uint32_t* indices) {
+	uint32_t c = bc1_colours(e);
+	int32_t p[4][3];
+#pragma unroll
+	for (uint32_t n = 0; n != 2; ++n) {
+		uint32_t colour = n ? (c & 0xFFFFu) : (c >> 16);
+		uint32_t r = colour >> 11, g = (colour >> 5) & 63u, b = colour & 31u;
+		p[n][0] = (int32_t) ((r << 3) | (r >> 2)); p[n][1] = (int32_t) ((g << 2) | (g >> 4)); p[n][2] = (int32_t) ((b << 3) | (b >> 2));
+	}
+#pragma unroll
+	for (uint32_t l = 0; l != 3; ++l) {
+		p[2][l] = (2 * p[0][l] + p[1][l] + 1) / 3;
+		p[3][l] = (p[0][l] + 2 * p[1][l] + 1) / 3;
+	}
+	uint32_t error = 0, packed = 0;
+#pragma unroll
+	for (uint32_t i = 0; i != 16; ++i) {
+		uint32_t least = 0xFFFFFFFFu, index = 0;
+#pragma unroll
+		for (uint32_t n = 0; n != 4; ++n) {
+			int32_t dr = t.r[i] - p[n][0], dg = t.g[i] - p[n][1], db = t.b[i] - p[n][2];
+			uint32_t d = (uint32_t) (dr * dr + dg * dg + db * db);
+			if (d < least) { least = d; index = n; }
+		}
+		error += least;
+		if (INDICES) packed |= index << (2 * i);
+	}
+	if (INDICES) *indices = packed;
+	return error;
+}
+
+__device__ static inline uint32_t bc1_round_5(int32_t v) { return (uint32_t) ((31 * v + 127) / 255); }
+__device__ static inline uint32_t bc1_round_6(int32_t v) { return (uint32_t) ((63 * v + 127) / 255); }
+
+// Shifts every component right until the largest magnitude has at most 10 bits
+__device__ static inline void bc1_normalise(int64_t v[3]) {
+	uint64_t largest = 0;
+#pragma unroll
+	for (uint32_t l = 0; l != 3; ++l) largest = max(largest, (uint64_t) (v[l] < 0 ? -v[l] : v[l]));
+	int32_t bits = largest ? 64 - __clzll((long long) largest) : 0;
+	int32_t shift = bits > 10 ? bits - 10 : 0;
+#pragma unroll
+	for (uint32_t l = 0; l != 3; ++l) v[l] >>= shift;
+}
+
+// Start state B: the texels at the two ends of the principal axis (four power iterations in integers), rounded to nearest
+__device__ static inline uint32_t bc1_principal_axis_state(const bc1_texels& t) {
+	int64_t S[3] = {0, 0, 0}, P[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+	for (uint32_t i = 0; i != 16; ++i) {
+		int64_t c[3] = {t.r[i], t.g[i], t.b[i]};
+#pragma unroll
+		for (uint32_t a = 0; a != 3; ++a) {
+			S[a] += c[a];
+#pragma unroll
+			for (uint32_t b = 0; b != 3; ++b) P[a][b] += c[a] * c[b];
+		}
+	}
+	int64_t C[3][3];
+#pragma unroll
+	for (uint32_t a = 0; a != 3; ++a)
+#pragma unroll
+		for (uint32_t b = 0; b != 3; ++b) C[a][b] = 16 * P[a][b] - S[a] * S[b];
+	bool second = C[1][1] > C[0][0], third = C[2][2] > (second ? C[1][1] : C[0][0]);
+	int64_t v[3];
+#pragma unroll
+	for (uint32_t l = 0; l != 3; ++l) v[l] = third ? C[2][l] : (second ? C[1][l] : C[0][l]);
+	bc1_normalise(v);
+	for (uint32_t iteration = 0; iteration != 4; ++iteration) {
+		int64_t w[3];
+#pragma unroll
+		for (uint32_t a = 0; a != 3; ++a) w[a] = C[a][0] * v[0] + C[a][1] * v[1] + C[a][2] * v[2];
+#pragma unroll
+		for (uint32_t a = 0; a != 3; ++a) v[a] = w[a];
+		bc1_normalise(v);
+	}
+	int32_t axis[3] = {(int32_t) v[0], (int32_t) v[1], (int32_t) v[2]};
+	int32_t most = INT32_MIN, least = INT32_MAX;
+	int32_t top[3] = {0, 0, 0}, bottom[3] = {0, 0, 0};
+#pragma unroll
+	for (uint32_t i = 0; i != 16; ++i) {
+		int32_t d = axis[0] * t.r[i] + axis[1] * t.g[i] + axis[2] * t.b[i];
+		if (d > most) { most = d; top[0] = t.r[i]; top[1] = t.g[i]; top[2] = t.b[i]; }
+		if (d < least) { least = d; bottom[0] = t.r[i]; bottom[1] = t.g[i]; bottom[2] = t.b[i]; }
+	}
+	return bc1_state(bc1_round_5(top[0]), bc1_round_6(top[1]), bc1_round_5(top[2]), bc1_round_5(bottom[0]), bc1_round_6(bottom[1]), bc1_round_5(bottom[2]));
+}
+
+// One lane per block: the 48 texel components stay in registers, the three descents run one after the other
+__global__ void __launch_bounds__(kBlock) k_encode_bc1(encode_args a) {
+	uint32_t block = blockIdx.x * kBlock + threadIdx.x;
+	if (block >= a.lane_count) return;
+	uint32_t bx = block & ((1u << a.log2_blocks_x) - 1u), by = block >> a.log2_blocks_x;
+	bc1_texels t;
+	int32_t most = INT32_MIN, least = INT32_MAX;
+	int32_t low[3] = {255, 255, 255}, high[3] = {0, 0, 0};
+	uint32_t bright = 0, dark = 0;
+#pragma unroll
+	for (uint32_t i = 0; i != 16; ++i) {
+		const float* texel = a.level + ((size_t) (4 * by + (i >> 2)) * a.level_width + 4 * bx + (i & 3u)) * 3;
+		t.r[i] = (int32_t) (a.srgb ? quantise_srgb(texel[0]) : quantise_unorm(texel[0]));
+		t.g[i] = (int32_t) (a.srgb ? quantise_srgb(texel[1]) : quantise_unorm(texel[1]));
+		t.b[i] = (int32_t) (a.srgb ? quantise_srgb(texel[2]) : quantise_unorm(texel[2]));
+		int32_t luminance = 2 * t.r[i] + 5 * t.g[i] + t.b[i];
+		uint32_t truncated = (uint32_t) (t.r[i] >> 3) | ((uint32_t) (t.g[i] >> 2) << 5) | ((uint32_t) (t.b[i] >> 3) << 11);
+		if (luminance > most) { most = luminance; bright = truncated; }
+		if (luminance < least) { least = luminance; dark = truncated; }
+		low[0] = min(low[0], t.r[i]); low[1] = min(low[1], t.g[i]); low[2] = min(low[2], t.b[i]);
+		high[0] = max(high[0], t.r[i]); high[1] = max(high[1], t.g[i]); high[2] = max(high[2], t.b[i]);
+	}
+	uint32_t best_state = 0, best_error = 0xFFFFFFFFu;
+	for (uint32_t candidate = 0; candidate != 3; ++candidate) {
+		uint32_t e;
+		if (candidate == 0) e = bright | (dark << 16);
+		else if (candidate == 1) e = bc1_principal_axis_state(t);
+		else e = bc1_state(bc1_round_5(high[0]), bc1_round_6(high[1]), bc1_round_5(high[2]), bc1_round_5(low[0]), bc1_round_6(low[1]), bc1_round_5(low[2]));
+		uint32_t error = bc1_error<false>(t, e, NULL);
+		for (uint32_t round = 0; round != 32; ++round) {
+			bool accepted = false;
+			for (uint32_t step = 1; step != 3; ++step)
+				for (uint32_t k = 0; k != 6; ++k)
+					for (uint32_t up = 0; up != 2; ++up) {
+						uint32_t offset = bc1_offset(k), limit = bc1_limit(k);
+						uint32_t value = (e >> offset) & limit;
+						if (up ? value + step > limit : value < step) continue;
+						uint32_t trial = (e & ~(limit << offset)) | ((up ? value + step : value - step) << offset);
+						uint32_t trial_error = bc1_error<false>(t, trial, NULL);
+						if (trial_error < error) { e = trial; error = trial_error; accepted = true; }
+					}
+			if (!accepted) break;
+		}
+		if (error < best_error) { best_error = error; best_state = e; }
+	}
+	uint32_t indices;
+	(void) bc1_error<true>(t, best_state, &indices);
+	uint32_t colours = bc1_colours(best_state);
+	((uint2*) a.payload)[block] = make_uint2((colours >> 16) | (colours << 16), indices);
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+
+static int is_power_of_two(uint32_t x) { return x && !(x & (x - 1)); }
+
+static uint32_t log2_of(uint32_t x) {
+	uint32_t l = 0;
+	while ((1u << l) < x) ++l;
+	return l;
+}
+
+extern "C" int convert_texture(converted_texture_t* out, const device_t* device, const void* pixels, uint32_t width, uint32_t height, uint32_t channel_count, int32_t vk_format) {
+	memset(out, 0, sizeof(*out));
+	// (main.c:142-183)
+	uint32_t channels = 0, bits_per_pixel = 0, is_float = 0, is_block = 0, is_srgb = 0;
+	switch (vk_format) {
+	case texture_conversion_format_r8g8b8a8_srgb: is_srgb = 1; // fall through
+	case texture_conversion_format_r8g8b8a8_unorm: channels = 4; bits_per_pixel = 32; break;
+	case texture_conversion_format_r16g16b16_sfloat: channels = 3; bits_per_pixel = 48; is_float = 1; break;
+	case texture_conversion_format_r16g16b16a16_sfloat: channels = 4; bits_per_pixel = 64; is_float = 1; break;
+	case texture_conversion_format_r32g32b32_sfloat: channels = 3; bits_per_pixel = 96; is_float = 1; break;
+	case texture_conversion_format_r32g32b32a32_sfloat: channels = 4; bits_per_pixel = 128; is_float = 1; break;
+	case texture_conversion_format_bc1_rgb_srgb: is_srgb = 1; // fall through
+	case texture_conversion_format_bc1_rgb_unorm: channels = 3; bits_per_pixel = 4; is_block = 1; break;
+	case texture_conversion_format_bc5_unorm: channels = 2; bits_per_pixel = 8; is_block = 1; break;
+	default:
+		printf("convert_texture() writes the formats 37, 43, 90, 97, 106, 109, 131, 132 and 141, not %d.\n", (int) vk_format);
+		return 1;
+	}
+	if (!pixels || channel_count < channels) {
+		printf("The image has %u channels but needs to have at least %u.\n", pixels ? channel_count : 0u, channels);
+		return 1;
+	}
+	if (!is_power_of_two(width) || !is_power_of_two(height) || width > (1u << VKR_TEXTURE_CONVERSION_MAX_LEVEL) || height > (1u << VKR_TEXTURE_CONVERSION_MAX_LEVEL)) {
+		printf("The image has extent %ux%u but it must be a power of two up to %u for both dimensions.\n", width, height, 1u << VKR_TEXTURE_CONVERSION_MAX_LEVEL);
+		return 1;
+	}
+	// (main.c:229-261)
+	uint32_t level_count = (width < height ? log2_of(width) : log2_of(height)) + 1;
+	uint8_t constant_block[16 * 4];
+	size_t source_texel_bytes = (is_float ? sizeof(float) : 1) * (size_t) channel_count;
+	if (is_block) {
+		if (width == 1 && height == 1) {
+			// (block formats take bytes)
+			channel_count = channels;
+			source_texel_bytes = channels;
+			for (uint32_t i = 0; i != 16; ++i) memcpy(constant_block + i * source_texel_bytes, pixels, channels);
+			pixels = constant_block;
+			width = height = 4;
+			level_count = 3;
+		}
+		if (width < 4 || height < 4) {
+			printf("The image has extent %ux%u but it must be at least 4x4 for block compression to work.\n", width, height);
+			return 1;
+		}
+		level_count -= 2;
+	}
+	// (the argument checks come first: they need no device)
+	if (!device) {
+		printf("convert_texture() needs a device: the converter is HIP kernels.\n");
+		return 1;
+	}
+	out->format = vk_format; out->mipmap_count = (int32_t) level_count; out->width = (int32_t) width; out->height = (int32_t) height;
+	// the floats of the levels above 0 follow the linear image in one buffer, the weights of all levels the tables
+	uint64_t level_floats[32], weight_offsets[32], float_count = 0, weight_count = 512;
+	for (uint32_t i = 0; i != level_count; ++i) {
+		uint64_t texels = (uint64_t) (width >> i) * (height >> i);
+		out->mipmap_sizes[i] = texels * bits_per_pixel / 8;
+		out->mipmap_offsets[i] = out->payload_size;
+		out->payload_size += out->mipmap_sizes[i];
+		level_floats[i] = float_count;
+		float_count += texels * channels;
+		weight_offsets[i] = weight_count;
+		weight_count += i ? 2 * get_texture_filter_weights(NULL, 0, i) : 0;
+	}
+	float* parameters_host = (float*) malloc(sizeof(float) * weight_count);
+	out->payload = (uint8_t*) malloc(out->payload_size);
+	void *source = NULL, *parameters = NULL, *floats = NULL, *payload = NULL;
+	size_t source_bytes = source_texel_bytes * width * height;
+	int failed = !parameters_host || !out->payload;
+	if (failed) printf("Out of memory for a texture of %llu bytes.\n", (unsigned long long) out->payload_size);
+	failed = failed || vkr_device_alloc(&source, device, source_bytes, "the source image") || vkr_device_alloc(&parameters, device, sizeof(float) * weight_count, "the filter weights")
+		|| vkr_device_alloc(&floats, device, sizeof(float) * float_count, "the linear mip chain") || vkr_device_alloc(&payload, device, out->payload_size, "the texture payload");
+	hipStream_t stream = (hipStream_t) device->stream;
+	if (!failed) {
+		get_texture_conversion_tables(parameters_host);
+		for (uint32_t i = 1; i != level_count; ++i) get_texture_filter_weights(parameters_host + weight_offsets[i], (uint32_t) (weight_count - weight_offsets[i]), i);
+		failed = vkr_copy_to_device_async(source, pixels, source_bytes, device) || vkr_copy_to_device_async(parameters, parameters_host, sizeof(float) * weight_count, device);
+	}
+	if (!failed) {
+		linearise_args args;
+		args.source = source; args.tables = (const float*) parameters; args.linear = (float*) floats;
+		args.lane_count = (uint64_t) width * height * channels;
+		args.source_channels = channel_count; args.channels = channels; args.source_is_float = is_float; args.srgb = is_srgb;
+		k_linearise<<<block_count(args.lane_count), kBlock, 0, stream>>>(args);
+		failed = hip_failed(hipGetLastError(), "making the linear image");
+	}
+	// the highest levels first: they are a few lanes with the longest chains
+	for (uint32_t i = level_count - 1; i != 0 && !failed; --i) {
+		filter_args args;
+		args.linear = (const float*) floats; args.weights = (const float*) parameters + weight_offsets[i]; args.level = (float*) floats + level_floats[i];
+		args.lane_count = (width >> i) * (height >> i) * channels;
+		args.width = width; args.height = height; args.channels = channels;
+		args.shift = i; args.log2_level_width = log2_of(width >> i); args.extent = get_texture_filter_weights(NULL, 0, i);
+		k_filter_level<<<block_count(args.lane_count), kBlock, sizeof(float) * 2 * args.extent, stream>>>(args);
+		failed = hip_failed(hipGetLastError(), "filtering a mip level");
+	}
+	for (uint32_t i = 0; i != level_count && !failed; ++i) {
+		const float* level = (const float*) floats + level_floats[i];
+		uint8_t* target = (uint8_t*) payload + out->mipmap_offsets[i];
+		uint32_t level_width = width >> i, level_height = height >> i;
+		if (is_block) {
+			encode_args args;
+			args.level = level; args.payload = target;
+			args.lane_count = (level_width / 4) * (level_height / 4) * (channels == 2 ? 2u : 1u);
+			args.log2_blocks_x = log2_of(level_width / 4); args.level_width = level_width; args.srgb = is_srgb;
+			if (channels == 2) k_encode_bc4<<<block_count(args.lane_count), kBlock, 0, stream>>>(args);
+			else k_encode_bc1<<<block_count(args.lane_count), kBlock, 0, stream>>>(args);
+		}
+		else {
+			pack_args args;
+			args.level = level; args.payload = target; args.texel_count = level_width * level_height; args.channels = channels; args.format = vk_format;
+			k_pack_level<<<block_count(args.texel_count), kBlock, 0, stream>>>(args);
+		}
+		failed = hip_failed(hipGetLastError(), "encoding a mip level");
+	}
+	// (the read-back waits for the stream: the kernels and the uploads read the temporaries)
+	if (!failed) failed = vkr_copy_to_host(out->payload, payload, out->payload_size, device);
+	else (void) hipStreamSynchronize(stream);
+	vkr_device_free(source, device); vkr_device_free(parameters, device); vkr_device_free(floats, device); vkr_device_free(payload, device);
+	free(parameters_host);
+	if (failed) free_converted_texture(out);
+	return failed;
+}

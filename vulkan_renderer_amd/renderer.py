@@ -330,6 +330,28 @@ class Renderer(HostScene):
         names = {v: k for k, v in NOISE.items()}
         return os.path.join(data_root or cwd, noise_tables.file_name(names[t], (n.width, n.height, n.depth)))
 
+    def convert_texture(self, image, vk_format, path=None):
+        """Converts an image (height x width x channels; float32 for the formats 90, 97, 106 and 109, uint8 for 37, 43,
+        131, 132 and 141) to a texture on the device (include/vkr_texture_conversion.h convert_texture) and writes it to
+        `path` as *.vkt if one is given.  Returns ([(width, height)], [bytes]) of the levels, largest first.  The call
+        runs on the device's stream behind whatever is queued there; it touches nothing a frame in flight reads."""
+        from . import texture_conversion
+        image = np.ascontiguousarray(image, np.float32 if texture_conversion.takes_float(vk_format) else np.uint8)
+        if image.ndim != 3:
+            raise ValueError("convert_texture takes a height x width x channels array")
+        texture = capi.ConvertedTexture()
+        if self.lib.convert_texture(C.byref(texture), self._dev(), image.ctypes.data, image.shape[1], image.shape[0], image.shape[2], int(vk_format)):
+            raise RuntimeError("convert_texture failed")
+        try:
+            if path is not None and self.lib.write_converted_texture(C.byref(texture), str(path).encode()):
+                raise RuntimeError("write_converted_texture failed for %s" % path)
+            payload = C.string_at(texture.payload, texture.payload_size)
+            extents = [(texture.width >> i, texture.height >> i) for i in range(texture.mipmap_count)]
+            payloads = [payload[texture.mipmap_offsets[i]:texture.mipmap_offsets[i] + texture.mipmap_sizes[i]] for i in range(texture.mipmap_count)]
+        finally:
+            self.lib.free_converted_texture(C.byref(texture))
+        return extents, payloads
+
     def fit_ltc_table(self, resolution=None, fresnel_count=None, sample_count=None, max_iterations=None):
         """Replaces the LTC table by one fitted on the device (include/vkr_ltc_table.h fit_ltc_table); None: the default
         of the setting (32, 51, 32, 200).  The fits stay with the renderer for ltc_fits() and write_ltc_table().  Returns
