@@ -202,6 +202,19 @@ class ConvertedTexture(C.Structure):
                 ("payload", C.POINTER(C.c_uint8))]
 
 
+class SceneExportSource(C.Structure):
+    _fields_ = [("vertex_count", C.c_uint64), ("triangle_count", C.c_uint64), ("material_count", C.c_uint64),
+                ("vertex_positions", c_float_p), ("vertex_normals", c_float_p), ("vertex_indices", C.POINTER(C.c_uint32)),
+                ("corner_tex_coords", c_float_p), ("material_indices", C.POINTER(C.c_uint8)), ("material_names", C.POINTER(C.c_char_p))]
+
+
+class ExportedScene(C.Structure):
+    _fields_ = [("material_count", C.c_uint64), ("triangle_count", C.c_uint64), ("material_names", C.POINTER(C.c_char_p)),
+                ("dequantization_factor", C.c_float * 3), ("dequantization_summand", C.c_float * 3),
+                ("positions", C.POINTER(C.c_uint32)), ("normals_and_tex_coords", C.POINTER(C.c_uint16)),
+                ("material_indices", C.POINTER(C.c_uint8))]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -319,6 +332,10 @@ SIGNATURES = {
     "convert_texture": (C.c_int, [P(ConvertedTexture), P(Device), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32]),
     "write_converted_texture": (C.c_int, [P(ConvertedTexture), C.c_char_p]),
     "free_converted_texture": (None, [P(ConvertedTexture)]),
+    "export_scene": (C.c_int, [P(ExportedScene), P(Device), P(SceneExportSource), C.c_uint32]),
+    "write_exported_scene": (C.c_int, [P(ExportedScene), C.c_char_p]),
+    "free_exported_scene": (None, [P(ExportedScene)]),
+    "get_scene_export_kernel_milliseconds": (C.c_float, []),
     "evaluate_texture_conversion_powf": (None, [P(C.c_float), P(C.c_float), C.c_float, C.c_uint64]),
     "get_texture_conversion_tables": (None, [P(C.c_float)]),
     "get_texture_filter_weights": (C.c_uint32, [P(C.c_float), C.c_uint32, C.c_uint32]),

@@ -55,6 +55,15 @@ void vkr_fill_srgb_table(float table[256]);
 /*! texture_conversion.c: the highest level convert_texture() filters (extents up to 4096) */
 #define VKR_TEXTURE_CONVERSION_MAX_LEVEL 12
 
+/*! scene_export.c, for export_scene() of scene_export.hip (include/vkr_scene_export.h).  factor = scale / (hi - lo) and
+	offset = -lo * factor per axis, both 0 where hi == lo; zeros of lo become +0 */
+struct exported_scene_s;
+struct scene_export_source_s;
+void vkr_scene_export_box_constants(float factor[3], float offset[3], float lo[3], const float hi[3], float scale);
+void vkr_scene_export_dequantization(struct exported_scene_s* scene, const float quantization_factor[3], const float lo[3], const float hi[3]);
+/*! the substituted names and the material count; 1 when out of memory (free_exported_scene() cleans up) */
+int vkr_scene_export_copy_names(struct exported_scene_s* scene, const struct scene_export_source_s* source);
+
 /*! 4x4 inverse with the operation order of reference math_utilities.h:24-47 */
 void vkr_matrix_inverse(float inverse[4][4], const float matrix[4][4]);
 /*! reference math_utilities.h:50-57 */

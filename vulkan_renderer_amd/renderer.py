@@ -352,6 +352,24 @@ class Renderer(HostScene):
             self.lib.free_converted_texture(C.byref(texture))
         return extents, payloads
 
+    def export_scene(self, positions, normals, indices=None, tex_coords=None, material_indices=None, material_names=("no_material_assigned",), sort_triangles=True, path=None):
+        """Exports a triangle mesh to a scene on the device (include/vkr_scene_export.h export_scene) and writes it to
+        `path` as *.vks if one is given.  positions, normals: (V, 3); indices: (T, 3), or None for the triangle list;
+        tex_coords: (T, 3, 2) per corner or None; material_indices: (T,) or None.  Returns the buffers as they are stored
+        in the file, under the names synthetic.write_vks() gives them, and the substituted material names.  The call runs
+        on the device's stream behind whatever is queued there; it touches nothing a frame in flight reads."""
+        from . import scene_export
+        source, keepalive = scene_export.export_source(positions, normals, indices, tex_coords, material_indices, material_names)
+        scene = capi.ExportedScene()
+        if self.lib.export_scene(C.byref(scene), self._dev(), C.byref(source), int(bool(sort_triangles))):
+            raise RuntimeError("export_scene failed")
+        try:
+            if path is not None and self.lib.write_exported_scene(C.byref(scene), str(path).encode()):
+                raise RuntimeError("write_exported_scene failed for %s" % path)
+            return scene_export.exported_buffers(scene)
+        finally:
+            self.lib.free_exported_scene(C.byref(scene))
+
     def fit_ltc_table(self, resolution=None, fresnel_count=None, sample_count=None, max_iterations=None):
         """Replaces the LTC table by one fitted on the device (include/vkr_ltc_table.h fit_ltc_table); None: the default
         of the setting (32, 51, 32, 200).  The fits stay with the renderer for ltc_fits() and write_ltc_table().  Returns
