@@ -57,7 +57,7 @@ typedef struct materials_s {
 	driver (vkCmdBuildAccelerationStructuresKHR, scene.c:254-262, PREFER_FAST_TRACE). */
 typedef enum acceleration_structure_builder_e {
 	acceleration_structure_none = 0,
-	/*! binned surface-area heuristic, built breadth-first by HIP kernels (lbvh_build.hip); the
+	/*! binned surface-area heuristic, built breadth-first by HIP kernels (bvh_build.hip); the
 		default (VK_TRUE) and the counterpart of PREFER_FAST_TRACE */
 	acceleration_structure_sah_device = 1,
 	/*! Morton-code LBVH by HIP kernels: the counterpart of PREFER_FAST_BUILD (more node visits per ray) */
@@ -95,7 +95,7 @@ typedef struct acceleration_structure_s {
 	uint32_t builder;
 	float build_milliseconds;
 	/*! Leaves of the tree: the triangle count, or more when the device SAH builder has split long thin triangles
-		that lie diagonally in their boxes into several leaves (each names the whole triangle; lbvh_build.hip
+		that lie diagonally in their boxes into several leaves (each names the whole triangle; bvh_build.hip
 		"fragments"; environment VKR_BVH_SPLIT_TRIANGLES=0 turns it off).  node_count = 2 leaf_count - 1. */
 	uint32_t leaf_count;
 	/*! which build of the process this is (1, 2, ...): two structures with the same serial are the same tree, even when a

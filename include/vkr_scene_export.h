@@ -59,7 +59,7 @@ typedef struct exported_scene_s {
    Sort (:459-469, 49-77; sort_triangles != 0).  The centroid is c = ((p0 + p1) + p2) / 3.0f per axis, clo and chi are the
    extremes of the centroids, f = 1024.0f / (chi - clo), g = trunc(min(max(c * f + (-clo * f), 0.0f), 1023.0f)), and
    code = spread(g.x) | spread(g.y) << 1 | spread(g.z) << 2, where spread() puts two zero bits between any two of the low
-   ten bits: x is the LOWEST bit (the BVH builder csrc/lbvh_build.hip and synthetic.write_vks have it the other way
+   ten bits: x is the LOWEST bit (the BVH builder csrc/bvh_build.hip and synthetic.write_vks have it the other way
    round).  Triangles are stored in ascending order of the code, and triangles of equal code keep their input order.
    (This is the project's rule: the add-on calls an unstable argsort, so its order among equal codes depends on the numpy
    build.)  Corners, texture coordinates and material indices move with their triangle.

@@ -106,7 +106,7 @@ def test_device_sah_tree_is_as_good_as_the_host_tree_and_wide_visits_are_few(big
 
 def test_triangles_in_a_random_order_give_a_tree_of_the_same_quality_and_the_oracle_frame(tmp_path):
     """The device build combines the contributions of a workgroup's 256 consecutive triangles in LDS before
-    its device-scope atomics - a 16-slot table keyed by the open node (csrc/lbvh_build.hip).  With the
+    its device-scope atomics - a 16-slot table keyed by the open node (csrc/bvh_build.hip).  With the
     triangles along a Morton curve, as the datasets store them, a workgroup meets a handful of nodes; in a
     random order it meets more than sixteen from the first levels on, and most triangles take the direct
     path.  Counts add up and bounds are minima / maxima either way: the tree has to be as good, the walk

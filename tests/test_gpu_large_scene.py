@@ -160,7 +160,7 @@ def test_primary_visibility_of_the_benchmark_scene_equals_the_oracle_at_baseline
 
 def test_long_thin_triangles_are_split_into_several_leaves_and_nothing_else_changes(large_dataset, large_oracle, big_dataset, monkeypatch):
     """The device SAH builder cuts triangles that lie diagonally in their boxes (the slats and bars of this scene) into
-    up to 16 leaves with the exact bounds of the triangle inside each slab (csrc/lbvh_build.hip "fragments"): more leaves
+    up to 16 leaves with the exact bounds of the triangle inside each slab (csrc/bvh_build.hip "fragments"): more leaves
     than triangles here, none on the benchmark scene, the same frame and the same visibility buffer either way, and far
     fewer triangle tests per ray."""
     def build(dataset, split):

@@ -18,10 +18,6 @@ using namespace vkr;
 
 namespace {
 
-#define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
-// inside a do { } while (0) that cleans up behind itself
-#define HIP_OK_BREAK(call) if ((call) != hipSuccess) break
-
 struct build_params {
 	const uint2* quantized_positions;
 	// primitives of the build: triangles, or - device SAH with split triangles - fragments of triangles
@@ -787,185 +783,184 @@ __global__ void __launch_bounds__(64) k_publish_counters(uint32_t* counters, uin
 
 }  // namespace
 
-// Replaces structure->nodes (fp32 threaded nodes on the device) by the quantised nodes
-static int quantize_nodes(acceleration_structure_t* structure, const device_t* device) {
-	hipStream_t stream = (hipStream_t) device->stream;
-	float root[8];
-	if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(root, structure->nodes, sizeof(root), hipMemcpyDeviceToHost) != hipSuccess) return 1;
-	const float lo[3] = {root[0], root[1], root[2]}, hi[3] = {root[3], root[4], root[5]};
+// ---- host ---------------------------------------------------------------------------------------
+// The phases of vkr_build_acceleration_structure() in the order it runs them.  Each returns 0 on success, frees the
+// temporaries it allocated on every way out and queues its kernels on device->stream.
+
+static struct timespec now() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t; }
+static double milliseconds(const struct timespec& a, const struct timespec& b) { return (double) (b.tv_sec - a.tv_sec) * 1.0e3 + (double) (b.tv_nsec - a.tv_nsec) * 1.0e-6; }
+
+// What the kernels need of the mesh.  *out_extent: the largest coordinate magnitude and extent of the quantisation grid
+static build_params make_build_params(const mesh_t* mesh, float* out_extent) {
+	build_params p;
+	p.quantized_positions = (const uint2*) mesh->positions;
+	p.triangle_count = (uint32_t) mesh->triangle_count;
+	p.fragment_triangle = NULL;
+	p.fragment_boxes = NULL;
+	float extent = 0.0f;
 	for (int j = 0; j != 3; ++j) {
-		// one spare cell on either side keeps every box strictly inside [0, kGridMax]
-		float extent = fmaxf(hi[j] - lo[j], 1.0e-20f);
-		float cell = extent / (kGridMax - 2.0f);
-		structure->grid_origin[j] = lo[j] - cell;
-		structure->grid_inverse_cell[j] = 1.0f / cell;
+		p.factor[j] = mesh->dequantization_factor[j];
+		p.summand[j] = mesh->dequantization_summand[j];
+		extent = fmaxf(extent, 2097152.0f * fabsf(mesh->dequantization_factor[j]));
+		extent = fmaxf(extent, fmaxf(fabsf(mesh->dequantization_summand[j]), fabsf(mesh->dequantization_summand[j] + 2097152.0f * mesh->dequantization_factor[j])));
 	}
-	void* quantized = NULL;
-	if (hipMalloc(&quantized, sizeof(uint4) * (size_t) structure->node_count) != hipSuccess) return 1;
-	k_quantize_nodes<<<(structure->node_count + 255) / 256, 256, 0, stream>>>(structure->node_count, (const float4*) structure->nodes,
-		f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]},
-		f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]}, (uint4*) quantized);
-	if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) { (void) hipFree(quantized); return 1; }
-	(void) hipFree(structure->nodes);
-	structure->nodes = quantized;
-	return 0;
+	// Conservative padding.  The slab test evaluates plane * (1/d) - o * (1/d) with a
+	// 1-ulp reciprocal and two roundings, i.e. it misplaces a plane by about
+	// |o| 2^-23; the triangle test may accept hits about as far outside the triangle.
+	// 2e-6 of the largest coordinate is sixteen times that.  (The padding must stay
+	// far below t_min = 1e-3: a ray leaving a flat floor would otherwise start inside
+	// the padded boxes of the floor and walk down to its own triangle.)
+	p.pad = 2.0e-6f * extent;
+	*out_extent = extent;
+	return p;
 }
 
-static __global__ void k_empty() {}
-extern "C" int vkr_launch_empty_kernel(void* stream) {
-	k_empty<<<1, 64, 0, (hipStream_t) stream>>>();
-	return hipGetLastError() != hipSuccess;
-}
-
-extern "C" void vkr_destroy_acceleration_structure(acceleration_structure_t* structure, const device_t* device) {
-	(void) device;
-	if (structure->triangle_vertices) (void) hipFree(structure->triangle_vertices);
-	if (structure->nodes) (void) hipFree(structure->nodes);
-	if (structure->wide_nodes) (void) hipFree(structure->wide_nodes);
-	memset(structure, 0, sizeof(*structure));
-}
-
-// Binary quantised nodes -> four-wide nodes, one level per launch (a level's node count is only
-// known when the level before it has been written).  Leaves structure->wide_nodes NULL (the
-// kernels then walk the binary tree) if the tree is a single leaf or a ray could need a deeper
-// stack than the kernels provide.
-static int collapse_to_wide(acceleration_structure_t* structure, const device_t* device, uint32_t* host_words) {
-	uint32_t triangle_count = (structure->node_count + 1) / 2;
-	if (triangle_count < 2) return 0;
+// Device SAH: long thin triangles that lie diagonally in their boxes become several primitives ("fragments" above;
+// VKR_BVH_SPLIT_TRIANGLES=0 builds over whole triangles as until round 3).  Returns the device memory that p then
+// points into, for the caller to free behind the build, or NULL with p as it was: nothing to split, splitting turned
+// off, or it failed - which costs a message and tree quality, not the build.
+static void* split_long_triangles(build_params& p, const device_t* device, int builder, float extent, bool trace) {
+	const char* knob = getenv("VKR_BVH_SPLIT_TRIANGLES");
+	const uint32_t n = p.triangle_count;
+	// (a triangle becomes at most 16 fragments: up to 2^31 / 16 triangles the 32-bit prefix sum of the counts cannot wrap;
+	// beyond that the mesh is built unsplit)
+	if (builder != (int) acceleration_structure_sah_device || n <= 1 || n > 0x7FFFFFFFu / 16u || (knob && knob[0] == '0')) return NULL;
 	hipStream_t stream = (hipStream_t) device->stream;
-	wide_item* items[2] = {NULL, NULL};
-	uint32_t* counters = NULL;
-	uint8_t* arena = NULL;
-	uint4* wide = NULL;
-	int failed = 1;
-	uint32_t host_counters[3] = {0, 1, 0};
-	const size_t item_bytes = (sizeof(wide_item) * (size_t) triangle_count + 255) & ~(size_t) 255;
-	do {
-		HIP_OK_BREAK(hipMalloc(&arena, 2 * item_bytes + 256));
-		items[0] = (wide_item*) arena;
-		items[1] = (wide_item*) (arena + item_bytes);
-		counters = (uint32_t*) (arena + 2 * item_bytes);
-		HIP_OK_BREAK(hipMalloc(&wide, sizeof(uint4) * 4 * (size_t) (triangle_count - 1)));
-		wide_item root = {0u, 0u, 0u};
-		HIP_OK_BREAK(hipMemcpyAsync(items[0], &root, sizeof(root), hipMemcpyHostToDevice, stream));
-		HIP_OK_BREAK(hipMemcpyAsync(counters, host_counters, sizeof(host_counters), hipMemcpyHostToDevice, stream));
-		uint32_t item_count = 1, level = 0;
-		bool ok = true;
-		while (item_count && ok) {
-			k_collapse_level<<<(item_count + 63) / 64, 64, 0, stream>>>((const uint4*) structure->nodes, items[level & 1], item_count, items[(level + 1) & 1], counters, wide);
-			k_publish_counters<<<1, 64, 0, stream>>>(counters, 3u, host_words);
-			ok = hipStreamSynchronize(stream) == hipSuccess && ++level < 4096;
-			for (int i = 0; i != 3; ++i) host_counters[i] = ((volatile uint32_t*) host_words)[i];
-			item_count = host_counters[0];
-		}
-		if (!ok || hipGetLastError() != hipSuccess) break;
-		failed = 0;
-	} while (0);
-	(void) hipFree(arena);
-	if (failed || host_counters[2] > kWideStackMax) {
-		if (!failed) printf("The four-wide BVH would need a stack of %u entries per ray (at most %u are provided); shadow rays walk the binary tree.\n", host_counters[2], kWideStackMax);
-		(void) hipFree(wide);
-		return failed;
+	const float least_extent = extent * (1.0f / 512.0f);
+	const uint32_t blocks = block_count(n, 256);
+	size_t scan_bytes = 0, arena_bytes = 0;
+	int failed = hipcub::DeviceScan::ExclusiveSum(NULL, scan_bytes, (uint32_t*) NULL, (uint32_t*) NULL, (int) n, stream) != hipSuccess;
+	const size_t counts_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * (size_t) n), first_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * (size_t) n);
+	const size_t scan_at = vkr_carve(&arena_bytes, scan_bytes);
+	void *arena = NULL, *fragments = NULL;
+	failed = failed || vkr_device_alloc(&arena, device, arena_bytes, "the fragment counts of the triangles");
+	// A mesh of nothing but slivers would grow leaves, nodes and triangle_vertices sixteenfold.  Beyond four leaves per
+	// triangle on average the cap per triangle is halved until the mesh fits (16, 8, 4, 2: with two fragments a mesh at
+	// most doubles), so that the longest slivers - the ones for which splitting pays most - are still split (ADVICE round
+	// 5: until then such a mesh was built unsplit, a performance cliff exactly where splitting matters).
+	uint32_t most = kMostFragments, total = n;
+	while (!failed) {
+		uint32_t *counts = (uint32_t*) ((uint8_t*) arena + counts_at), *first = (uint32_t*) ((uint8_t*) arena + first_at);
+		uint32_t last[2] = {0, 0};
+		k_count_fragments<<<blocks, 256, 0, stream>>>(p, least_extent, most, counts);
+		failed = hipcub::DeviceScan::ExclusiveSum((uint8_t*) arena + scan_at, scan_bytes, counts, first, (int) n, stream) != hipSuccess
+			|| hipMemcpyAsync(&last[0], counts + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess
+			|| hipMemcpyAsync(&last[1], first + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess
+			|| hipStreamSynchronize(stream) != hipSuccess;
+		if (failed) break;
+		total = last[0] + last[1];
+		if ((uint64_t) total <= 4ull * n || most <= 2u) break;
+		most /= 2u;
 	}
-	structure->wide_nodes = wide;
-	structure->wide_node_count = host_counters[1];
-	structure->wide_stack_need = host_counters[2];
-	return 0;
+	if (!failed && most != kMostFragments && trace)
+		printf("Long thin triangles are split into at most %u fragments (16 would turn %u triangles into more than %llu leaves).\n", most, n, 4ull * n);
+	const bool worthwhile = !failed && total > n && (uint64_t) total <= 4ull * n;
+	// fragment_triangle[total], then fragment_boxes[6 total]
+	failed = failed || (worthwhile && vkr_device_alloc(&fragments, device, sizeof(uint32_t) * (size_t) total + sizeof(float) * 6 * (size_t) total + 16, "the fragments of the triangles"));
+	if (fragments) {
+		uint32_t* fragment_triangle = (uint32_t*) fragments;
+		float* fragment_boxes = (float*) (fragment_triangle + total);
+		k_write_fragments<<<blocks, 256, 0, stream>>>(p, least_extent, most, (const uint32_t*) ((uint8_t*) arena + first_at), fragment_triangle, fragment_boxes);
+		failed = hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess;
+		if (!failed) { p.fragment_triangle = fragment_triangle; p.fragment_boxes = fragment_boxes; p.triangle_count = total; }
+	}
+	vkr_device_free(arena, device);
+	if (failed) {
+		printf("Splitting the long thin triangles of the mesh failed; the BVH is built over whole triangles.\n");
+		vkr_device_free(fragments, device);
+		fragments = NULL;
+		(void) hipGetLastError();
+	}
+	return fragments;
 }
 
 // The binned SAH build by HIP kernels (see above); leaves fp32 threaded nodes in structure->nodes
 static int build_sah_on_device(acceleration_structure_t* structure, const device_t* device, const build_params& p, uint32_t* host_words) {
 	hipStream_t stream = (hipStream_t) device->stream;
-	uint32_t n = p.triangle_count;
-	uint32_t total_nodes = 2 * n - 1;
+	const uint32_t n = p.triangle_count, total_nodes = 2 * n - 1, blocks = block_count(n, 256);
 	// at most n / 2 nodes with two or more triangles are open at a time
-	uint32_t open_capacity = n / 2 + 1;
-	sah_open_node* open[2] = {NULL, NULL};
-	sah_bin* bins = NULL;
-	uint32_t *triangle_node = NULL, *counters = NULL;
+	const uint32_t open_capacity = n / 2 + 1;
 	// the temporaries of the build in ONE allocation (five hipMalloc / hipFree pairs of up to 90 MB were a
 	// third of the build's wall-clock time)
-	uint8_t* arena = NULL;
-	auto aligned = [](size_t bytes) { return (bytes + 255) & ~(size_t) 255; };
-	const size_t open_bytes = aligned(sizeof(sah_open_node) * (size_t) open_capacity), bin_bytes = aligned(sizeof(sah_bin) * 3 * kSahBinCount * (size_t) open_capacity),
-		triangle_node_bytes = aligned(sizeof(uint32_t) * (size_t) n);
-	int failed = 1;
-	do {
-		HIP_OK_BREAK(hipMalloc(&structure->triangle_vertices, sizeof(float4) * 3 * (size_t) n));
-		HIP_OK_BREAK(hipMalloc(&structure->nodes, sizeof(float4) * 2 * (size_t) total_nodes));
-		HIP_OK_BREAK(hipMalloc(&arena, 2 * open_bytes + bin_bytes + triangle_node_bytes + 256));
-		open[0] = (sah_open_node*) arena;
-		open[1] = (sah_open_node*) (arena + open_bytes);
-		bins = (sah_bin*) (arena + 2 * open_bytes);
-		triangle_node = (uint32_t*) (arena + 2 * open_bytes + bin_bytes);
-		counters = (uint32_t*) (arena + 2 * open_bytes + bin_bytes + triangle_node_bytes);
-		uint32_t blocks = (n + 255) / 256;
+	size_t arena_bytes = 0;
+	const size_t open_bytes = sizeof(sah_open_node) * (size_t) open_capacity;
+	const size_t open_at[2] = {vkr_carve(&arena_bytes, open_bytes), vkr_carve(&arena_bytes, open_bytes)};
+	const size_t bins_at = vkr_carve(&arena_bytes, sizeof(sah_bin) * 3 * kSahBinCount * (size_t) open_capacity), triangle_node_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * (size_t) n);
+	const size_t counters_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * 2);
+	void* arena = NULL;
+	int failed = vkr_device_alloc(&structure->triangle_vertices, device, sizeof(float4) * 3 * (size_t) n, "the triangles of the BVH")
+		|| vkr_device_alloc(&structure->nodes, device, sizeof(float4) * 2 * (size_t) total_nodes, "the nodes of the BVH")
+		|| vkr_device_alloc(&arena, device, arena_bytes, "the open nodes and bins of the SAH build");
+	if (!failed) {
+		uint8_t* base = (uint8_t*) arena;
+		sah_open_node* open[2] = {(sah_open_node*) (base + open_at[0]), (sah_open_node*) (base + open_at[1])};
+		sah_bin* bins = (sah_bin*) (base + bins_at);
+		uint32_t *triangle_node = (uint32_t*) (base + triangle_node_at), *counters = (uint32_t*) (base + counters_at);
+		float4 *nodes = (float4*) structure->nodes, *triangles = (float4*) structure->triangle_vertices;
 		k_sah_reset_root<<<1, 64, 0, stream>>>(open[0], n, counters);
-		k_sah_init<<<blocks, 256, 0, stream>>>(p, triangle_node, open[0], (float4*) structure->nodes, (float4*) structure->triangle_vertices);
+		k_sah_init<<<blocks, 256, 0, stream>>>(p, triangle_node, open[0], nodes, triangles);
 		uint32_t open_count = n > 1 ? 1u : 0u, level = 0;
-		bool ok = true;
-		while (open_count && ok) {
-			sah_open_node *now = open[level & 1], *next = open[(level + 1) & 1];
+		while (open_count && !failed) {
+			sah_open_node *current = open[level & 1], *next = open[(level + 1) & 1];
 			uint32_t bin_count = open_count * 3u * kSahBinCount;
-			k_sah_clear_bins<<<(bin_count + 255) / 256, 256, 0, stream>>>(bins, bin_count);
-			if (open_count <= kSahSharedNodes) k_sah_bin_shared<<<blocks, 256, 0, stream>>>(p, triangle_node, now, open_count, bins);
-			else k_sah_bin<<<blocks, 256, 0, stream>>>(p, triangle_node, now, bins);
-			k_sah_split<<<(open_count + kSplitNodesPerGroup - 1u) / kSplitNodesPerGroup, 256, 0, stream>>>(now, open_count, bins, next, counters, (float4*) structure->nodes, p.pad);
-			k_sah_assign<<<blocks, 256, 0, stream>>>(p, triangle_node, now, next, (float4*) structure->nodes, (float4*) structure->triangle_vertices);
+			k_sah_clear_bins<<<block_count(bin_count, 256), 256, 0, stream>>>(bins, bin_count);
+			if (open_count <= kSahSharedNodes) k_sah_bin_shared<<<blocks, 256, 0, stream>>>(p, triangle_node, current, open_count, bins);
+			else k_sah_bin<<<blocks, 256, 0, stream>>>(p, triangle_node, current, bins);
+			k_sah_split<<<block_count(open_count, kSplitNodesPerGroup), 256, 0, stream>>>(current, open_count, bins, next, counters, nodes, p.pad);
+			k_sah_assign<<<blocks, 256, 0, stream>>>(p, triangle_node, current, next, nodes, triangles);
 			k_publish_counters<<<1, 64, 0, stream>>>(counters, 1u, host_words);
-			ok = hipStreamSynchronize(stream) == hipSuccess;
-			uint32_t next_count = ((volatile uint32_t*) host_words)[0];
-			ok = ok && next_count <= open_capacity && ++level < 4096;
-			open_count = next_count;
+			failed = hipStreamSynchronize(stream) != hipSuccess;
+			open_count = ((volatile uint32_t*) host_words)[0];
+			failed = failed || open_count > open_capacity || ++level >= 4096;
 		}
-		if (!ok || hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) break;
-		structure->node_count = total_nodes;
-		structure->root = 0;
-		failed = 0;
-	} while (0);
-	(void) hipFree(arena);
+		failed = failed || hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess;
+	}
+	vkr_device_free(arena, device);
+	structure->node_count = total_nodes;
+	structure->root = 0;
 	return failed;
 }
 
 static int build_lbvh_on_device(acceleration_structure_t* structure, const device_t* device, const build_params& p) {
 	hipStream_t stream = (hipStream_t) device->stream;
-	uint32_t n = p.triangle_count;
-	uint32_t inner_count = n > 1 ? n - 1 : 1;
-	uint32_t total_nodes = 2 * n - 1;
-	bvh_build_node* build_nodes = NULL;
-	uint64_t *keys = NULL, *sorted_keys = NULL;
-	float *lo = NULL, *hi = NULL;
-	uint32_t *leaf_parents = NULL, *arrivals = NULL;
-	void* sort_storage = NULL;
-	size_t sort_bytes = 0;
-	int failed = 1;
-	do {
-		if (hipMalloc(&structure->triangle_vertices, sizeof(float4) * 3 * (size_t) n) != hipSuccess) break;
-		if (hipMalloc(&structure->nodes, sizeof(float4) * 2 * (size_t) total_nodes) != hipSuccess) break;
-		if (hipMalloc(&build_nodes, sizeof(bvh_build_node) * (size_t) inner_count) != hipSuccess) break;
-		if (hipMalloc(&keys, sizeof(uint64_t) * n) != hipSuccess || hipMalloc(&sorted_keys, sizeof(uint64_t) * n) != hipSuccess) break;
-		if (hipMalloc(&lo, sizeof(float) * 3 * (2 * (size_t) n)) != hipSuccess || hipMalloc(&hi, sizeof(float) * 3 * (2 * (size_t) n)) != hipSuccess) break;
-		if (hipMalloc(&leaf_parents, sizeof(uint32_t) * n) != hipSuccess || hipMalloc(&arrivals, sizeof(uint32_t) * inner_count) != hipSuccess) break;
-		if (hipMemsetAsync(arrivals, 0, sizeof(uint32_t) * inner_count, stream) != hipSuccess) break;
-		if (hipMemsetAsync(build_nodes, 0, sizeof(bvh_build_node) * (size_t) inner_count, stream) != hipSuccess) break;
-		uint32_t blocks = (n + 255) / 256;
-		k_morton_keys<<<blocks, 256, 0, stream>>>(p, keys);
-		if (hipcub::DeviceRadixSort::SortKeys(NULL, sort_bytes, keys, sorted_keys, (int) n, 0, 62, stream) != hipSuccess) break;
-		if (hipMalloc(&sort_storage, sort_bytes ? sort_bytes : 1) != hipSuccess) break;
-		if (hipcub::DeviceRadixSort::SortKeys(sort_storage, sort_bytes, keys, sorted_keys, (int) n, 0, 62, stream) != hipSuccess) break;
-		k_write_leaves<<<blocks, 256, 0, stream>>>(p, sorted_keys, (float4*) structure->triangle_vertices, lo, hi);
-		if (n > 1) {
-			k_build_hierarchy<<<(n - 1 + 255) / 256, 256, 0, stream>>>(sorted_keys, (int) n, build_nodes, leaf_parents);
-			k_refit<<<blocks, 256, 0, stream>>>((int) n, build_nodes, leaf_parents, lo, hi, arrivals);
+	const uint32_t n = p.triangle_count, inner_count = n > 1 ? n - 1 : 1, total_nodes = 2 * n - 1, blocks = block_count(n, 256);
+	size_t sort_bytes = 0, arena_bytes = 0;
+	int failed = hipcub::DeviceRadixSort::SortKeys(NULL, sort_bytes, (const uint64_t*) NULL, (uint64_t*) NULL, (int) n, 0, 62, stream) != hipSuccess;
+	// the temporaries in one allocation, like those of the SAH build
+	const size_t build_nodes_at = vkr_carve(&arena_bytes, sizeof(bvh_build_node) * (size_t) inner_count);
+	const size_t keys_at = vkr_carve(&arena_bytes, sizeof(uint64_t) * (size_t) n), sorted_keys_at = vkr_carve(&arena_bytes, sizeof(uint64_t) * (size_t) n);
+	const size_t lo_at = vkr_carve(&arena_bytes, sizeof(float) * 3 * (2 * (size_t) n)), hi_at = vkr_carve(&arena_bytes, sizeof(float) * 3 * (2 * (size_t) n));
+	const size_t leaf_parents_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * (size_t) n), arrivals_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * (size_t) inner_count);
+	const size_t sort_storage_at = vkr_carve(&arena_bytes, sort_bytes);
+	void* arena = NULL;
+	failed = failed || vkr_device_alloc(&structure->triangle_vertices, device, sizeof(float4) * 3 * (size_t) n, "the triangles of the BVH")
+		|| vkr_device_alloc(&structure->nodes, device, sizeof(float4) * 2 * (size_t) total_nodes, "the nodes of the BVH")
+		|| vkr_device_alloc(&arena, device, arena_bytes, "the keys, boxes and radix tree of the LBVH build");
+	if (!failed) {
+		uint8_t* base = (uint8_t*) arena;
+		bvh_build_node* build_nodes = (bvh_build_node*) (base + build_nodes_at);
+		uint64_t *keys = (uint64_t*) (base + keys_at), *sorted_keys = (uint64_t*) (base + sorted_keys_at);
+		float *lo = (float*) (base + lo_at), *hi = (float*) (base + hi_at);
+		uint32_t *leaf_parents = (uint32_t*) (base + leaf_parents_at), *arrivals = (uint32_t*) (base + arrivals_at);
+		failed = hipMemsetAsync(arrivals, 0, sizeof(uint32_t) * inner_count, stream) != hipSuccess
+			|| hipMemsetAsync(build_nodes, 0, sizeof(bvh_build_node) * (size_t) inner_count, stream) != hipSuccess;
+		if (!failed) {
+			k_morton_keys<<<blocks, 256, 0, stream>>>(p, keys);
+			failed = hipcub::DeviceRadixSort::SortKeys(base + sort_storage_at, sort_bytes, keys, sorted_keys, (int) n, 0, 62, stream) != hipSuccess;
 		}
-		k_thread_nodes<<<(total_nodes + 255) / 256, 256, 0, stream>>>((int) n, build_nodes, leaf_parents, lo, hi, (float4*) structure->nodes);
-		structure->root = 0;
-		if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) break;
-		structure->node_count = total_nodes;
-		failed = 0;
-	} while (0);
-	(void) hipFree(keys); (void) hipFree(sorted_keys); (void) hipFree(lo); (void) hipFree(hi);
-	(void) hipFree(leaf_parents); (void) hipFree(arrivals); (void) hipFree(sort_storage); (void) hipFree(build_nodes);
+		if (!failed) {
+			k_write_leaves<<<blocks, 256, 0, stream>>>(p, sorted_keys, (float4*) structure->triangle_vertices, lo, hi);
+			if (n > 1) {
+				k_build_hierarchy<<<block_count(n - 1, 256), 256, 0, stream>>>(sorted_keys, (int) n, build_nodes, leaf_parents);
+				k_refit<<<blocks, 256, 0, stream>>>((int) n, build_nodes, leaf_parents, lo, hi, arrivals);
+			}
+			k_thread_nodes<<<block_count(total_nodes, 256), 256, 0, stream>>>((int) n, build_nodes, leaf_parents, lo, hi, (float4*) structure->nodes);
+			failed = hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess;
+		}
+	}
+	vkr_device_free(arena, device);
+	structure->node_count = total_nodes;
+	structure->root = 0;
 	return failed;
 }
 
@@ -986,6 +981,85 @@ static int build_sah_on_host(acceleration_structure_t* structure, const device_t
 	return upload_failed;
 }
 
+// Replaces structure->nodes (fp32 threaded nodes on the device) by the quantised nodes
+static int quantize_nodes(acceleration_structure_t* structure, const device_t* device) {
+	hipStream_t stream = (hipStream_t) device->stream;
+	float root[8];
+	void* quantized = NULL;
+	int failed = hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(root, structure->nodes, sizeof(root), hipMemcpyDeviceToHost) != hipSuccess
+		|| vkr_device_alloc(&quantized, device, sizeof(uint4) * (size_t) structure->node_count, "the quantised BVH nodes");
+	if (!failed) {
+		const float lo[3] = {root[0], root[1], root[2]}, hi[3] = {root[3], root[4], root[5]};
+		for (int j = 0; j != 3; ++j) {
+			// one spare cell on either side keeps every box strictly inside [0, kGridMax]
+			float extent = fmaxf(hi[j] - lo[j], 1.0e-20f);
+			float cell = extent / (kGridMax - 2.0f);
+			structure->grid_origin[j] = lo[j] - cell;
+			structure->grid_inverse_cell[j] = 1.0f / cell;
+		}
+		k_quantize_nodes<<<block_count(structure->node_count, 256), 256, 0, stream>>>(structure->node_count, (const float4*) structure->nodes,
+			f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]},
+			f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]}, (uint4*) quantized);
+		failed = hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess;
+	}
+	if (failed) printf("Quantising the BVH nodes failed.\n");
+	vkr_device_free(failed ? quantized : structure->nodes, device);
+	if (!failed) structure->nodes = quantized;
+	return failed;
+}
+
+// Binary quantised nodes -> four-wide nodes, one level per launch (a level's node count is only
+// known when the level before it has been written).  Leaves structure->wide_nodes NULL (the
+// kernels then walk the binary tree) if the tree is a single leaf or a ray could need a deeper
+// stack than the kernels provide.
+static int collapse_to_wide(acceleration_structure_t* structure, const device_t* device, uint32_t* host_words) {
+	const uint32_t triangle_count = (structure->node_count + 1) / 2;
+	if (triangle_count < 2) return 0;
+	hipStream_t stream = (hipStream_t) device->stream;
+	size_t arena_bytes = 0;
+	const size_t item_bytes = sizeof(wide_item) * (size_t) triangle_count;
+	const size_t items_at[2] = {vkr_carve(&arena_bytes, item_bytes), vkr_carve(&arena_bytes, item_bytes)};
+	const size_t counters_at = vkr_carve(&arena_bytes, sizeof(uint32_t) * 3);
+	void *arena = NULL, *wide = NULL;
+	uint32_t host_counters[3] = {0, 1, 0};
+	int failed = vkr_device_alloc(&arena, device, arena_bytes, "the work lists of the four-wide collapse")
+		|| vkr_device_alloc(&wide, device, sizeof(uint4) * 4 * (size_t) (triangle_count - 1), "the four-wide BVH nodes");
+	if (!failed) {
+		uint8_t* base = (uint8_t*) arena;
+		wide_item* items[2] = {(wide_item*) (base + items_at[0]), (wide_item*) (base + items_at[1])};
+		uint32_t* counters = (uint32_t*) (base + counters_at);
+		const wide_item root = {0u, 0u, 0u};
+		failed = hipMemcpyAsync(items[0], &root, sizeof(root), hipMemcpyHostToDevice, stream) != hipSuccess
+			|| hipMemcpyAsync(counters, host_counters, sizeof(host_counters), hipMemcpyHostToDevice, stream) != hipSuccess;
+		uint32_t item_count = 1, level = 0;
+		while (item_count && !failed) {
+			k_collapse_level<<<block_count(item_count, 64), 64, 0, stream>>>((const uint4*) structure->nodes, items[level & 1], item_count, items[(level + 1) & 1], counters, (uint4*) wide);
+			k_publish_counters<<<1, 64, 0, stream>>>(counters, 3u, host_words);
+			failed = hipStreamSynchronize(stream) != hipSuccess || ++level >= 4096;
+			for (int i = 0; i != 3; ++i) host_counters[i] = ((volatile uint32_t*) host_words)[i];
+			item_count = host_counters[0];
+		}
+		failed = failed || hipGetLastError() != hipSuccess;
+	}
+	vkr_device_free(arena, device);
+	if (!failed && host_counters[2] <= kWideStackMax) {
+		structure->wide_nodes = wide;
+		structure->wide_node_count = host_counters[1];
+		structure->wide_stack_need = host_counters[2];
+		return 0;
+	}
+	if (!failed) printf("The four-wide BVH would need a stack of %u entries per ray (at most %u are provided); shadow rays walk the binary tree.\n", host_counters[2], kWideStackMax);
+	vkr_device_free(wide, device);
+	return failed;
+}
+
+extern "C" void vkr_destroy_acceleration_structure(acceleration_structure_t* structure, const device_t* device) {
+	vkr_device_free(structure->triangle_vertices, device);
+	vkr_device_free(structure->nodes, device);
+	vkr_device_free(structure->wide_nodes, device);
+	memset(structure, 0, sizeof(*structure));
+}
+
 extern "C" int vkr_build_acceleration_structure(acceleration_structure_t* structure, const device_t* device, const mesh_t* mesh, int builder) {
 	memset(structure, 0, sizeof(*structure));
 	if (builder <= (int) acceleration_structure_none || builder >= (int) acceleration_structure_builder_count) {
@@ -996,128 +1070,41 @@ extern "C" int vkr_build_acceleration_structure(acceleration_structure_t* struct
 		printf("The BVH builders support 1 to 2^31 triangles, the mesh has %llu.\n", (unsigned long long) mesh->triangle_count);
 		return 1;
 	}
-	hipStream_t stream = (hipStream_t) device->stream;
-	uint32_t n = (uint32_t) mesh->triangle_count;
-	build_params p;
-	p.quantized_positions = (const uint2*) mesh->positions;
-	p.triangle_count = n;
-	p.fragment_triangle = NULL;
-	p.fragment_boxes = NULL;
-	float extent = 0.0f;
-	for (int j = 0; j != 3; ++j) {
-		p.factor[j] = mesh->dequantization_factor[j];
-		p.summand[j] = mesh->dequantization_summand[j];
-		// largest coordinate magnitude and extent of the quantisation grid
-		extent = fmaxf(extent, 2097152.0f * fabsf(mesh->dequantization_factor[j]));
-		extent = fmaxf(extent, fmaxf(fabsf(mesh->dequantization_summand[j]), fabsf(mesh->dequantization_summand[j] + 2097152.0f * mesh->dequantization_factor[j])));
-	}
-	// Conservative padding.  The slab test evaluates plane * (1/d) - o * (1/d) with a
-	// 1-ulp reciprocal and two roundings, i.e. it misplaces a plane by about
-	// |o| 2^-23; the triangle test may accept hits about as far outside the triangle.
-	// 2e-6 of the largest coordinate is sixteen times that.  (The padding must stay
-	// far below t_min = 1e-3: a ray leaving a flat floor would otherwise start inside
-	// the padded boxes of the floor and walk down to its own triangle.)
-	p.pad = 2.0e-6f * extent;
-	if (hipStreamSynchronize(stream) != hipSuccess) return 1;
-	struct timespec start, end;
-	clock_gettime(CLOCK_MONOTONIC, &start);
-	// VKR_BVH_BUILD_TRACE=1 prints the wall-clock time of the three phases (diagnostics)
-	const bool trace = getenv("VKR_BVH_BUILD_TRACE") != NULL;
-	struct timespec phase[3] = {start, start, start};
+	const uint32_t n = (uint32_t) mesh->triangle_count;
+	float extent;
+	build_params p = make_build_params(mesh, &extent);
+	if (hipStreamSynchronize((hipStream_t) device->stream) != hipSuccess) return 1;
+	const struct timespec start = now();
 	// (pinned: where the level loops of the build read their counters, k_publish_counters)
 	uint32_t* host_words = NULL;
-	if (hipHostMalloc(&host_words, 64) != hipSuccess) {
+	if (vkr_host_alloc_pinned((void**) &host_words, 64)) {
 		printf("Failed to allocate pinned host memory for the BVH build.\n");
 		return 1;
 	}
-	// device SAH: long thin triangles that lie diagonally in their boxes become several primitives ("fragments" above;
-	// VKR_BVH_SPLIT_TRIANGLES=0 builds over whole triangles as until round 3)
-	void* fragment_memory = NULL;
-	const char* split_knob = getenv("VKR_BVH_SPLIT_TRIANGLES");
-	// (a triangle becomes at most 16 fragments: up to 2^31 / 16 triangles the 32-bit prefix sum of the counts cannot wrap;
-	// beyond that the mesh is built unsplit)
-	if (builder == (int) acceleration_structure_sah_device && n > 1 && n <= 0x7FFFFFFFu / 16u && !(split_knob && split_knob[0] == '0')) {
-		uint32_t* counts = NULL;
-		void* scan_storage = NULL;
-		size_t scan_bytes = 0;
-		const float least_extent = extent * (1.0f / 512.0f);
-		uint32_t blocks = (n + 255) / 256, total = n;
-		bool ok = hipMalloc(&counts, sizeof(uint32_t) * 2 * (size_t) n) == hipSuccess;
-		uint32_t* first = counts ? counts + n : NULL;
-		// A mesh of nothing but slivers would grow leaves, nodes and triangle_vertices sixteenfold.  Beyond four leaves per
-		// triangle on average the cap per triangle is halved until the mesh fits (16, 8, 4, 2: with two fragments a mesh at
-		// most doubles), so that the longest slivers - the ones for which splitting pays most - are still split (ADVICE round
-		// 5: until then such a mesh was built unsplit, a performance cliff exactly where splitting matters).
-		uint32_t most = kMostFragments;
-		while (ok) {
-			k_count_fragments<<<blocks, 256, 0, stream>>>(p, least_extent, most, counts);
-			if (!scan_storage)
-				ok = hipcub::DeviceScan::ExclusiveSum(NULL, scan_bytes, counts, first, (int) n, stream) == hipSuccess
-					&& hipMalloc(&scan_storage, scan_bytes ? scan_bytes : 1) == hipSuccess;
-			ok = ok && hipcub::DeviceScan::ExclusiveSum(scan_storage, scan_bytes, counts, first, (int) n, stream) == hipSuccess;
-			uint32_t last[2] = {0, 0};
-			ok = ok && hipMemcpyAsync(&last[0], counts + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess
-				&& hipMemcpyAsync(&last[1], first + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess
-				&& hipStreamSynchronize(stream) == hipSuccess;
-			if (!ok) break;
-			total = last[0] + last[1];
-			if ((uint64_t) total <= 4ull * n || most <= 2u) break;
-			most /= 2u;
-		}
-		if (ok && most != kMostFragments && trace)
-			printf("Long thin triangles are split into at most %u fragments (16 would turn %u triangles into more than %llu leaves).\n", most, n, 4ull * n);
-		if (ok && total > n && (uint64_t) total <= 4ull * n) {
-			// fragment_triangle[total], then fragment_boxes[6 total]
-			ok = hipMalloc(&fragment_memory, sizeof(uint32_t) * (size_t) total + sizeof(float) * 6 * (size_t) total + 16) == hipSuccess;
-			if (ok) {
-				uint32_t* fragment_triangle = (uint32_t*) fragment_memory;
-				float* fragment_boxes = (float*) (fragment_triangle + total);
-				k_write_fragments<<<blocks, 256, 0, stream>>>(p, least_extent, most, first, fragment_triangle, fragment_boxes);
-				ok = hipStreamSynchronize(stream) == hipSuccess && hipGetLastError() == hipSuccess;
-				if (ok) {
-					p.fragment_triangle = fragment_triangle;
-					p.fragment_boxes = fragment_boxes;
-					p.triangle_count = total;
-				}
-			}
-		}
-		(void) hipFree(scan_storage);
-		(void) hipFree(counts);
-		if (!ok) {
-			printf("Splitting the long thin triangles of the mesh failed; the BVH is built over whole triangles.\n");
-			(void) hipFree(fragment_memory);
-			fragment_memory = NULL;
-			p.fragment_triangle = NULL; p.fragment_boxes = NULL; p.triangle_count = n;
-			(void) hipGetLastError();
-		}
-	}
+	// VKR_BVH_BUILD_TRACE=1 prints the wall-clock time of the three phases (diagnostics)
+	const bool trace = getenv("VKR_BVH_BUILD_TRACE") != NULL;
+	void* fragments = split_long_triangles(p, device, builder, extent, trace);
 	int failed = builder == (int) acceleration_structure_sah_host ? build_sah_on_host(structure, device, mesh, p.pad)
 		: (builder == (int) acceleration_structure_lbvh_device ? build_lbvh_on_device(structure, device, p) : build_sah_on_device(structure, device, p, host_words));
-	(void) hipFree(fragment_memory);
-	if (trace) clock_gettime(CLOCK_MONOTONIC, &phase[0]);
-	if (!failed) {
-		failed = quantize_nodes(structure, device);
-		if (failed) printf("Quantising the BVH nodes failed.\n");
-	}
-	if (trace) clock_gettime(CLOCK_MONOTONIC, &phase[1]);
-	if (!failed) failed = collapse_to_wide(structure, device, host_words);
-	(void) hipHostFree(host_words);
-	if (trace) {
-		clock_gettime(CLOCK_MONOTONIC, &phase[2]);
-		auto ms = [](const struct timespec& a, const struct timespec& b) { return (double) (b.tv_sec - a.tv_sec) * 1.0e3 + (double) (b.tv_nsec - a.tv_nsec) * 1.0e-6; };
-		printf("BVH build over %u triangles: tree %.3f ms, quantisation %.3f ms, four-wide collapse %.3f ms\n", n, ms(start, phase[0]), ms(phase[0], phase[1]), ms(phase[1], phase[2]));
-	}
+	vkr_device_free(fragments, device);
+	const struct timespec tree_built = now();
+	failed = failed || quantize_nodes(structure, device);
+	const struct timespec quantized = now();
+	failed = failed || collapse_to_wide(structure, device, host_words);
+	vkr_host_free_pinned(host_words);
+	const struct timespec collapsed = now();
+	if (trace)
+		printf("BVH build over %u triangles: tree %.3f ms, quantisation %.3f ms, four-wide collapse %.3f ms\n", n, milliseconds(start, tree_built), milliseconds(tree_built, quantized), milliseconds(quantized, collapsed));
 	if (failed) {
 		printf("Building the BVH over %u triangles failed: %s\n", n, hipGetErrorString(hipGetLastError()));
 		vkr_destroy_acceleration_structure(structure, device);
 		return 1;
 	}
-	clock_gettime(CLOCK_MONOTONIC, &end);
 	structure->builder = (uint32_t) builder;
 	structure->leaf_count = (structure->node_count + 1u) / 2u;
 	// (ranks of one process build their trees on threads of their own: vkr_multi_gpu)
 	static std::atomic<uint32_t> builds{0};
 	structure->build_serial = builds.fetch_add(1u) + 1u;
-	structure->build_milliseconds = (float) ((double) (end.tv_sec - start.tv_sec) * 1.0e3 + (double) (end.tv_nsec - start.tv_nsec) * 1.0e-6);
+	structure->build_milliseconds = (float) milliseconds(start, now());
 	return 0;
 }

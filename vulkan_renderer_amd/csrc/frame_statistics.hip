@@ -12,12 +12,6 @@ constexpr uint32_t kBlock = 256;
 // (the grid's x extent)
 constexpr uint64_t kMaxPixelCount = 0x7FFFFFFFull * kBlock;
 
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
 template <int K> struct frame_sources {
@@ -93,8 +87,6 @@ static hipStream_t device_stream(const application_t* app) { return (hipStream_t
 
 static uint64_t frame_pixel_count(const application_t* app) { return (uint64_t) app->swapchain.extent.width * app->swapchain.extent.height; }
 
-static uint32_t block_count(uint64_t pixel_count) { return (uint32_t) ((pixel_count + kBlock - 1) / kBlock); }
-
 // Makes `stream` wait for the accumulations queued so far
 static int wait_for_accumulations(const frame_statistics_t* stats, hipStream_t stream) {
 	if (!stats->pending) return 0;
@@ -166,7 +158,7 @@ extern "C" int reset_frame_statistics(frame_statistics_t* stats, application_t* 
 template <int K> static void launch_accumulate(const void* const* frames, frame_statistics_t* stats) {
 	frame_sources<K> sources;
 	for (int k = 0; k != K; ++k) sources.frame[k] = (const float4*) frames[k];
-	k_accumulate_frames<K><<<block_count(stats->pixel_count), kBlock, 0, (hipStream_t) stats->stream>>>(sources, (double2*) stats->sums, stats->pixel_count);
+	k_accumulate_frames<K><<<block_count(stats->pixel_count, kBlock), kBlock, 0, (hipStream_t) stats->stream>>>(sources, (double2*) stats->sums, stats->pixel_count);
 }
 
 extern "C" int accumulate_frames(frame_statistics_t* stats, application_t* app, const void* const* device_frames, uint32_t count) {
@@ -231,7 +223,7 @@ extern "C" int resolve_frame_statistics(frame_statistics_t* stats, application_t
 	if (finish_frames(app) || wait_for_accumulations(stats, stream)) return 1;
 	if (out_mean) vkr_order_target_write(app, out_mean, bytes, stream);
 	if (out_variance) vkr_order_target_write(app, out_variance, bytes, stream);
-	k_resolve_statistics<<<block_count(stats->pixel_count), kBlock, 0, stream>>>((const double2*) stats->sums, stats->pixel_count, stats->frame_count, (float4*) out_mean, (float4*) out_variance);
+	k_resolve_statistics<<<block_count(stats->pixel_count, kBlock), kBlock, 0, stream>>>((const double2*) stats->sums, stats->pixel_count, stats->frame_count, (float4*) out_mean, (float4*) out_variance);
 	if (hip_failed(hipGetLastError(), "resolving the statistics")
 		|| hip_failed(hipEventRecord((hipEvent_t) stats->resolved, stream), "marking the resolve"))
 		return 1;
@@ -268,7 +260,7 @@ static int reduce_frames(application_t* app, const void* a, const void* b, uint6
 		return 1;
 	}
 	hipStream_t stream = device_stream(app);
-	uint32_t blocks = block_count(pixel_count);
+	uint32_t blocks = block_count(pixel_count, kBlock);
 	size_t bytes = sizeof(double) * 3 * (size_t) blocks;
 	double* partials = NULL;
 	double* host = (double*) malloc(bytes);

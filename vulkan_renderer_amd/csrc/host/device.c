@@ -1,13 +1,6 @@
 /* HIP context and memory helpers behind device_t.  Plain C on top of the HIP
  * runtime's C API. */
 #include "vkr_internal.h"
-#include <hip/hip_runtime_api.h>
-
-static int check(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
 
 /* Makes sure that the first `count` frame streams exist (and have run their first kernel).
    The frame streams have the default priority.  Measured and removed: the lowest priority, so
@@ -20,12 +13,12 @@ int vkr_ensure_frame_streams(device_t* device, uint32_t count) {
 	for (uint32_t i = 0; i != count; ++i) {
 		if (device->frame_streams[i]) continue;
 		hipStream_t stream = NULL;
-		if (check(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "creating a frame stream")) return 1;
+		if (hip_failed(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "creating a frame stream")) return 1;
 		device->frame_streams[i] = stream;
 		/* The first kernel a process launches on a stream pays for the stream's hardware queue and for
 		   loading the code object: several milliseconds that would otherwise be billed to whatever
 		   comes first.  An empty kernel moves them here.  VKR_NO_WARM_UP=1 leaves it out. */
-		if (!getenv("VKR_NO_WARM_UP") && (vkr_launch_empty_kernel(stream) || check(hipStreamSynchronize(stream), "warming a frame stream up"))) return 1;
+		if (!getenv("VKR_NO_WARM_UP") && (vkr_launch_empty_kernel(stream) || hip_failed(hipStreamSynchronize(stream), "warming a frame stream up"))) return 1;
 	}
 	return 0;
 }
@@ -41,9 +34,9 @@ int create_hip_device(device_t* device, int32_t hip_device, void* existing_strea
 		printf("HIP device %d was requested but only %d devices exist.\n", hip_device, count);
 		return 1;
 	}
-	if (check(hipSetDevice(hip_device), "selecting the device")) return 1;
+	if (hip_failed(hipSetDevice(hip_device), "selecting the device")) return 1;
 	hipDeviceProp_t properties;
-	if (check(hipGetDeviceProperties(&properties, hip_device), "querying device properties")) return 1;
+	if (hip_failed(hipGetDeviceProperties(&properties, hip_device), "querying device properties")) return 1;
 	device->hip_device = hip_device;
 	device->stream = existing_stream;
 	device->ray_tracing_supported = VK_TRUE;
@@ -91,8 +84,8 @@ void destroy_hip_device(device_t* device) {
 int wait_for_device(const device_t* device) {
 	int failed = 0;
 	for (int i = 0; i != VKR_MAX_FRAMES_IN_FLIGHT; ++i)
-		if (device->frame_streams[i]) failed |= check(hipStreamSynchronize((hipStream_t) device->frame_streams[i]), "waiting for a frame stream");
-	return failed | check(hipStreamSynchronize((hipStream_t) device->stream), "waiting for the stream");
+		if (device->frame_streams[i]) failed |= hip_failed(hipStreamSynchronize((hipStream_t) device->frame_streams[i]), "waiting for a frame stream");
+	return failed | hip_failed(hipStreamSynchronize((hipStream_t) device->stream), "waiting for the stream");
 }
 
 int vkr_device_alloc(void** out, const device_t* device, size_t size, const char* what) {
@@ -114,7 +107,7 @@ void vkr_device_free(void* pointer, const device_t* device) {
 int vkr_device_upload(void** out, const device_t* device, const void* host, size_t size, const char* what) {
 	if (vkr_device_alloc(out, device, size, what)) return 1;
 	if (!device) return 0;
-	if (check(hipMemcpy(*out, host, size, hipMemcpyHostToDevice), what)) {
+	if (hip_failed(hipMemcpy(*out, host, size, hipMemcpyHostToDevice), what)) {
 		hipFree(*out);
 		*out = NULL;
 		return 1;
@@ -132,10 +125,10 @@ void vkr_host_free_pinned(void* pointer) {
 }
 
 int vkr_copy_to_device_async(void* device_pointer, const void* host, size_t size, const device_t* device) {
-	return check(hipMemcpyAsync(device_pointer, host, size, hipMemcpyHostToDevice, (hipStream_t) device->stream), "uploading");
+	return hip_failed(hipMemcpyAsync(device_pointer, host, size, hipMemcpyHostToDevice, (hipStream_t) device->stream), "uploading");
 }
 
 int vkr_copy_to_host(void* host, const void* device_pointer, size_t size, const device_t* device) {
-	if (check(hipMemcpyAsync(host, device_pointer, size, hipMemcpyDeviceToHost, (hipStream_t) device->stream), "reading back")) return 1;
-	return check(hipStreamSynchronize((hipStream_t) device->stream), "reading back");
+	if (hip_failed(hipMemcpyAsync(host, device_pointer, size, hipMemcpyDeviceToHost, (hipStream_t) device->stream), "reading back")) return 1;
+	return hip_failed(hipStreamSynchronize((hipStream_t) device->stream), "reading back");
 }

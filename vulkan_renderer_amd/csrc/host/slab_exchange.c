@@ -16,7 +16,6 @@
  * (assemble_exchanged_frame, finish_slab_exchange) - SURVEY.md 8(e): "or un-tile on the consumer only". */
 #include "vkr_internal.h"
 #include "vkr_slab_exchange.h"
-#include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <pthread.h>
@@ -30,12 +29,6 @@ typedef struct rccl_binding_s {
 	__typeof__(&ncclGetErrorString) get_error_string;
 	ncclComm_t communicator;
 } rccl_binding_t;
-
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
 
 /* RCCL is loaded once per process and stays loaded: it registers exit handlers and keeps helper threads
    (the bootstrap thread of a rendezvous token, proxy threads of a communicator) whose code must not be

@@ -2,6 +2,7 @@
 #ifndef VKR_INTERNAL_H
 #define VKR_INTERNAL_H
 #include "vkr_shading_pass.h"
+#include "vkr_hip.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,7 +26,7 @@ int vkr_device_alloc(void** out, const device_t* device, size_t size, const char
 void vkr_device_free(void* pointer, const device_t* device);
 int vkr_device_upload(void** out, const device_t* device, const void* host, size_t size, const char* what);
 int vkr_host_alloc_pinned(void** out, size_t size);
-/* lbvh_build.hip: an empty kernel on `stream` (create_hip_device() warms the queues up with it) */
+/* output_encoding.hip: an empty kernel on `stream` (create_hip_device() warms the queues up with it) */
 int vkr_launch_empty_kernel(void* stream);
 /* fills the per-device tables of the kernels (sRGB code thresholds) and waits for it (output_encoding.hip) */
 int vkr_fill_device_tables(void* stream);

@@ -6,12 +6,6 @@
 #include "host/vkr_internal.h"
 #include <hip/hip_runtime.h>
 
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
 constexpr double kPi = 3.141592653589793;
 constexpr double kInvPi = 1.0 / kPi;
 constexpr double kTolerance = 1e-12;

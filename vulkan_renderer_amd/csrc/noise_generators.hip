@@ -5,12 +5,6 @@
 #include "host/vkr_internal.h"
 #include <hip/hip_runtime.h>
 
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
 // (vkr_wang_random_number of host/noise_table.c)
 __host__ __device__ static inline uint32_t wang(uint32_t seed) {
 	seed = (seed ^ 61u) ^ (seed >> 16);

@@ -57,6 +57,13 @@ extern "C" int vkr_fill_device_tables(void* stream) {
 	return hip_failed(hipStreamSynchronize((hipStream_t) stream), "filling the sRGB code starts");
 }
 
+// The other thing device.c needs from a HIP unit: the kernel that warms a stream up
+static __global__ void k_empty() {}
+extern "C" int vkr_launch_empty_kernel(void* stream) {
+	k_empty<<<1, 64, 0, (hipStream_t) stream>>>();
+	return hipGetLastError() != hipSuccess;
+}
+
 __device__ __forceinline__ uint32_t srgb_code(float v) {
 	v = gclamp(v, 0.0f, 1.0f);  // (NaN -> 0 like to_unorm8(linear_to_srgb(NaN)))
 	float estimate = (v <= 0.0031308f) ? (12.92f * v) : fmaf(1.055f, __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(v) * (1.0f / 2.4f)), -0.055f);

@@ -6,12 +6,6 @@
 #include "shading_kernel.h"
 #include "host/vkr_internal.h"
 
-inline int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
 inline vkr::bvh_view make_bvh_view(const acceleration_structure_t* structure) {
 	vkr::bvh_view view;
 	view.nodes = (const uint4*) structure->nodes;

@@ -8,12 +8,6 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
 constexpr uint32_t kBlock = 256, kWave = 64;
 // the reductions run over at most this many workgroups (each ends in six atomics on the same words)
 constexpr uint32_t kMostReductionBlocks = 1024;
@@ -249,12 +243,10 @@ __global__ void __launch_bounds__(kBlock) k_write_triangles(export_args a) {
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
 
-static inline uint32_t block_count(uint64_t lanes) { return (uint32_t) ((lanes + kBlock - 1) / kBlock); }
 static inline uint32_t reduction_block_count(uint64_t lanes) {
 	uint64_t blocks = (lanes + kBlock - 1) / kBlock;
 	return (uint32_t) (blocks < kMostReductionBlocks ? blocks : kMostReductionBlocks);
 }
-static inline size_t aligned(size_t size) { return (size + 255) & ~(size_t) 255; }
 
 static float last_kernel_milliseconds = 0.0f;
 extern "C" float get_scene_export_kernel_milliseconds(void) { return last_kernel_milliseconds; }
@@ -285,18 +277,22 @@ extern "C" int export_scene(exported_scene_t* out, const device_t* device, const
 	size_t attribute_bytes = sizeof(float) * 3 * V;
 	size_t index_bytes = source->vertex_indices ? sizeof(uint32_t) * 3 * (size_t) T : 0, tex_coord_bytes = source->corner_tex_coords ? sizeof(float) * 6 * (size_t) T : 0;
 	size_t material_bytes = source->material_indices ? (size_t) T : 0;
-	size_t normals_at = aligned(attribute_bytes), indices_at = normals_at + aligned(attribute_bytes), tex_coords_at = indices_at + aligned(index_bytes);
-	size_t materials_at = tex_coords_at + aligned(tex_coord_bytes), source_bytes = materials_at + aligned(material_bytes);
-	size_t records_at = aligned(sizeof(export_state)), centroids_at = records_at + aligned(sizeof(uint4) * V);
-	size_t keys_at = centroids_at + (sort_triangles ? aligned(sizeof(float) * 3 * (size_t) T) : 0), sorted_keys_at = keys_at + (sort_triangles ? aligned(sizeof(uint64_t) * T) : 0);
-	size_t sort_storage_at = sorted_keys_at + (sort_triangles ? aligned(sizeof(uint64_t) * T) : 0), sort_bytes = 0;
+	size_t source_bytes = 0, temporary_bytes = 0, output_bytes = 0, sort_bytes = 0;
 	if (sort_triangles && hipcub::DeviceRadixSort::SortKeys(NULL, sort_bytes, (const uint64_t*) NULL, (uint64_t*) NULL, (int) T, 0, 62, (hipStream_t) device->stream) != hipSuccess) {
 		printf("Failed to size the sort of %u triangles.\n", T);
 		return 1;
 	}
-	size_t temporary_bytes = sort_storage_at + aligned(sort_bytes);
 	size_t position_bytes = sizeof(uint32_t) * 6 * (size_t) T, code_bytes = sizeof(uint16_t) * 12 * (size_t) T;
-	size_t codes_at = aligned(position_bytes), out_materials_at = codes_at + aligned(code_bytes), output_bytes = out_materials_at + aligned(T);
+	// (the positions, the export_state and the packed positions are what the three buffers begin with)
+	vkr_carve(&source_bytes, attribute_bytes);
+	const size_t normals_at = vkr_carve(&source_bytes, attribute_bytes), indices_at = vkr_carve(&source_bytes, index_bytes);
+	const size_t tex_coords_at = vkr_carve(&source_bytes, tex_coord_bytes), materials_at = vkr_carve(&source_bytes, material_bytes);
+	vkr_carve(&temporary_bytes, sizeof(export_state));
+	const size_t records_at = vkr_carve(&temporary_bytes, sizeof(uint4) * V), centroids_at = vkr_carve(&temporary_bytes, sort_triangles ? sizeof(float) * 3 * (size_t) T : 0);
+	const size_t keys_at = vkr_carve(&temporary_bytes, sort_triangles ? sizeof(uint64_t) * T : 0), sorted_keys_at = vkr_carve(&temporary_bytes, sort_triangles ? sizeof(uint64_t) * T : 0);
+	const size_t sort_storage_at = vkr_carve(&temporary_bytes, sort_bytes);
+	vkr_carve(&output_bytes, position_bytes);
+	const size_t codes_at = vkr_carve(&output_bytes, code_bytes), out_materials_at = vkr_carve(&output_bytes, T);
 
 	out->triangle_count = T;
 	out->positions = (uint32_t*) malloc(position_bytes);
@@ -358,7 +354,7 @@ extern "C" int export_scene(exported_scene_t* out, const device_t* device, const
 		for (uint32_t j = 0; j != 3; ++j) { lo[j] = float_of_ordered_image(state.vertex_lo[j]); hi[j] = float_of_ordered_image(state.vertex_hi[j]); }
 		vkr_scene_export_box_constants(args.qf, args.qo, lo, hi, 2097152.0f);
 		vkr_scene_export_dequantization(out, args.qf, lo, hi);
-		k_vertex_records<<<block_count(V), kBlock, 0, stream>>>(args);
+		k_vertex_records<<<block_count(V, kBlock), kBlock, 0, stream>>>(args);
 		failed = hip_failed(hipGetLastError(), "packing the vertices");
 	}
 	if (!failed && sort_triangles) {
@@ -366,13 +362,13 @@ extern "C" int export_scene(exported_scene_t* out, const device_t* device, const
 		for (uint32_t j = 0; j != 3; ++j) { lo[j] = float_of_ordered_image(state.centroid_lo[j]); hi[j] = float_of_ordered_image(state.centroid_hi[j]); }
 		vkr_scene_export_box_constants(args.mf, args.mo, lo, hi, 1024.0f);
 		uint64_t* sorted_keys = (uint64_t*) ((uint8_t*) temporaries + sorted_keys_at);
-		k_morton_keys<<<block_count(T), kBlock, 0, stream>>>(args);
+		k_morton_keys<<<block_count(T, kBlock), kBlock, 0, stream>>>(args);
 		failed = hip_failed(hipGetLastError(), "making the Morton keys")
 			|| hip_failed(hipcub::DeviceRadixSort::SortKeys((uint8_t*) temporaries + sort_storage_at, sort_bytes, (const uint64_t*) args.keys, sorted_keys, (int) T, 0, 62, stream), "sorting the triangles");
 		args.sorted_keys = sorted_keys;
 	}
 	if (!failed) {
-		k_write_triangles<<<block_count(T), kBlock, 0, stream>>>(args);
+		k_write_triangles<<<block_count(T, kBlock), kBlock, 0, stream>>>(args);
 		failed = hip_failed(hipGetLastError(), "writing the triangles");
 		(void) hipEventRecord(kernels_end, stream);
 	}

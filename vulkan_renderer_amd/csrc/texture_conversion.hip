@@ -8,15 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "glibc_math.h"
 
-static int hip_failed(hipError_t error, const char* what) {
-	if (error == hipSuccess) return 0;
-	printf("HIP error while %s: %s\n", what, hipGetErrorString(error));
-	return 1;
-}
-
 constexpr uint32_t kBlock = 64;
-
-static inline uint32_t block_count(uint64_t lanes) { return (uint32_t) ((lanes + kBlock - 1) / kBlock); }
 
 // ---- linear image and mip chain --------------------------------------------------------------------------------------
 
@@ -480,7 +472,7 @@ extern "C" int convert_texture(converted_texture_t* out, const device_t* device,
 		args.source = source; args.tables = (const float*) parameters; args.linear = (float*) floats;
 		args.lane_count = (uint64_t) width * height * channels;
 		args.source_channels = channel_count; args.channels = channels; args.source_is_float = is_float; args.srgb = is_srgb;
-		k_linearise<<<block_count(args.lane_count), kBlock, 0, stream>>>(args);
+		k_linearise<<<block_count(args.lane_count, kBlock), kBlock, 0, stream>>>(args);
 		failed = hip_failed(hipGetLastError(), "making the linear image");
 	}
 	// the highest levels first: they are a few lanes with the longest chains
@@ -490,7 +482,7 @@ extern "C" int convert_texture(converted_texture_t* out, const device_t* device,
 		args.lane_count = (width >> i) * (height >> i) * channels;
 		args.width = width; args.height = height; args.channels = channels;
 		args.shift = i; args.log2_level_width = log2_of(width >> i); args.extent = get_texture_filter_weights(NULL, 0, i);
-		k_filter_level<<<block_count(args.lane_count), kBlock, sizeof(float) * 2 * args.extent, stream>>>(args);
+		k_filter_level<<<block_count(args.lane_count, kBlock), kBlock, sizeof(float) * 2 * args.extent, stream>>>(args);
 		failed = hip_failed(hipGetLastError(), "filtering a mip level");
 	}
 	for (uint32_t i = 0; i != level_count && !failed; ++i) {
@@ -502,13 +494,13 @@ extern "C" int convert_texture(converted_texture_t* out, const device_t* device,
 			args.level = level; args.payload = target;
 			args.lane_count = (level_width / 4) * (level_height / 4) * (channels == 2 ? 2u : 1u);
 			args.log2_blocks_x = log2_of(level_width / 4); args.level_width = level_width; args.srgb = is_srgb;
-			if (channels == 2) k_encode_bc4<<<block_count(args.lane_count), kBlock, 0, stream>>>(args);
-			else k_encode_bc1<<<block_count(args.lane_count), kBlock, 0, stream>>>(args);
+			if (channels == 2) k_encode_bc4<<<block_count(args.lane_count, kBlock), kBlock, 0, stream>>>(args);
+			else k_encode_bc1<<<block_count(args.lane_count, kBlock), kBlock, 0, stream>>>(args);
 		}
 		else {
 			pack_args args;
 			args.level = level; args.payload = target; args.texel_count = level_width * level_height; args.channels = channels; args.format = vk_format;
-			k_pack_level<<<block_count(args.texel_count), kBlock, 0, stream>>>(args);
+			k_pack_level<<<block_count(args.texel_count, kBlock), kBlock, 0, stream>>>(args);
 		}
 		failed = hip_failed(hipGetLastError(), "encoding a mip level");
 	}
