@@ -215,6 +215,18 @@ class ExportedScene(C.Structure):
                 ("material_indices", C.POINTER(C.c_uint8))]
 
 
+class Ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("direction", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [("primitive", C.c_uint32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float)]
+
+
+class RayQueryOptions(C.Structure):
+    _fields_ = [("walk", C.c_uint32), ("lds_stack_entries", C.c_uint32)]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -339,6 +351,8 @@ SIGNATURES = {
     "evaluate_texture_conversion_powf": (None, [P(C.c_float), P(C.c_float), C.c_float, C.c_uint64]),
     "get_texture_conversion_tables": (None, [P(C.c_float)]),
     "get_texture_filter_weights": (C.c_uint32, [P(C.c_float), C.c_uint32, C.c_uint32]),
+    "trace_closest_hits": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, P(RayQueryOptions), C.c_void_p]),
+    "trace_any_hits": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_uint64, C.c_void_p, P(RayQueryOptions), C.c_void_p]),
 }
 
 _lib = None

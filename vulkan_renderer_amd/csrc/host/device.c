@@ -73,6 +73,7 @@ int create_hip_device(device_t* device, int32_t hip_device, void* existing_strea
 }
 
 void destroy_hip_device(device_t* device) {
+	vkr_free_ray_query_buffers(device->hip_device);
 	for (int i = 0; i != VKR_MAX_FRAMES_IN_FLIGHT; ++i)
 		if (device->frame_streams[i]) {
 			(void) hipStreamSynchronize((hipStream_t) device->frame_streams[i]);

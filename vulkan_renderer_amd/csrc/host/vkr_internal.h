@@ -30,6 +30,8 @@ int vkr_host_alloc_pinned(void** out, size_t size);
 int vkr_launch_empty_kernel(void* stream);
 /* fills the per-device tables of the kernels (sRGB code thresholds) and waits for it (output_encoding.hip) */
 int vkr_fill_device_tables(void* stream);
+/* ray_queries.hip: frees the stack buffer that the wide ray queries keep per HIP device (destroy_hip_device() calls it) */
+void vkr_free_ray_query_buffers(int32_t hip_device);
 void vkr_host_free_pinned(void* pointer);
 int vkr_copy_to_device_async(void* device_pointer, const void* host, size_t size, const device_t* device);
 int vkr_copy_to_host(void* host, const void* device_pointer, size_t size, const device_t* device);

@@ -607,6 +607,86 @@ class Renderer(HostScene):
             raise RuntimeError("read_back_visibility failed")
         return out
 
+    # -- ray queries (include/vkr_ray_queries.h) ------------------------------------------
+    def _trace(self, closest, origins, directions, t_min, t_max, cull_back_faces, walk, lds_stack_entries, rays_pointer, out_pointer, count, stream):
+        """Both ray queries.  Host arrays are uploaded and the answers read back (a blocking call); with rays_pointer and
+        out_pointer - device memory of `count` records - nothing is copied and the call returns once it is enqueued."""
+        from . import ray_queries
+        hip = C.CDLL("libamdhip64.so")
+        # (an int, a ctypes pointer or None: the address, None for the device's stream)
+        stream = C.cast(stream, C.c_void_p).value if isinstance(stream, (C._SimpleCData, C._Pointer)) else (int(stream) if stream else None)
+        waited_for = C.c_void_p(stream or self.app.device.stream)
+        options = capi.RayQueryOptions(_enum(ray_queries.WALK, walk), int(lds_stack_entries))
+        record = ray_queries.HIT if closest else np.dtype(np.uint8)
+        owned = []
+
+        def allocate(nbytes):
+            pointer = C.c_void_p()
+            if hip.hipMalloc(C.byref(pointer), C.c_size_t(max(nbytes, 1))):
+                raise RuntimeError("out of device memory for %d bytes of a ray query" % nbytes)
+            owned.append(pointer)
+            return pointer
+
+        try:
+            if rays_pointer is None:
+                rays = ray_queries.make_rays(origins, directions, t_min, t_max)
+                count = len(rays)
+                rays_pointer = allocate(rays.nbytes)
+                if count and hip.hipMemcpy(rays_pointer, C.c_void_p(rays.ctypes.data), C.c_size_t(rays.nbytes), 1):
+                    raise RuntimeError("uploading the rays failed")
+            elif count is None:
+                raise ValueError("rays_pointer needs count")
+            read_back = out_pointer is None
+            if read_back:
+                out_pointer = allocate(record.itemsize * count)
+            scene, device = C.byref(self.app.scene), self._dev()
+            if closest:
+                failed = self.lib.trace_closest_hits(scene, device, rays_pointer, count, int(bool(cull_back_faces)), out_pointer, C.byref(options), stream)
+            else:
+                failed = self.lib.trace_any_hits(scene, device, rays_pointer, count, out_pointer, C.byref(options), stream)
+            if failed:
+                raise RuntimeError("%s failed" % ("trace_closest_hits" if closest else "trace_any_hits"))
+            if not read_back:
+                return None
+            out = np.zeros(count, record)
+            # (hipMemcpy does not wait for a non-blocking stream)
+            if hip.hipStreamSynchronize(waited_for) or (count and hip.hipMemcpy(C.c_void_p(out.ctypes.data), out_pointer, C.c_size_t(out.nbytes), 2)):
+                raise RuntimeError("reading the answers of the ray query back failed")
+            return out if closest else out.astype(bool)
+        finally:
+            if owned:
+                hip.hipStreamSynchronize(waited_for)
+            for pointer in owned:
+                hip.hipFree(pointer)
+
+    def trace_closest_hits(self, origins=None, directions=None, t_min=1.0e-3, t_max=np.inf, cull_back_faces=False, walk="auto", rays_pointer=None, hits_pointer=None, count=None, lds_stack_entries=0, stream=None):
+        """The closest hit of every ray o + t d, t in [t_min, t_max], with the triangles of the loaded scene
+        (include/vkr_ray_queries.h trace_closest_hits): a structured array of ray_queries.HIT - primitive (0xFFFFFFFF:
+        none), t, u, v.  origins, directions: (n, 3); t_min, t_max: scalars or (n,).  rays_pointer, hits_pointer: device
+        memory of `count` ray_t / ray_hit_t instead of the arrays / the return value; stream: a hipStream_t instead of
+        the device's."""
+        return self._trace(True, origins, directions, t_min, t_max, cull_back_faces, walk, lds_stack_entries, rays_pointer, hits_pointer, count, stream)
+
+    def trace_any_hits(self, origins=None, directions=None, t_min=1.0e-3, t_max=np.inf, walk="auto", rays_pointer=None, blocked_pointer=None, count=None, lds_stack_entries=0, stream=None):
+        """Whether anything blocks the segments t in [t_min, t_max] of the rays (trace_any_hits): a bool array; the
+        arguments of trace_closest_hits(), blocked_pointer one byte per ray"""
+        return self._trace(False, origins, directions, t_min, t_max, False, walk, lds_stack_entries, rays_pointer, blocked_pointer, count, stream)
+
+    def pixel_rays(self):
+        """The pixel-centre rays of the current camera and extent, raster order, as ray_queries.RAY records: what
+        render_visibility_pass() traces, built from the same bytes of the constant buffer"""
+        from . import ray_queries
+        e, camera = self.app.swapchain.extent, self.app.scene_specification.camera
+        return ray_queries.pixel_rays(self.constants(), e.width, e.height, camera.near, camera.far)
+
+    def pick(self, x, y):
+        """The front-facing triangle under the centre of pixel (x, y): one ray_queries.HIT record"""
+        e = self.app.swapchain.extent
+        if not (0 <= x < e.width and 0 <= y < e.height):
+            raise ValueError("pixel (%d, %d) is outside the %d x %d frame" % (x, y, e.width, e.height))
+        ray = self.pixel_rays()[y * e.width + x:y * e.width + x + 1]
+        return self.trace_closest_hits(ray["origin"], ray["direction"], ray["t_min"], ray["t_max"], cull_back_faces=True)[0]
+
     def read_encoded(self, output_linear_rgb=False, frame_bits=0):
         e = self.app.swapchain.extent
         self.app.screenshot.frame_bits = frame_bits
