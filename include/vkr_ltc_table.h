@@ -23,6 +23,10 @@ typedef struct ltc_table_s {
 	void* device_rgba;
 	void* device_rg;
 	ltc_constants_t constants;
+	/*! which upload of the process this is (1, 2, ...; 0 without a device): two tables with the same serial hold the same
+		texels on the device, even when a later one was uploaded into the allocations that an earlier one has freed.  What
+		the shading pass keeps from frame to frame because the table has not changed is tied to it. */
+	uint32_t upload_serial;
 } ltc_table_t;
 
 /*! reference ltc_table.h:69 / ltc_table.c:23-194: reads <directory>/fit<i>.dat for

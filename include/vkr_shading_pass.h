@@ -430,6 +430,14 @@ VKR_API int get_light_shaft_statistics(application_t* app, uint64_t out_statisti
 	reasons above; with 20 (triangles in the way) bits 8 ... 31 name one such triangle (its index in the mesh, if below
 	2^24).  Returns the number of words written. */
 VKR_API uint64_t read_back_light_shafts(application_t* app, uint32_t* out_words, uint64_t capacity);
+/*! Prepared polygons kept while the inputs of the launches stand still: {how the most recent launch got
+	its prepared polygons - 0 plain: it prepared them itself, 1 storing: it also wrote them to device memory, 2 loading:
+	it read them from there -, bytes of the buffer that holds them (0: none allocated), launches of the pass so far that
+	ran plain, storing, loading, launches that ran plain only because the storing launch, on another stream, had not
+	completed yet, state
+	(0 nothing stored, 1 being stored, 2 stored), the budget in MiB (environment VKR_PREPARED_POLYGONS_MIB, 0: off)}.
+	0 on success, 1 (all zero) before the first frame with wavefront rays. */
+VKR_API int get_prepared_polygon_statistics(application_t* app, uint64_t out_statistics[8]);
 /*! (diagnostics, only with VKR_SHAFT_COUNTERS=1 in the environment) work of the shaft kernel of the most recent
 	launch: {steps of its walks (16 nodes each), batches of triangles, walks}.  0 on success. */
 VKR_API int get_light_shaft_work(application_t* app, uint64_t out_work[3]);

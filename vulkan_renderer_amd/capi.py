@@ -45,7 +45,7 @@ class LtcConstants(C.Structure):
 class LtcTable(C.Structure):
     _fields_ = [("roughness_count", C.c_uint32), ("inclination_count", C.c_uint32), ("fresnel_count", C.c_uint32),
                 ("host_rgba", C.POINTER(C.c_uint16)), ("host_rg", C.POINTER(C.c_uint16)),
-                ("device_rgba", C.c_void_p), ("device_rg", C.c_void_p), ("constants", LtcConstants)]
+                ("device_rgba", C.c_void_p), ("device_rg", C.c_void_p), ("constants", LtcConstants), ("upload_serial", C.c_uint32)]
 
 
 class LtcFitSettings(C.Structure):
@@ -301,6 +301,7 @@ SIGNATURES = {
     "get_light_shaft_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),
     "read_back_light_shafts": (C.c_uint64, [P(Application), C.c_void_p, C.c_uint64]),
     "get_light_shaft_work": (C.c_int, [P(Application), P(C.c_uint64)]),
+    "get_prepared_polygon_statistics": (C.c_int, [P(Application), P(C.c_uint64)]),
     "get_dispatch_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),
     "get_shading_kernel_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),
     "get_frame_period_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),

@@ -52,6 +52,8 @@ int vkr_fill_ltc_table(ltc_table_t* table, const device_t* device, const float* 
 			destroy_ltc_table(table, device);
 			return 1;
 		}
+		static uint32_t uploads = 0;
+		table->upload_serial = __atomic_add_fetch(&uploads, 1u, __ATOMIC_RELAXED);
 	}
 	/* lookup constants, ltc_table.c:184-191 */
 	table->constants.fresnel_index_factor = (float) (table->fresnel_count - 1);

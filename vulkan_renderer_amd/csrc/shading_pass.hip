@@ -15,6 +15,9 @@ static const launch_function_t g_launchers[6][5] = {
 	VKR_LAUNCHER_ROW(libm), VKR_LAUNCHER_ROW(fast), VKR_LAUNCHER_ROW(exact),
 	VKR_LAUNCHER_ROW(textured_libm), VKR_LAUNCHER_ROW(textured_fast), VKR_LAUNCHER_ROW(textured_exact),
 };
+// [arithmetic_mode_t][strategy - kStrategySeparately]: the kernels with kept prepared polygons; none in the fast mode
+#define VKR_PREPARED_ROW(mode) {vkr_launch_shade_prepared_##mode##_2, vkr_launch_shade_prepared_##mode##_3, vkr_launch_shade_prepared_##mode##_4}
+static const prepared_launch_function_t g_prepared_launchers[3][3] = {VKR_PREPARED_ROW(libm), {NULL, NULL, NULL}, VKR_PREPARED_ROW(exact)};
 static const error_launch_function_t g_error_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_error_display);
 static const resolve_launch_function_t g_resolve_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_resolve_materials);
 
@@ -118,6 +121,30 @@ static void free_wavefront_buffers(wavefront_buffers* w) {
 	memset(w, 0, sizeof(*w));
 }
 
+// The prepared polygons of the most recent launches (shading_kernel.h "Prepared polygons that are still true")
+enum { kCacheEmpty = 0, kCachePending = 1, kCacheValid = 2 };
+struct prepared_cache {
+	uint4* buffer;  // the second argument of the storing and the loading kernel, allocated when a launch first stores
+	size_t buffer_quads;
+	// a byte image of everything the preparation reads (prepared_arrangement below), of the most recent launch that the
+	// cache could serve: seen_size bytes, 0: none
+	uint8_t* seen;
+	size_t seen_size, seen_capacity;
+	uint8_t* scratch;
+	size_t scratch_capacity;
+	// kCachePending: a storing launch with the inputs in `seen` has been submitted and `stored` recorded behind it;
+	// kCacheValid: that event has been seen complete - launches with these inputs load
+	uint32_t state;
+	hipEvent_t stored;
+	hipStream_t stored_stream;  // the stream of that storing launch
+	// VKR_PREPARED_POLYGONS_MIB: the largest buffer that is allocated (0: no launch stores or loads)
+	uint32_t budget_mib;
+	// for get_prepared_polygon_statistics(): the mode of the last launch, launches per mode, launches that ran plain because
+	// the storing launch had not completed yet
+	uint32_t last_mode;
+	uint64_t launches[3], waited;
+};
+
 // What a frame in flight owns.  With frames_in_flight = n >= 2 consecutive frames take turns
 // on n contexts (and n of the device's frame streams); otherwise only context 0 is used, on
 // device->stream.
@@ -151,6 +178,9 @@ struct frame_pipeline {
 	// the polygon tables in device memory (wavefront_buffers::psa_table_memory) of the frames without wavefront rays, which
 	// own no context
 	wavefront_buffers device_stream_buffers;
+	// the prepared polygons that the shading kernel keeps while its inputs stand still ("prepared polygon cache" below): one
+	// per pass, not per frame context - it is read-only while it is valid
+	prepared_cache prepared;
 	uint32_t next;            // context of the next pipelined frame
 	uint32_t last;            // context of the most recent frame
 	uint32_t depth;           // frames in flight of the most recent pipelined frame
@@ -189,6 +219,10 @@ static void destroy_wavefront(shading_pass_t* pass) {
 	if (frames->inputs_ready) (void) hipEventDestroy(frames->inputs_ready);
 	if (frames->readers_done) (void) hipEventDestroy(frames->readers_done);
 	free(frames->shaft_scratch);
+	(void) hipFree(frames->prepared.buffer);
+	if (frames->prepared.stored) (void) hipEventDestroy(frames->prepared.stored);
+	free(frames->prepared.seen);
+	free(frames->prepared.scratch);
 	free(frames);
 	pass->wavefront = NULL;
 }
@@ -199,7 +233,8 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 	frames = (frame_pipeline*) calloc(1, sizeof(frame_pipeline));
 	pass->wavefront = frames;
 	bool failed = !frames || hipEventCreateWithFlags(&frames->inputs_ready, kSyncEventFlags) != hipSuccess
-		|| hipEventCreateWithFlags(&frames->readers_done, kSyncEventFlags) != hipSuccess;
+		|| hipEventCreateWithFlags(&frames->readers_done, kSyncEventFlags) != hipSuccess
+		|| hipEventCreateWithFlags(&frames->prepared.stored, kSyncEventFlags) != hipSuccess;
 	for (int i = 0; i != VKR_MAX_FRAMES_IN_FLIGHT && !failed; ++i) failed = hipEventCreateWithFlags(&frames->contexts[i].done, kSyncEventFlags) != hipSuccess;
 	if (failed) {
 		printf("Failed to create the events of the frame pipeline.\n");
@@ -224,6 +259,9 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 	frames->wide_refill_below = environment_knob("VKR_WIDE_REFILL_BELOW", kWideRefillBelow, 0u, 256u);
 	frames->wavefront_budget_mib = environment_knob("VKR_WAVEFRONT_BUDGET_MIB", 36864u, 64u, 262144u);
 	frames->band_count = environment_knob("VKR_BAND_COUNT", 0u, 0u, 4096u);
+	// VKR_PREPARED_POLYGONS_MIB: most device memory that the kept prepared polygons of a launch may take; 0: nothing is kept,
+	// every launch prepares its polygons itself.  (Config 3 at 1920x1080 keeps 2 040 MiB: 2.09 M threads x 4 lights x 256 B.)
+	frames->prepared.budget_mib = environment_knob("VKR_PREPARED_POLYGONS_MIB", 4096u, 0u, 262144u);
 	return frames;
 }
 
@@ -824,6 +862,13 @@ struct frame_plan {
 	shade_params p;          // the parameters of every launch of the frame; a band step adds the band's blocks and buffers
 	frame_pipeline* frames;  // NULL for a frame without wavefront rays, unless its polygon tables live in device memory
 	int strategy, technique, capacity, error_mode, ray_mode;
+	// how the launch gets its prepared polygons (kPreparedPlain / kPreparedStoring / kPreparedLoading, choose_prepared_mode()) and
+	// the buffer of the other two than plain
+	int prepared_mode;
+	uint4* prepared;
+	// quads (16 B) of the buffer that the prepared polygons of the frame's one launch may take: plan_bands() has found room for
+	// them in the budgets; 0: this frame keeps none
+	size_t prepared_quads;
 	// (table_in_memory: the kernel variants that keep one of their two polygon tables in device memory, shading_kernel.h psa_table_in_memory)
 	bool table_in_memory, hidden_terms, base_color, use_wide_tree, textured, pipelined;
 	uint32_t grid_blocks, table_bytes_per_workgroup, max_terms;
@@ -944,6 +989,15 @@ static int plan_frame(application_t* app, void* out_radiance, frame_plan* f) {
 	return 0;
 }
 
+// Which launches can keep prepared polygons at all ("prepared polygon cache" below): the kernel variants of
+// prepared_polygons_apply() (shading_kernel.h), untextured.  plan_bands() adds: one launch per frame, and room in the budgets.
+static bool prepared_polygons_possible(const application_t* app, const frame_plan* f) {
+	return f->ray_mode == kRaysDeferredBlocks && f->error_mode == kErrorNone && !f->table_in_memory && !f->textured
+		&& !f->p.light_texture_descriptors && app->shading_pass.arithmetic_mode != arithmetic_mode_fast && f->p.light_count != 0
+		&& (f->technique == kTechniquePsa || f->technique == kTechniquePsaBiased) && f->strategy >= kStrategySeparately && f->strategy <= kStrategyRandom
+		&& f->capacity >= 4 && f->capacity <= 5;
+}
+
 // Launches with wavefront rays may run n at a time: launch k on frame stream k mod n with
 // its own buffers, so that the (latency-bound) tracing of one launch overlaps the
 // (VALU-bound) shading of the next ones.  Everything else runs on device->stream, behind
@@ -998,6 +1052,19 @@ static int plan_bands(application_t* app, frame_plan* f) {
 	f->trace_blocks = (f->trace_blocks + 7u) & ~7u;
 	f->p.ray_block = f->ray_mode == kRaysDeferredBlocks ? ray_block_size(f->max_terms) : 0u;
 	f->p.refill_threshold = kRefillThreshold;
+	// The prepared polygons of a frame that is one launch (a frame in bands meets a context's buffers with another band each
+	// time, and config 4, the frame that is rendered in bands, has no such kernel variant): one buffer per pass, counted against
+	// the budget of the wavefront buffers like the shafts' tables, and against VKR_PREPARED_POLYGONS_MIB.  (bind_textures() runs
+	// after this: a frame with light textures is turned away by choose_prepared_mode().)
+	f->prepared_quads = 0;
+	if (f->band_count == 1 && frames->prepared.budget_mib != 0u && prepared_polygons_possible(app, f)) {
+		const uint32_t thread_count = f->blocks_per_band * 256u;
+		const size_t quads = (size_t) thread_count * f->p.light_count * (prepared_bytes_per_pair(f->capacity) / 16u);
+		const double bytes = 16.0 * (double) quads;
+		if (bytes <= (double) frames->prepared.budget_mib * 1048576.0
+			&& f->depth * wavefront_bytes(thread_count, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, 0u) + bytes <= budget)
+			f->prepared_quads = quads;
+	}
 	return 0;
 }
 
@@ -1254,12 +1321,152 @@ static int run_light_shafts(application_t* app, frame_plan* f, frame_context* fr
 	return 0;
 }
 
+// ---- prepared polygon cache ------------------------------------------------------------------
+// Everything the preparation of a launch reads, as bytes: this struct and behind it the constants of the launch - camera,
+// de-quantisation, roughness factor, the LTC table's lookup constants and every light's record - with the four noise
+// words blanked, which only the samples read.  (The constants hold more than the preparation reads - exposure, the MIS
+// visibility estimate: a change of those costs one plain and one storing launch and nothing else.)
+// What lies behind the pointers is named by inputs_generation (visibility buffer, mark_inputs_changed()), the tree's
+// build_serial (mesh and materials are uploaded with it, load_scene()) and the LTC table's upload_serial.
+struct prepared_arrangement {
+	uint32_t first_block, block_count, thread_count, width, height, tile_size, rank, rank_count, tiles_x, tile_count, slab_layout;
+	uint32_t light_count, max_light_vertex_count, strategy, technique, capacity, arithmetic_mode;
+	uint32_t inputs_generation, build_serial, ltc_serial, ltc_resolution, ltc_layer_count;
+	const void *visibility, *positions, *normals_and_tex_coords, *material_indices, *material_constants, *ltc_rgba, *ltc_rg;
+};
+static_assert(sizeof(prepared_arrangement) == 22 * 4 + 7 * sizeof(void*), "no padding: the struct is compared as bytes");
+
+static void forget_prepared_polygons(frame_pipeline* frames) {
+	if (!frames) return;
+	frames->prepared.state = kCacheEmpty;
+	frames->prepared.seen_size = 0;
+}
+
+// ... and gives the buffer back: for a launch that cannot keep prepared polygons at all (another kernel variant, a frame in
+// bands, no room in the budgets).  A launch whose inputs merely differ from the last one's keeps the buffer - a camera that
+// moves and stops would free and allocate 2 GB each time.  (hipFree waits for the device: no launch still loads from it.)
+static void release_prepared_polygons(frame_pipeline* frames) {
+	forget_prepared_polygons(frames);
+	if (!frames || !frames->prepared.buffer) return;
+	(void) hipFree(frames->prepared.buffer);
+	frames->prepared.buffer = NULL;
+	frames->prepared.buffer_quads = 0;
+}
+
+// Band step 4b: decides how this launch gets its prepared polygons -> f->prepared_mode, f->prepared
+//   loading  when the cache holds the polygons of exactly these inputs and the launch that stored them has completed (the
+//            event is queried, never waited for: until it completes, launches run plain) or runs on this launch's stream
+//   storing  when the inputs are those of the launch before and nothing is stored or being stored
+//   plain    otherwise - a moving frame pays a memcmp that fails early
+static int choose_prepared_mode(application_t* app, frame_plan* f, frame_context* frame, hipStream_t stream) {
+	const shade_params& p = f->p;
+	f->prepared_mode = kPreparedPlain;
+	f->prepared = NULL;
+	frame_pipeline* frames = f->frames;
+	if (!frames) return 0;
+	prepared_cache* cache = &frames->prepared;
+	cache->last_mode = kPreparedPlain;
+	if (!frame || f->prepared_quads == 0 || !prepared_polygons_possible(app, f)) {
+		release_prepared_polygons(frames);
+		++cache->launches[kPreparedPlain];
+		return 0;
+	}
+	const shading_pass_t* pass = &app->shading_pass;
+	prepared_arrangement arrangement;
+	memset(&arrangement, 0, sizeof(arrangement));
+	arrangement.first_block = p.first_block; arrangement.block_count = p.block_count; arrangement.thread_count = p.thread_count;
+	arrangement.width = p.width; arrangement.height = p.height;
+	arrangement.tile_size = p.tile_size; arrangement.rank = p.rank; arrangement.rank_count = p.rank_count;
+	arrangement.tiles_x = p.tiles_x; arrangement.tile_count = p.tile_count; arrangement.slab_layout = p.slab_layout;
+	arrangement.light_count = p.light_count; arrangement.max_light_vertex_count = p.max_light_vertex_count;
+	arrangement.strategy = (uint32_t) f->strategy; arrangement.technique = (uint32_t) f->technique; arrangement.capacity = (uint32_t) f->capacity;
+	arrangement.arithmetic_mode = (uint32_t) pass->arithmetic_mode;
+	arrangement.inputs_generation = frames->inputs_generation;
+	arrangement.build_serial = app->scene.acceleration_structure.build_serial;
+	arrangement.ltc_serial = app->ltc_table.upload_serial;
+	arrangement.ltc_resolution = p.ltc_resolution; arrangement.ltc_layer_count = p.ltc_layer_count;
+	arrangement.visibility = p.visibility; arrangement.positions = p.positions; arrangement.normals_and_tex_coords = p.normals_and_tex_coords;
+	arrangement.material_indices = p.material_indices; arrangement.material_constants = p.material_constants;
+	arrangement.ltc_rgba = p.ltc_rgba; arrangement.ltc_rg = p.ltc_rg;
+	const size_t size = sizeof(arrangement) + pass->constants_size;
+	if (grow_bytes(&cache->scratch, &cache->scratch_capacity, size) || grow_bytes(&cache->seen, &cache->seen_capacity, size)) {
+		printf("Failed to allocate %zu bytes for the inputs of the prepared polygons.\n", size);
+		forget_prepared_polygons(frames);
+		return 1;
+	}
+	uint8_t* now = cache->scratch;
+	memcpy(now, &arrangement, sizeof(arrangement));
+	memcpy(now + sizeof(arrangement), pass->constants_host, pass->constants_size);
+	memset(now + sizeof(arrangement) + offsetof(per_frame_constants_t, noise_random_numbers), 0, sizeof(((per_frame_constants_t*) NULL)->noise_random_numbers));
+	if (cache->seen_size != size || memcmp(now, cache->seen, size) != 0) {
+		// other inputs: whatever is stored, or being stored, is of no use to anybody any more
+		memcpy(cache->seen, now, size);
+		cache->seen_size = size;
+		cache->state = kCacheEmpty;
+		++cache->launches[kPreparedPlain];
+		return 0;
+	}
+	if (cache->state == kCachePending) {
+		hipError_t stored = hipEventQuery(cache->stored);
+		if (stored == hipSuccess) cache->state = kCacheValid;
+		else {
+			// (hipErrorNotReady is an answer, not an error: it must not meet the launch checks below)
+			(void) hipGetLastError();
+			// A launch on the stream of the storing launch runs behind it whatever the event says - the stream is in order -,
+			// so it loads: frames that are submitted in a burst on ONE stream (frames_in_flight <= 1) load from the third on
+			// instead of running plain until somebody waits.  Other streams are never made to wait for the storing launch.
+			if (stream != cache->stored_stream) ++cache->waited;
+		}
+	}
+	if (cache->state == kCacheValid || (cache->state == kCachePending && stream == cache->stored_stream)) {
+		f->prepared_mode = cache->last_mode = kPreparedLoading;
+		f->prepared = cache->buffer;
+	}
+	else if (cache->state == kCacheEmpty) {
+		// (plan_bands() has found room for the buffer.  One of another size goes first: freeing waits for the device, so no launch
+		// still loads from it, and the bytes that the statistics report are those of this arrangement.)
+		if (cache->buffer && cache->buffer_quads != f->prepared_quads) {
+			(void) hipFree(cache->buffer);
+			cache->buffer = NULL;
+			cache->buffer_quads = 0;
+		}
+		if (grow_device_buffer(&cache->buffer, &cache->buffer_quads, f->prepared_quads, sizeof(uint4), "Failed to allocate %.1f MiB for the prepared polygons.\n")) return 1;
+		// launches in flight on other streams may still load what an earlier arrangement stored here.  (A launch outside the
+		// pipeline runs behind finish_frames(), join_frame_pipeline(): it waits for events that it is behind already.)
+		for (uint32_t c = 0; c != VKR_MAX_FRAMES_IN_FLIGHT; ++c) {
+			frame_context* other = &frames->contexts[c];
+			if (other != frame && other->recorded) (void) hipStreamWaitEvent(stream, other->done, 0);
+		}
+		f->prepared_mode = cache->last_mode = kPreparedStoring;
+		f->prepared = cache->buffer;
+	}
+	++cache->launches[f->prepared_mode];
+	return 0;
+}
+
+// ... and behind the launch: the event of a storing launch, or nothing kept after a launch that failed
+static void note_prepared_launch(frame_plan* f, int status, hipStream_t stream) {
+	frame_pipeline* frames = f->frames;
+	if (!frames) return;
+	if (status != 0) forget_prepared_polygons(frames);
+	else if (f->prepared_mode == kPreparedStoring) {
+		frames->prepared.stored_stream = stream;
+		if (hipEventRecord(frames->prepared.stored, stream) == hipSuccess) frames->prepared.state = kCachePending;
+		else forget_prepared_polygons(frames);
+	}
+}
+
 // Band step 5: the shading kernel, or the error display's; < 0: no such kernel variant was built
 static int launch_shading(const application_t* app, const frame_plan* f, hipStream_t stream) {
 	const int mode = app->shading_pass.arithmetic_mode;
 	const shade_params* p = &f->p;
 	if (f->error_mode != kErrorNone)
 		return g_error_launchers[mode](has_specular_technique(&app->render_settings), f->technique, f->capacity, f->error_mode, p, p->block_count, stream);
+	if (f->prepared_mode != kPreparedPlain) {
+		// (a variant that prepared_polygons_possible() promises and the library lacks is an error, not a reason to run plain)
+		const prepared_launch_function_t launch = g_prepared_launchers[mode][f->strategy - kStrategySeparately];
+		return launch ? launch(f->technique, f->capacity, f->prepared_mode, f->prepared, p, p->block_count, stream) : -1;
+	}
 	return g_launchers[mode + (p->light_texture_descriptors ? 3 : 0)][f->strategy](f->technique, f->capacity, f->ray_mode, p, p->block_count, stream);
 }
 
@@ -1368,7 +1575,9 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 		if (!is_deferred(f.ray_mode)) order_output_write(pass, &f, frame, band, stream);
 		// (the second event of a timed frame: the shading kernel itself begins here, behind the shaft kernel)
 		if (timed && band == 0) (void) hipEventRecord(timing_event(pass, slot, kTimingShadingStart), stream);
+		if (choose_prepared_mode(app, &f, frame, stream)) return 1;
 		status = launch_shading(app, &f, stream);
+		note_prepared_launch(&f, status, stream);
 		if (timed && band + 1 == f.band_count) (void) hipEventRecord(timing_event(pass, slot, kTimingShadingEnd), stream);
 		if (status == 0 && is_deferred(f.ray_mode)) {
 			launch_tracing(app, &f, frame, stream);
@@ -1658,6 +1867,22 @@ extern "C" int get_light_shaft_statistics(application_t* app, uint64_t out_stati
 	out_statistics[10] = counts[7];
 	out_statistics[11] = counts[8];
 	return failed;
+}
+
+// {mode of the last launch, bytes of the buffer, launches plain / storing / loading, launches that found the storing one
+// incomplete, state, budget in MiB} of the prepared polygon cache (include/vkr_shading_pass.h)
+extern "C" int get_prepared_polygon_statistics(application_t* app, uint64_t out_statistics[8]) {
+	memset(out_statistics, 0, 8 * sizeof(uint64_t));
+	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
+	if (!frames) return 1;
+	const prepared_cache* cache = &frames->prepared;
+	out_statistics[0] = cache->last_mode;
+	out_statistics[1] = (uint64_t) cache->buffer_quads * sizeof(uint4);
+	for (int i = 0; i != 3; ++i) out_statistics[2 + i] = cache->launches[i];
+	out_statistics[5] = cache->waited;
+	out_statistics[6] = cache->state;
+	out_statistics[7] = cache->budget_mib;
+	return 0;
 }
 
 // (diagnostics, VKR_SHAFT_COUNTERS=1) {steps, triangle batches, walks} of the most recent launch's shaft kernel

@@ -100,3 +100,33 @@ extern "C" int VKR_LAUNCH_NAME(int technique, int capacity, int rays, const shad
 	default: return -1;
 	}
 }
+
+// The same kernels with kept prepared polygons (shading_kernel.h "Prepared polygons that are still true"): the storing or
+// the loading instantiation, which exist where prepared_polygons_apply().  Same return values.
+#if VKR_STRATEGY >= 2 && !VKR_LIGHT_TEXTURES && !VKR_FAST_MATH
+#if VKR_MATH_MODE == 2
+#define VKR_PREPARED_LAUNCH_NAME VKR_CAT(vkr_launch_shade_prepared_libm_, VKR_STRATEGY, , )
+#else
+#define VKR_PREPARED_LAUNCH_NAME VKR_CAT(vkr_launch_shade_prepared_exact_, VKR_STRATEGY, , )
+#endif
+template <int TECHNIQUE, int V>
+static int launch_prepared(int prepared_mode, prepared_quad* prepared, const shade_params& p, unsigned int grid_x, hipStream_t stream) {
+	if constexpr (prepared_polygons_apply(VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE)) {
+		const dim3 grid(shade_grid_size(grid_x));
+		const uint32_t lds = shade_lds_bytes(VKR_STRATEGY, TECHNIQUE, V, VKR_MODE);
+		if (prepared_mode == kPreparedStoring) shade_pixels<VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE, kPreparedStoring><<<grid, kShadeThreads, lds, stream>>>(p, prepared);
+		else if (prepared_mode == kPreparedLoading) shade_pixels<VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE, kPreparedLoading><<<grid, kShadeThreads, lds, stream>>>(p, prepared);
+		else return -1;
+		return hipGetLastError() != hipSuccess;
+	}
+	else return -1;
+}
+
+extern "C" int VKR_PREPARED_LAUNCH_NAME(int technique, int capacity, int prepared_mode, void* prepared, const shade_params* p, unsigned int grid_x, void* stream) {
+	if (!prepared || (technique != kTechniquePsa && technique != kTechniquePsaBiased) || (capacity != 4 && capacity != 5)) return -1;
+	prepared_quad* buffer = (prepared_quad*) prepared;
+	hipStream_t s = (hipStream_t) stream;
+	if (technique == kTechniquePsa) return capacity == 4 ? launch_prepared<kTechniquePsa, 4>(prepared_mode, buffer, *p, grid_x, s) : launch_prepared<kTechniquePsa, 5>(prepared_mode, buffer, *p, grid_x, s);
+	return capacity == 4 ? launch_prepared<kTechniquePsaBiased, 4>(prepared_mode, buffer, *p, grid_x, s) : launch_prepared<kTechniquePsaBiased, 5>(prepared_mode, buffer, *p, grid_x, s);
+}
+#endif

@@ -487,6 +487,15 @@ class Renderer(HostScene):
                 # pairs whose rays the shading kernel decides against a handful of triangles, and those triangles
                 "list_pairs": int(out[10]), "listed_triangles": int(out[11])}
 
+    def prepared_polygon_statistics(self):
+        """How the last launch got its prepared polygons ("plain", "storing", "loading") and the state of the cache that
+        keeps them while the inputs stand still (include/vkr_shading_pass.h get_prepared_polygon_statistics)"""
+        out = (C.c_uint64 * 8)()
+        self.lib.get_prepared_polygon_statistics(C.byref(self.app), out)
+        return {"mode": ("plain", "storing", "loading")[int(out[0])], "buffer_bytes": int(out[1]),
+                "launches": {"plain": int(out[2]), "storing": int(out[3]), "loading": int(out[4])}, "waited": int(out[5]),
+                "state": ("empty", "pending", "valid")[int(out[6])], "budget_mib": int(out[7])}
+
     def light_shaft_words(self):
         """The verdict words of the last launch as a (patches, lights) uint32 array (include/vkr_shading_pass.h
         read_back_light_shafts); empty when that launch ran without the shaft test"""
