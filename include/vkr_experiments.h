@@ -88,4 +88,9 @@ VKR_API int write_hdr_rgb32f(const char* path, uint32_t width, uint32_t height, 
 	Either path may be NULL.  Returns 0 on success; prints the reason otherwise. */
 VKR_API int take_screenshot(application_t* app, const char* path_png, const char* path_hdr);
 
+/*! The *.jpg of implement_screenshot (reference main.c:1745-1752, stbi_write_jpg at quality 70): the sRGB-encoded LDR
+	frame that take_screenshot() gives path_png, encoded on the device (include/vkr_jpeg.h) and written to path_jpg.
+	path_jpg NULL does nothing.  Returns 0 on success; prints the reason otherwise. */
+VKR_API int take_jpg_screenshot(application_t* app, const char* path_jpg);
+
 #endif

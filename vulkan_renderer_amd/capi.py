@@ -227,6 +227,13 @@ class RayQueryOptions(C.Structure):
     _fields_ = [("walk", C.c_uint32), ("lds_stack_entries", C.c_uint32)]
 
 
+class JpegEncoder(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("quality", C.c_uint32), ("subsampled", C.c_uint32),
+                ("slot_count", C.c_uint32), ("data_unit_count", C.c_uint32), ("capacity", C.c_uint64), ("state", C.c_void_p)]
+
+
+JPEG_HEADER_SIZE = 607  # VKR_JPEG_HEADER_SIZE
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -354,6 +361,17 @@ SIGNATURES = {
     "get_texture_filter_weights": (C.c_uint32, [P(C.c_float), C.c_uint32, C.c_uint32]),
     "trace_closest_hits": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, P(RayQueryOptions), C.c_void_p]),
     "trace_any_hits": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_uint64, C.c_void_p, P(RayQueryOptions), C.c_void_p]),
+    "create_jpeg_encoder": (C.c_int, [P(JpegEncoder), P(Device), C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32]),
+    "destroy_jpeg_encoder": (None, [P(JpegEncoder)]),
+    "begin_jpeg_encode": (C.c_int, [P(JpegEncoder), C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "end_jpeg_encode": (C.c_int, [P(JpegEncoder), C.c_uint32, P(C.c_void_p), P(C.c_uint64)]),
+    "encode_jpeg": (C.c_int, [P(JpegEncoder), C.c_void_p, C.c_uint32, C.c_uint64, P(C.c_void_p), P(C.c_uint64)]),
+    "encode_jpeg_on_device": (C.c_int, [P(JpegEncoder), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "get_jpeg_capacity": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_int32]),
+    "get_jpeg_stuffing_chunk_size": (C.c_uint32, []),
+    "get_jpeg_header": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]),
+    "write_jpeg": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
+    "take_jpg_screenshot": (C.c_int, [P(Application), C.c_char_p]),
 }
 
 _lib = None

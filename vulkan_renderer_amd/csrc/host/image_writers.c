@@ -6,6 +6,7 @@
  * writer produces. */
 #include "vkr_internal.h"
 #include "vkr_experiments.h"
+#include "vkr_jpeg.h"
 
 /* ---- byte buffer ----------------------------------------------------------------- */
 
@@ -377,5 +378,23 @@ int take_screenshot(application_t* app, const char* path_png, const char* path_h
 	}
 	app->screenshot.frame_bits = frame_bits_before;
 	free(rgba); free(ldr); free(hdr);
+	return failed;
+}
+
+int take_jpg_screenshot(application_t* app, const char* path_jpg) {
+	if (!path_jpg) return 0;
+	uint32_t frame_bits_before = app->screenshot.frame_bits;
+	jpeg_encoder_t encoder;
+	const uint8_t* bytes = NULL;
+	uint64_t size = 0;
+	/* the LDR frame of take_screenshot(), straight from the device: alpha is ignored by the encoder (main.c:1745-1752) */
+	app->screenshot.frame_bits = 0;
+	int failed = create_jpeg_encoder(&encoder, &app->device, app->swapchain.extent.width, app->swapchain.extent.height, 70, 1);
+	if (!failed) {
+		failed = encode_output(app, VK_FALSE) || encode_jpeg(&encoder, app->render_targets.encoded, 4, 0, &bytes, &size) || write_jpeg(path_jpg, bytes, size);
+		destroy_jpeg_encoder(&encoder);
+	}
+	if (!failed) printf("Wrote screenshot to %s.\n", path_jpg);
+	app->screenshot.frame_bits = frame_bits_before;
 	return failed;
 }

@@ -707,6 +707,43 @@ class Renderer(HostScene):
         self.app.screenshot.frame_bits = 0
         return out
 
+    # -- JPEG files (include/vkr_jpeg.h) ---------------------------------------------------
+    def create_jpeg_encoder(self, width=None, height=None, quality=70, slot_count=1):
+        """An encoder for frames of one extent (default: the frame's) and quality with `slot_count` output slots: a
+        JpegEncoder, which exposes begin() and end() per slot.  The caller closes it (Renderer.close() closes what is left)."""
+        e = self.app.swapchain.extent
+        encoder = JpegEncoder(self, int(width or e.width), int(height or e.height), quality, slot_count)
+        self._jpeg_encoders = getattr(self, "_jpeg_encoders", []) + [encoder]
+        return encoder
+
+    def _cached_jpeg_encoder(self, width, height, quality):
+        cache = self.__dict__.setdefault("_jpeg_cache", {})
+        key = (int(width), int(height), int(quality))
+        if key not in cache or cache[key].closed:
+            cache[key] = self.create_jpeg_encoder(width, height, quality)
+        return cache[key]
+
+    def encode_jpeg(self, image_or_pointer, quality=70, width=None, height=None, channel_count=4, row_stride_bytes=0):
+        """The bytes of the JPEG file of an image - a uint8 array (height, width, 3 or 4), which is uploaded - or of
+        device memory (an address; width, height default to the frame's extent; channel_count 3 or 4, rows
+        row_stride_bytes apart).  Byte for byte what jpeg.encode() gives.  The encoder is kept for the next call with
+        the same extent and quality."""
+        if isinstance(image_or_pointer, np.ndarray):
+            image = np.ascontiguousarray(image_or_pointer, np.uint8)
+            if image.ndim != 3 or image.shape[2] not in (3, 4):
+                raise ValueError("a JPEG is made from a uint8 image of shape (height, width, 3 or 4)")
+            return self._cached_jpeg_encoder(image.shape[1], image.shape[0], quality).encode_image(image)
+        e = self.app.swapchain.extent
+        return self._cached_jpeg_encoder(width or e.width, height or e.height, quality).encode(image_or_pointer, channel_count, row_stride_bytes)
+
+    def read_jpeg(self, quality=70):
+        """The current frame as a JPEG file: the sRGB-encoded frame of read_encoded(), encoded on the device, so that
+        only the file crosses the bus"""
+        self.app.screenshot.frame_bits = 0
+        if self.lib.encode_output(C.byref(self.app), 0):
+            raise RuntimeError("encode_output failed")
+        return self.encode_jpeg(self.app.render_targets.encoded, quality)
+
     def slab_pixel_count(self, rank=0):
         return int(self.lib.get_slab_pixel_count(C.byref(self.app), rank))
 
@@ -752,7 +789,76 @@ class Renderer(HostScene):
     def close(self):
         for statistics in list(getattr(self, "_statistics", ())):
             statistics.close()
+        for encoder in getattr(self, "_jpeg_encoders", ()):
+            encoder.close()
         super().close()
+
+
+class JpegEncoder:
+    """create_jpeg_encoder() of include/vkr_jpeg.h for a Renderer: encode() for one frame at a time, begin() and end()
+    per slot for frames in flight, encode_on_device() for a file that stays in device memory."""
+
+    def __init__(self, owner, width, height, quality=70, slot_count=1):
+        self.owner, self.lib = owner, owner.lib
+        self.encoder = capi.JpegEncoder()
+        self.closed = True
+        if self.lib.create_jpeg_encoder(C.byref(self.encoder), owner._dev(), width, height, int(quality), slot_count):
+            raise RuntimeError("create_jpeg_encoder failed")
+        self.closed = False
+
+    @property
+    def capacity(self):
+        return int(self.encoder.capacity)
+
+    def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, stream=None):
+        """Enqueues the encode of device memory on `stream` (None: the device's) into the slot and returns at once"""
+        if self.lib.begin_jpeg_encode(C.byref(self.encoder), slot, pointer, channel_count, row_stride_bytes, stream):
+            raise RuntimeError("begin_jpeg_encode failed")
+
+    def end(self, slot, copy=True):
+        """Waits for the slot: the bytes of the file (copy=False: a numpy VIEW of the pinned staging memory, valid until
+        the slot's next begin())"""
+        address, size = C.c_void_p(), C.c_uint64()
+        if self.lib.end_jpeg_encode(C.byref(self.encoder), slot, C.byref(address), C.byref(size)):
+            raise RuntimeError("end_jpeg_encode failed")
+        if copy:
+            return C.string_at(address.value, size.value)
+        return np.frombuffer((C.c_uint8 * size.value).from_address(address.value), np.uint8)
+
+    def encode(self, pointer, channel_count=4, row_stride_bytes=0):
+        self.begin(0, pointer, channel_count, row_stride_bytes)
+        return self.end(0)
+
+    def encode_image(self, image, row_stride_bytes=0):
+        """Uploads a uint8 image (height, width, 3 or 4), rows row_stride_bytes apart on the device, and encodes it"""
+        image = np.ascontiguousarray(image, np.uint8)
+        if image.shape[0] != self.encoder.height or image.shape[1] != self.encoder.width:
+            raise ValueError("this encoder is for %d x %d images" % (self.encoder.width, self.encoder.height))
+        row = image.shape[1] * image.shape[2]
+        stride = int(row_stride_bytes) or row
+        padded = np.zeros((image.shape[0], stride), np.uint8)
+        padded[:, :row] = image.reshape(image.shape[0], row)
+        hip = C.CDLL("libamdhip64.so")
+        pointer = C.c_void_p()
+        if hip.hipMalloc(C.byref(pointer), C.c_size_t(padded.nbytes)):
+            raise RuntimeError("out of device memory for an image of %d bytes" % padded.nbytes)
+        try:
+            if hip.hipMemcpy(pointer, C.c_void_p(padded.ctypes.data), C.c_size_t(padded.nbytes), 1):
+                raise RuntimeError("uploading the image failed")
+            return self.encode(pointer, image.shape[2], stride)
+        finally:
+            hip.hipFree(pointer)
+
+    def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, stream=None):
+        """encode_jpeg_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
+        size_pointer, both device memory; returns once it is enqueued"""
+        if self.lib.encode_jpeg_on_device(C.byref(self.encoder), pointer, channel_count, row_stride_bytes, out_pointer, capacity, size_pointer, stream):
+            raise RuntimeError("encode_jpeg_on_device failed")
+
+    def close(self):
+        if not self.closed:
+            self.lib.destroy_jpeg_encoder(C.byref(self.encoder))
+            self.closed = True
 
 
 class FrameStatistics:
