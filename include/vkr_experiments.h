@@ -93,4 +93,11 @@ VKR_API int take_screenshot(application_t* app, const char* path_png, const char
 	path_jpg NULL does nothing.  Returns 0 on success; prints the reason otherwise. */
 VKR_API int take_jpg_screenshot(application_t* app, const char* path_jpg);
 
+/*! The *.hdr of implement_screenshot (reference main.c:1700-1711, stbi_write_hdr at :1757), encoded on the device
+	(include/vkr_hdr.h): the frame that take_screenshot() gives path_hdr - every channel of the radiance target rounded to
+	half precision and widened again - in the file the reference's writer makes of it, header included; only the file
+	crosses the bus.  From the end of the header on it is the file of take_screenshot().  path_hdr NULL does nothing.
+	Returns 0 on success; prints the reason otherwise. */
+VKR_API int take_hdr_screenshot(application_t* app, const char* path_hdr);
+
 #endif

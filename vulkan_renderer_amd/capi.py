@@ -234,6 +234,14 @@ class JpegEncoder(C.Structure):
 
 JPEG_HEADER_SIZE = 607  # VKR_JPEG_HEADER_SIZE
 
+
+class HdrEncoder(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("slot_count", C.c_uint32), ("header_size", C.c_uint32),
+                ("run_length_coded", C.c_uint32), ("capacity", C.c_uint64), ("state", C.c_void_p)]
+
+
+HDR_MAX_HEADER_SIZE = 128  # VKR_HDR_MAX_HEADER_SIZE
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -372,6 +380,18 @@ SIGNATURES = {
     "get_jpeg_header": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]),
     "write_jpeg": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
     "take_jpg_screenshot": (C.c_int, [P(Application), C.c_char_p]),
+    "create_hdr_encoder": (C.c_int, [P(HdrEncoder), P(Device), C.c_uint32, C.c_uint32, C.c_uint32]),
+    "destroy_hdr_encoder": (None, [P(HdrEncoder)]),
+    "begin_hdr_encode": (C.c_int, [P(HdrEncoder), C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "end_hdr_encode": (C.c_int, [P(HdrEncoder), C.c_uint32, P(C.c_void_p), P(C.c_uint64)]),
+    "encode_hdr": (C.c_int, [P(HdrEncoder), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, P(C.c_void_p), P(C.c_uint64)]),
+    "encode_hdr_on_device": (C.c_int, [P(HdrEncoder), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "get_hdr_capacity": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "get_hdr_chunk_size": (C.c_uint32, []),
+    "get_hdr_segment_size": (C.c_uint32, []),
+    "get_hdr_header": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "write_hdr_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
+    "take_hdr_screenshot": (C.c_int, [P(Application), C.c_char_p]),
 }
 
 _lib = None

@@ -59,13 +59,15 @@ class _DeviceTargets:
         self.pointers = []
 
 
-def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False):
+def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False, mean_hdr=None):
     """Renders `frames` frames with animated noise into a ring of targets and accumulates them on the device.  `renderer`
     has its targets, its pass and its visibility buffer.  reference_mean: a float32 image (height, width, 4) to take the
     RMSE against; seed: noise_table_t.random_seed of the first frame (default: wherever the sequence stands).
     Returns {"frames", "ms_per_frame", "mean_variance" (sample variance, ddof = 1, averaged over pixels and R, G, B; None for
     one frame), "rmse" (of the accumulated mean against the reference over pixels and R, G, B; None without one)} and,
-    with return_mean, "mean": the accumulated mean as a float32 image."""
+    with return_mean, "mean": the accumulated mean as a float32 image.  mean_hdr: a path that gets the accumulated mean as
+    a Radiance file, encoded on the device (include/vkr_hdr.h): the floats are not read back for it; "mean_hdr_bytes" is
+    the size of the file."""
     if frames < 1:
         raise ValueError("at least one frame")
     app = renderer.app
@@ -98,6 +100,12 @@ def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False)
             result["rmse"] = math.sqrt(float(renderer.squared_error(scratch, reference, pixels).sum()) / (3 * pixels))
         if return_mean:
             result["mean"] = targets.download(len(targets.pointers) - 2, (extent.height, extent.width, 4))
+        if mean_hdr:
+            # (resolve() left the mean on the device's stream, which the encoder uses)
+            data = renderer.encode_hdr(scratch, width=extent.width, height=extent.height)
+            with open(mean_hdr, "wb") as file:
+                file.write(data)
+            result["mean_hdr_bytes"] = len(data)
         if frames >= 2:
             statistics.resolve(None, scratch)
             result["mean_variance"] = float(renderer.frame_sum(scratch, pixels).sum()) / (3 * pixels)
@@ -150,6 +158,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1000, help="noise seed of the first measured frame")
     ap.add_argument("--reference-seed", type=int, default=50000)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--mean-hdr", metavar="PATH", default=None, help="write the mean of the accumulated frames as a Radiance *.hdr file, encoded on the device (with several combinations: of the last one)")
     args = ap.parse_args(argv)
     common = {} if args.sample_count is None else {"sample_count": args.sample_count}
     with tempfile.TemporaryDirectory() as directory:
@@ -172,7 +181,7 @@ def main(argv=None):
                 r = _make_renderer(args, dataset, arithmetic, noise, ltc, **overrides)
                 extent = r.app.swapchain.extent
                 line.update({"width": extent.width, "height": extent.height, "sample_count": int(r.app.render_settings.sample_count), "reference_frames": args.reference_frames})
-                line.update(measure(r, args.frames, reference, seed=args.seed))
+                line.update(measure(r, args.frames, reference, seed=args.seed, mean_hdr=args.mean_hdr))
             except RuntimeError as error:
                 # (a combination the pass refuses, e.g. a diffuse-only technique with an MIS strategy: its message is on stdout)
                 line["error"] = str(error)

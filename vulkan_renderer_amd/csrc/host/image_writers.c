@@ -7,6 +7,7 @@
 #include "vkr_internal.h"
 #include "vkr_experiments.h"
 #include "vkr_jpeg.h"
+#include "vkr_hdr.h"
 
 /* ---- byte buffer ----------------------------------------------------------------- */
 
@@ -396,5 +397,25 @@ int take_jpg_screenshot(application_t* app, const char* path_jpg) {
 	}
 	if (!failed) printf("Wrote screenshot to %s.\n", path_jpg);
 	app->screenshot.frame_bits = frame_bits_before;
+	return failed;
+}
+
+int take_hdr_screenshot(application_t* app, const char* path_hdr) {
+	if (!path_hdr) return 0;
+	hdr_encoder_t encoder;
+	const uint8_t* bytes = NULL;
+	uint64_t size = 0;
+	if (!app->render_targets.radiance) {
+		printf("There is no radiance target to write to %s: no frame has been rendered.\n", path_hdr);
+		return 1;
+	}
+	/* the HDR frame of take_screenshot(), straight from the radiance target: every channel through the half (main.c:1700-1711),
+	   alpha ignored; finish_frames() orders the device's stream behind the frames in flight as encode_output() does */
+	int failed = create_hdr_encoder(&encoder, &app->device, app->swapchain.extent.width, app->swapchain.extent.height, 1);
+	if (!failed) {
+		failed = finish_frames(app) || encode_hdr(&encoder, app->render_targets.radiance, 4, 0, VK_TRUE, &bytes, &size) || write_hdr_file(path_hdr, bytes, size);
+		destroy_hdr_encoder(&encoder);
+	}
+	if (!failed) printf("Wrote screenshot to %s.\n", path_hdr);
 	return failed;
 }

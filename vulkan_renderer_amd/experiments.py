@@ -107,8 +107,9 @@ def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=
         lib.destroy_experiment_list(C.byref(table))
 
 
-def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None, ltc="synthetic", jpg=False, png=True):
-    """Renders experiment `index` and stores its screenshot.  jpg: a *.jpg, encoded on the device (take_jpg_screenshot), next
+def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None, ltc="synthetic", jpg=False, png=True, device_hdr=False):
+    """Renders experiment `index` and stores its screenshot.  device_hdr: the *.hdr of hdr=True, encoded on the device
+    (take_hdr_screenshot) with the header of the reference's writer.  jpg: a *.jpg, encoded on the device (take_jpg_screenshot), next
     to the *.png or - png=False - instead of it; like the reference (main.c:1551) not together with hdr.  Returns a dict with the
     frame time and the screenshot path, or raises with the library's message.
     accumulate = n > 0: the screenshot holds the mean of n further frames with animated noise (summed on the device,
@@ -139,6 +140,7 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
             statistics.resolve(r.app.render_targets.radiance, None)
             statistics.close()
             settings.animate_noise = animate_before
+        hdr = hdr or device_hdr
         if jpg and hdr:
             raise ValueError("*.jpg and *.hdr screenshots cannot be mixed")
         screenshot = C.string_at(experiment.screenshot_path).decode()
@@ -148,7 +150,10 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
         path = C.string_at(pointer).decode()
         C.CDLL(None).free(C.c_void_p(pointer))
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        if (hdr or png or not jpg) and lib.take_screenshot(C.byref(r.app), None if hdr else path.encode(), path.encode() if hdr else None):
+        if device_hdr:
+            if lib.take_hdr_screenshot(C.byref(r.app), path.encode()):
+                raise RuntimeError("take_hdr_screenshot failed for %s" % path)
+        elif (hdr or png or not jpg) and lib.take_screenshot(C.byref(r.app), None if hdr else path.encode(), path.encode() if hdr else None):
             raise RuntimeError("take_screenshot failed for %s" % path)
         path_jpg = path[:-3] + "jpg" if jpg else None
         if jpg and lib.take_jpg_screenshot(C.byref(r.app), path_jpg.encode()):
@@ -176,13 +181,14 @@ def main(argv=None):
     ap.add_argument("--synthetic", metavar="DIR", default=None, help="write a generated stand-in data root to DIR and use it")
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--hdr", action="store_true", help="store *.hdr instead of *.png (take_hdr_screenshots of the reference)")
+    ap.add_argument("--device-hdr", action="store_true", help="store the *.hdr of --hdr, encoded on the device, with the header of the reference's writer")
     ap.add_argument("--jpg", action="store_true", help="store a *.jpg, encoded on the device at quality 70, next to the *.png (not with --hdr)")
     ap.add_argument("--no-png", action="store_true", help="with --jpg: store the *.jpg instead of the *.png")
     ap.add_argument("--accumulate", type=int, default=0, metavar="N", help="store the mean of N frames with animated noise instead of the last frame")
     ap.add_argument("--noise", default=None, choices=["blue", "sobol", "owen", "burley_owen"], help="generate this noise table on the device instead of loading the experiment's")
     ap.add_argument("--ltc", default="synthetic", choices=["synthetic", "fitted"], help="fitted: fit the LTC table on the device instead of reading data/ggx_ltc_fit (synthetic: the files of the data root, which --synthetic fills with placeholder fits)")
     args = ap.parse_args(argv)
-    if args.jpg and args.hdr:
+    if args.jpg and (args.hdr or args.device_hdr):
         ap.error("--jpg and --hdr cannot be mixed")
     lib = capi.load()
     if args.experiment is None:
@@ -196,7 +202,7 @@ def main(argv=None):
     if args.synthetic:
         root = args.synthetic
         fresnel_count = write_synthetic_data_root(root)["fresnel_count"]
-    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise, ltc=args.ltc, jpg=args.jpg, png=not (args.jpg and args.no_png))
+    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise, ltc=args.ltc, jpg=args.jpg, png=not (args.jpg and args.no_png), device_hdr=args.device_hdr)
     return 0
 
 

@@ -744,6 +744,42 @@ class Renderer(HostScene):
             raise RuntimeError("encode_output failed")
         return self.encode_jpeg(self.app.render_targets.encoded, quality)
 
+    # -- Radiance files (include/vkr_hdr.h) --------------------------------------------------
+    def create_hdr_encoder(self, width=None, height=None, slot_count=1):
+        """An encoder for float frames of one extent (default: the frame's) with `slot_count` output slots: an HdrEncoder,
+        which exposes begin() and end() per slot.  The caller closes it (Renderer.close() closes what is left)."""
+        e = self.app.swapchain.extent
+        encoder = HdrEncoder(self, int(width or e.width), int(height or e.height), slot_count)
+        self._hdr_encoders = getattr(self, "_hdr_encoders", []) + [encoder]
+        return encoder
+
+    def _cached_hdr_encoder(self, width, height):
+        cache = self.__dict__.setdefault("_hdr_cache", {})
+        key = (int(width), int(height))
+        if key not in cache or cache[key].closed:
+            cache[key] = self.create_hdr_encoder(width, height)
+        return cache[key]
+
+    def encode_hdr(self, image_or_pointer, through_half=False, width=None, height=None, channel_count=4, row_stride_bytes=0):
+        """The bytes of the Radiance file of an image - a float32 array (height, width, 3 or 4), which is uploaded - or of
+        device memory (an address; width, height default to the frame's extent; channel_count 3 or 4 floats, rows
+        row_stride_bytes apart).  Byte for byte what hdr.encode() gives.  The encoder is kept for the next call with
+        the same extent."""
+        if isinstance(image_or_pointer, np.ndarray):
+            image = np.ascontiguousarray(image_or_pointer, np.float32)
+            if image.ndim != 3 or image.shape[2] not in (3, 4):
+                raise ValueError("an HDR file is made from a float image of shape (height, width, 3 or 4)")
+            return self._cached_hdr_encoder(image.shape[1], image.shape[0]).encode_image(image, through_half=through_half)
+        e = self.app.swapchain.extent
+        return self._cached_hdr_encoder(width or e.width, height or e.height).encode(image_or_pointer, channel_count, row_stride_bytes, through_half)
+
+    def read_hdr(self, through_half=False):
+        """The current radiance target as a Radiance file, encoded on the device, so that only the file crosses the bus;
+        through_half: every channel through half precision first, as the screenshots of the reference"""
+        if self.lib.finish_frames(C.byref(self.app)):
+            raise RuntimeError("finish_frames failed")
+        return self.encode_hdr(self.app.render_targets.radiance, through_half)
+
     def slab_pixel_count(self, rank=0):
         return int(self.lib.get_slab_pixel_count(C.byref(self.app), rank))
 
@@ -790,6 +826,8 @@ class Renderer(HostScene):
         for statistics in list(getattr(self, "_statistics", ())):
             statistics.close()
         for encoder in getattr(self, "_jpeg_encoders", ()):
+            encoder.close()
+        for encoder in getattr(self, "_hdr_encoders", ()):
             encoder.close()
         super().close()
 
@@ -858,6 +896,73 @@ class JpegEncoder:
     def close(self):
         if not self.closed:
             self.lib.destroy_jpeg_encoder(C.byref(self.encoder))
+            self.closed = True
+
+
+class HdrEncoder:
+    """create_hdr_encoder() of include/vkr_hdr.h for a Renderer: encode() for one frame at a time, begin() and end() per
+    slot for frames in flight, encode_on_device() for a file that stays in device memory."""
+
+    def __init__(self, owner, width, height, slot_count=1):
+        self.owner, self.lib = owner, owner.lib
+        self.encoder = capi.HdrEncoder()
+        self.closed = True
+        if self.lib.create_hdr_encoder(C.byref(self.encoder), owner._dev(), width, height, slot_count):
+            raise RuntimeError("create_hdr_encoder failed")
+        self.closed = False
+
+    @property
+    def capacity(self):
+        return int(self.encoder.capacity)
+
+    def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
+        """Enqueues the encode of device memory on `stream` (None: the device's) into the slot and returns at once"""
+        if self.lib.begin_hdr_encode(C.byref(self.encoder), slot, pointer, channel_count, row_stride_bytes, int(bool(through_half)), stream):
+            raise RuntimeError("begin_hdr_encode failed")
+
+    def end(self, slot, copy=True):
+        """Waits for the slot: the bytes of the file (copy=False: a numpy VIEW of the pinned staging memory, valid until
+        the slot's next begin())"""
+        address, size = C.c_void_p(), C.c_uint64()
+        if self.lib.end_hdr_encode(C.byref(self.encoder), slot, C.byref(address), C.byref(size)):
+            raise RuntimeError("end_hdr_encode failed")
+        if copy:
+            return C.string_at(address.value, size.value)
+        return np.frombuffer((C.c_uint8 * size.value).from_address(address.value), np.uint8)
+
+    def encode(self, pointer, channel_count=4, row_stride_bytes=0, through_half=False):
+        self.begin(0, pointer, channel_count, row_stride_bytes, through_half)
+        return self.end(0)
+
+    def encode_image(self, image, row_stride_bytes=0, through_half=False):
+        """Uploads a float32 image (height, width, 3 or 4), rows row_stride_bytes apart on the device, and encodes it"""
+        image = np.ascontiguousarray(image, np.float32)
+        if image.shape[0] != self.encoder.height or image.shape[1] != self.encoder.width:
+            raise ValueError("this encoder is for %d x %d images" % (self.encoder.width, self.encoder.height))
+        row = image.shape[1] * image.shape[2] * 4
+        stride = int(row_stride_bytes) or row
+        padded = np.zeros((image.shape[0], stride), np.uint8)
+        padded[:, :row] = image.view(np.uint8).reshape(image.shape[0], row)
+        hip = C.CDLL("libamdhip64.so")
+        pointer = C.c_void_p()
+        if hip.hipMalloc(C.byref(pointer), C.c_size_t(padded.nbytes)):
+            raise RuntimeError("out of device memory for an image of %d bytes" % padded.nbytes)
+        try:
+            if hip.hipMemcpy(pointer, C.c_void_p(padded.ctypes.data), C.c_size_t(padded.nbytes), 1):
+                raise RuntimeError("uploading the image failed")
+            return self.encode(pointer, image.shape[2], stride, through_half)
+        finally:
+            hip.hipFree(pointer)
+
+    def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
+        """encode_hdr_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
+        size_pointer, both device memory; returns once it is enqueued"""
+        if self.lib.encode_hdr_on_device(C.byref(self.encoder), pointer, channel_count, row_stride_bytes, int(bool(through_half)), out_pointer, capacity, size_pointer, stream):
+            raise RuntimeError("encode_hdr_on_device failed")
+
+    def close(self):
+        if not self.closed:
+            self.lib.destroy_hdr_encoder(C.byref(self.encoder))
             self.closed = True
 
 
