@@ -100,4 +100,12 @@ VKR_API int take_jpg_screenshot(application_t* app, const char* path_jpg);
 	Returns 0 on success; prints the reason otherwise. */
 VKR_API int take_hdr_screenshot(application_t* app, const char* path_hdr);
 
+/*! The *.png of implement_screenshot (reference main.c:1664-1674, stbi_write_png at :1738), encoded on the device
+	(include/vkr_png.h): the frame that take_screenshot() gives path_png, with the same filtered rows as the reference's
+	file and this project's own deflate stream; only the file crosses the bus.  Every call creates and destroys an
+	encoder, pinned staging memory included, which costs tens of milliseconds: fine for a screenshot; who
+	encodes frame after frame keeps a png_encoder_t (include/vkr_png.h).  path_png NULL does nothing.  Returns 0 on
+	success; prints the reason otherwise. */
+VKR_API int take_png_screenshot(application_t* app, const char* path_png);
+
 #endif

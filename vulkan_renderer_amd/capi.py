@@ -242,6 +242,14 @@ class HdrEncoder(C.Structure):
 
 HDR_MAX_HEADER_SIZE = 128  # VKR_HDR_MAX_HEADER_SIZE
 
+
+class PngEncoder(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("slot_count", C.c_uint32), ("row_length", C.c_uint32),
+                ("rows_per_segment", C.c_uint32), ("segment_count", C.c_uint32), ("capacity", C.c_uint64), ("state", C.c_void_p)]
+
+
+PNG_HEADER_SIZE = 33  # VKR_PNG_HEADER_SIZE
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -392,6 +400,18 @@ SIGNATURES = {
     "get_hdr_header": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "write_hdr_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
     "take_hdr_screenshot": (C.c_int, [P(Application), C.c_char_p]),
+    "create_png_encoder": (C.c_int, [P(PngEncoder), P(Device), C.c_uint32, C.c_uint32, C.c_uint32]),
+    "destroy_png_encoder": (None, [P(PngEncoder)]),
+    "begin_png_encode": (C.c_int, [P(PngEncoder), C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "end_png_encode": (C.c_int, [P(PngEncoder), C.c_uint32, P(C.c_void_p), P(C.c_uint64)]),
+    "encode_png": (C.c_int, [P(PngEncoder), C.c_void_p, C.c_uint32, C.c_uint64, P(C.c_void_p), P(C.c_uint64)]),
+    "encode_png_on_device": (C.c_int, [P(PngEncoder), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "get_png_capacity": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "get_png_stream_capacity": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "get_png_header": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "write_png_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
+    "probe_png_stream": (C.c_int, [P(Device), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
+    "take_png_screenshot": (C.c_int, [P(Application), C.c_char_p]),
 }
 
 _lib = None

@@ -59,7 +59,7 @@ class _DeviceTargets:
         self.pointers = []
 
 
-def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False, mean_hdr=None):
+def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False, mean_hdr=None, mean_png=None):
     """Renders `frames` frames with animated noise into a ring of targets and accumulates them on the device.  `renderer`
     has its targets, its pass and its visibility buffer.  reference_mean: a float32 image (height, width, 4) to take the
     RMSE against; seed: noise_table_t.random_seed of the first frame (default: wherever the sequence stands).
@@ -67,7 +67,8 @@ def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False,
     one frame), "rmse" (of the accumulated mean against the reference over pixels and R, G, B; None without one)} and,
     with return_mean, "mean": the accumulated mean as a float32 image.  mean_hdr: a path that gets the accumulated mean as
     a Radiance file, encoded on the device (include/vkr_hdr.h): the floats are not read back for it; "mean_hdr_bytes" is
-    the size of the file."""
+    the size of the file.  mean_png: a path that gets the sRGB8 encoding of the accumulated mean as a PNG file, encoded on
+    the device as well (include/vkr_png.h); "mean_png_bytes" is its size."""
     if frames < 1:
         raise ValueError("at least one frame")
     app = renderer.app
@@ -106,6 +107,13 @@ def measure(renderer, frames, reference_mean=None, seed=None, return_mean=False,
             with open(mean_hdr, "wb") as file:
                 file.write(data)
             result["mean_hdr_bytes"] = len(data)
+        if mean_png:
+            # the output encoding of the mean into the target of the reference, which has served its purpose
+            renderer.encode_slab(scratch, reference, pixels)
+            data = renderer.encode_png(reference, width=extent.width, height=extent.height)
+            with open(mean_png, "wb") as file:
+                file.write(data)
+            result["mean_png_bytes"] = len(data)
         if frames >= 2:
             statistics.resolve(None, scratch)
             result["mean_variance"] = float(renderer.frame_sum(scratch, pixels).sum()) / (3 * pixels)
@@ -159,6 +167,7 @@ def main(argv=None):
     ap.add_argument("--reference-seed", type=int, default=50000)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--mean-hdr", metavar="PATH", default=None, help="write the mean of the accumulated frames as a Radiance *.hdr file, encoded on the device (with several combinations: of the last one)")
+    ap.add_argument("--mean-png", metavar="PATH", default=None, help="write the sRGB8 encoding of the mean of the accumulated frames as a *.png file, encoded on the device (with several combinations: of the last one)")
     args = ap.parse_args(argv)
     common = {} if args.sample_count is None else {"sample_count": args.sample_count}
     with tempfile.TemporaryDirectory() as directory:
@@ -181,7 +190,7 @@ def main(argv=None):
                 r = _make_renderer(args, dataset, arithmetic, noise, ltc, **overrides)
                 extent = r.app.swapchain.extent
                 line.update({"width": extent.width, "height": extent.height, "sample_count": int(r.app.render_settings.sample_count), "reference_frames": args.reference_frames})
-                line.update(measure(r, args.frames, reference, seed=args.seed, mean_hdr=args.mean_hdr))
+                line.update(measure(r, args.frames, reference, seed=args.seed, mean_hdr=args.mean_hdr, mean_png=args.mean_png))
             except RuntimeError as error:
                 # (a combination the pass refuses, e.g. a diffuse-only technique with an MIS strategy: its message is on stdout)
                 line["error"] = str(error)

@@ -8,6 +8,7 @@
 #include "vkr_experiments.h"
 #include "vkr_jpeg.h"
 #include "vkr_hdr.h"
+#include "vkr_png.h"
 
 /* ---- byte buffer ----------------------------------------------------------------- */
 
@@ -417,5 +418,23 @@ int take_hdr_screenshot(application_t* app, const char* path_hdr) {
 		destroy_hdr_encoder(&encoder);
 	}
 	if (!failed) printf("Wrote screenshot to %s.\n", path_hdr);
+	return failed;
+}
+
+int take_png_screenshot(application_t* app, const char* path_png) {
+	if (!path_png) return 0;
+	uint32_t frame_bits_before = app->screenshot.frame_bits;
+	png_encoder_t encoder;
+	const uint8_t* bytes = NULL;
+	uint64_t size = 0;
+	/* the LDR frame of take_screenshot(), straight from the device: alpha is dropped by the encoder (main.c:1664-1674, 1738) */
+	app->screenshot.frame_bits = 0;
+	int failed = create_png_encoder(&encoder, &app->device, app->swapchain.extent.width, app->swapchain.extent.height, 1);
+	if (!failed) {
+		failed = encode_output(app, VK_FALSE) || encode_png(&encoder, app->render_targets.encoded, 4, 0, &bytes, &size) || write_png_file(path_png, bytes, size);
+		destroy_png_encoder(&encoder);
+	}
+	if (!failed) printf("Wrote screenshot to %s.\n", path_png);
+	app->screenshot.frame_bits = frame_bits_before;
 	return failed;
 }

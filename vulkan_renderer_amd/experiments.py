@@ -107,8 +107,9 @@ def experiment_renderer(index, data_root, synthetic_inputs=False, fresnel_count=
         lib.destroy_experiment_list(C.byref(table))
 
 
-def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None, ltc="synthetic", jpg=False, png=True, device_hdr=False):
-    """Renders experiment `index` and stores its screenshot.  device_hdr: the *.hdr of hdr=True, encoded on the device
+def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False, fresnel_count=51, hdr=False, hip_device=0, verbose=True, accumulate=0, noise=None, ltc="synthetic", jpg=False, png=True, device_hdr=False, device_png=False):
+    """Renders experiment `index` and stores its screenshot.  device_png: the *.png, encoded on the device
+    (take_png_screenshot): the pixels of the host writer's file in fewer bytes.  device_hdr: the *.hdr of hdr=True, encoded on the device
     (take_hdr_screenshot) with the header of the reference's writer.  jpg: a *.jpg, encoded on the device (take_jpg_screenshot), next
     to the *.png or - png=False - instead of it; like the reference (main.c:1551) not together with hdr.  Returns a dict with the
     frame time and the screenshot path, or raises with the library's message.
@@ -153,6 +154,9 @@ def run_experiment(index, data_root, frames=32, warmup=4, synthetic_inputs=False
         if device_hdr:
             if lib.take_hdr_screenshot(C.byref(r.app), path.encode()):
                 raise RuntimeError("take_hdr_screenshot failed for %s" % path)
+        elif device_png and not hdr and (png or not jpg):
+            if lib.take_png_screenshot(C.byref(r.app), path.encode()):
+                raise RuntimeError("take_png_screenshot failed for %s" % path)
         elif (hdr or png or not jpg) and lib.take_screenshot(C.byref(r.app), None if hdr else path.encode(), path.encode() if hdr else None):
             raise RuntimeError("take_screenshot failed for %s" % path)
         path_jpg = path[:-3] + "jpg" if jpg else None
@@ -182,6 +186,7 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--hdr", action="store_true", help="store *.hdr instead of *.png (take_hdr_screenshots of the reference)")
     ap.add_argument("--device-hdr", action="store_true", help="store the *.hdr of --hdr, encoded on the device, with the header of the reference's writer")
+    ap.add_argument("--device-png", action="store_true", help="store the *.png encoded on the device: the same pixels and filtered rows, dynamic Huffman codes")
     ap.add_argument("--jpg", action="store_true", help="store a *.jpg, encoded on the device at quality 70, next to the *.png (not with --hdr)")
     ap.add_argument("--no-png", action="store_true", help="with --jpg: store the *.jpg instead of the *.png")
     ap.add_argument("--accumulate", type=int, default=0, metavar="N", help="store the mean of N frames with animated noise instead of the last frame")
@@ -202,7 +207,7 @@ def main(argv=None):
     if args.synthetic:
         root = args.synthetic
         fresnel_count = write_synthetic_data_root(root)["fresnel_count"]
-    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise, ltc=args.ltc, jpg=args.jpg, png=not (args.jpg and args.no_png), device_hdr=args.device_hdr)
+    run_experiment(args.experiment, root, frames=args.frames, synthetic_inputs=bool(args.synthetic), fresnel_count=fresnel_count, hdr=args.hdr, accumulate=args.accumulate, noise=args.noise, ltc=args.ltc, jpg=args.jpg, png=not (args.jpg and args.no_png), device_hdr=args.device_hdr, device_png=args.device_png)
     return 0
 
 

@@ -780,6 +780,60 @@ class Renderer(HostScene):
             raise RuntimeError("finish_frames failed")
         return self.encode_hdr(self.app.render_targets.radiance, through_half)
 
+    # -- PNG files (include/vkr_png.h) -------------------------------------------------------
+    def create_png_encoder(self, width=None, height=None, slot_count=1):
+        """An encoder for 8-bit frames of one extent (default: the frame's) with `slot_count` output slots: a PngEncoder,
+        which exposes begin() and end() per slot.  The caller closes it (Renderer.close() closes what is left)."""
+        e = self.app.swapchain.extent
+        encoder = PngEncoder(self, int(width or e.width), int(height or e.height), slot_count)
+        self._png_encoders = getattr(self, "_png_encoders", []) + [encoder]
+        return encoder
+
+    def _cached_png_encoder(self, width, height):
+        cache = self.__dict__.setdefault("_png_cache", {})
+        key = (int(width), int(height))
+        if key not in cache or cache[key].closed:
+            cache[key] = self.create_png_encoder(width, height)
+        return cache[key]
+
+    def encode_png(self, image_or_pointer, width=None, height=None, channel_count=4, row_stride_bytes=0):
+        """The bytes of the PNG file of an image - a uint8 array (height, width, 3 or 4), which is uploaded - or of device
+        memory (an address; width, height default to the frame's extent; channel_count 3 or 4 bytes, rows
+        row_stride_bytes apart).  Byte for byte what png.encode() gives.  The encoder is kept for the next call with the
+        same extent."""
+        if isinstance(image_or_pointer, np.ndarray):
+            image = np.ascontiguousarray(image_or_pointer, np.uint8)
+            if image.ndim != 3 or image.shape[2] not in (3, 4):
+                raise ValueError("a PNG file is made from a uint8 image of shape (height, width, 3 or 4)")
+            return self._cached_png_encoder(image.shape[1], image.shape[0]).encode_image(image)
+        e = self.app.swapchain.extent
+        return self._cached_png_encoder(width or e.width, height or e.height).encode(image_or_pointer, channel_count, row_stride_bytes)
+
+    def read_png(self, output_linear_rgb=False):
+        """The current frame as a PNG file of its sRGB8 encoding (the RGB of read_encoded()), encoded on the device, so that
+        only the file crosses the bus"""
+        before = self.app.screenshot.frame_bits
+        self.app.screenshot.frame_bits = 0
+        try:
+            if self.lib.encode_output(C.byref(self.app), int(output_linear_rgb)):
+                raise RuntimeError("encode_output failed")
+        finally:
+            self.app.screenshot.frame_bits = before
+        return self.encode_png(self.app.render_targets.encoded)
+
+    def probe_png_stream(self, stream):
+        """probe_png_stream() of include/vkr_png.h: the file the device makes of a filtered stream of the caller's, a uint8
+        array (rows, row_length)"""
+        stream = np.ascontiguousarray(stream, np.uint8)
+        rows, row_length = stream.shape
+        capacity = int(self.lib.get_png_stream_capacity(row_length, rows))
+        out, size = np.zeros(capacity, np.uint8), C.c_uint64()
+        if capacity == 0 or self.lib.probe_png_stream(self._dev(), C.c_void_p(stream.ctypes.data), row_length, rows, C.c_void_p(out.ctypes.data), capacity, C.byref(size)):
+            raise RuntimeError("probe_png_stream failed")
+        if size.value > capacity:
+            raise RuntimeError("a file of %d bytes exceeds the capacity of %d" % (size.value, capacity))
+        return out[:size.value].tobytes()
+
     def slab_pixel_count(self, rank=0):
         return int(self.lib.get_slab_pixel_count(C.byref(self.app), rank))
 
@@ -828,6 +882,8 @@ class Renderer(HostScene):
         for encoder in getattr(self, "_jpeg_encoders", ()):
             encoder.close()
         for encoder in getattr(self, "_hdr_encoders", ()):
+            encoder.close()
+        for encoder in getattr(self, "_png_encoders", ()):
             encoder.close()
         super().close()
 
@@ -963,6 +1019,89 @@ class HdrEncoder:
     def close(self):
         if not self.closed:
             self.lib.destroy_hdr_encoder(C.byref(self.encoder))
+            self.closed = True
+
+
+_HIP_RUNTIME = None
+
+
+def _hip_runtime():
+    """The HIP runtime that the library has loaded, opened once, with the signatures of the three calls that
+    PngEncoder.encode_image() makes"""
+    global _HIP_RUNTIME
+    if _HIP_RUNTIME is None:
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes, hip.hipMalloc.restype = [C.POINTER(C.c_void_p), C.c_size_t], C.c_int
+        hip.hipMemcpy.argtypes, hip.hipMemcpy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
+        hip.hipFree.argtypes, hip.hipFree.restype = [C.c_void_p], C.c_int
+        _HIP_RUNTIME = hip
+    return _HIP_RUNTIME
+
+
+class PngEncoder:
+    """create_png_encoder() of include/vkr_png.h for a Renderer: encode() for one frame at a time, begin() and end() per
+    slot for frames in flight, encode_on_device() for a file that stays in device memory."""
+
+    def __init__(self, owner, width, height, slot_count=1):
+        self.owner, self.lib = owner, owner.lib
+        self.encoder = capi.PngEncoder()
+        self.closed = True
+        if self.lib.create_png_encoder(C.byref(self.encoder), owner._dev(), width, height, slot_count):
+            raise RuntimeError("create_png_encoder failed")
+        self.closed = False
+
+    @property
+    def capacity(self):
+        return int(self.encoder.capacity)
+
+    def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, stream=None):
+        """Enqueues the encode of device memory on `stream` (None: the device's) into the slot and returns at once"""
+        if self.lib.begin_png_encode(C.byref(self.encoder), slot, pointer, channel_count, row_stride_bytes, stream):
+            raise RuntimeError("begin_png_encode failed")
+
+    def end(self, slot, copy=True):
+        """Waits for the slot: the bytes of the file (copy=False: a numpy VIEW of the pinned staging memory, valid until
+        the slot's next begin())"""
+        address, size = C.c_void_p(), C.c_uint64()
+        if self.lib.end_png_encode(C.byref(self.encoder), slot, C.byref(address), C.byref(size)):
+            raise RuntimeError("end_png_encode failed")
+        if copy:
+            return C.string_at(address.value, size.value)
+        return np.frombuffer((C.c_uint8 * size.value).from_address(address.value), np.uint8)
+
+    def encode(self, pointer, channel_count=4, row_stride_bytes=0):
+        self.begin(0, pointer, channel_count, row_stride_bytes)
+        return self.end(0)
+
+    def encode_image(self, image, row_stride_bytes=0):
+        """Uploads a uint8 image (height, width, 3 or 4), rows row_stride_bytes apart on the device, and encodes it"""
+        image = np.ascontiguousarray(image, np.uint8)
+        if image.shape[0] != self.encoder.height or image.shape[1] != self.encoder.width:
+            raise ValueError("this encoder is for %d x %d images" % (self.encoder.width, self.encoder.height))
+        row = image.shape[1] * image.shape[2]
+        stride = int(row_stride_bytes) or row
+        padded = np.full((image.shape[0], stride), 0xA5, np.uint8)
+        padded[:, :row] = image.reshape(image.shape[0], row)
+        hip = _hip_runtime()
+        pointer = C.c_void_p()
+        if hip.hipMalloc(C.byref(pointer), padded.nbytes):
+            raise RuntimeError("out of device memory for an image of %d bytes" % padded.nbytes)
+        try:
+            if hip.hipMemcpy(pointer, padded.ctypes.data, padded.nbytes, 1):
+                raise RuntimeError("uploading the image failed")
+            return self.encode(pointer, image.shape[2], stride)
+        finally:
+            hip.hipFree(pointer)
+
+    def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, stream=None):
+        """encode_png_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
+        size_pointer, both device memory; returns once it is enqueued"""
+        if self.lib.encode_png_on_device(C.byref(self.encoder), pointer, channel_count, row_stride_bytes, out_pointer, capacity, size_pointer, stream):
+            raise RuntimeError("encode_png_on_device failed")
+
+    def close(self):
+        if not self.closed:
+            self.lib.destroy_png_encoder(C.byref(self.encoder))
             self.closed = True
 
 
