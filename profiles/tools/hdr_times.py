@@ -141,9 +141,11 @@ def summarise_trace(directory, dispatches=11):
     for row in rows:
         name = row["Kernel_Name"]
         # (the scan's kernels count between the two passes over the rows only: other units scan too)
-        in_chain = "k_hdr_row_sizes" in name or (in_chain and "k_hdr" not in name)
-        if "k_hdr" in name or (in_chain and "scan" in name.lower()):
-            short = name[name.index("k_hdr"):].split("(")[0].split("E")[0] if "k_hdr" in name else ("rocprim init_lookback_scan_state" if "init" in name.lower() else "rocprim scan")
+        # (the copy-out is the kernel that the encoders share, csrc/output_slots.hip: in this run every one is an HDR file's)
+        own = "k_hdr" if "k_hdr" in name else "k_copy_record_out" if "k_copy_record_out" in name else None
+        in_chain = "k_hdr_row_sizes" in name or (in_chain and not own)
+        if own or (in_chain and "scan" in name.lower()):
+            short = name[name.index(own):].split("(")[0].split("E")[0] if own else ("rocprim init_lookback_scan_state" if "init" in name.lower() else "rocprim scan")
             durations.setdefault(short, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-3)
     result = {}
     for kernel, values in durations.items():

@@ -88,7 +88,7 @@ def measure_frame(r, encoder, pointer, width, height, rounds, screenshot):
 
 def summarise_trace(directory, dispatches):
     """Medians per kernel and input from the *_kernel_trace.csv of a `--trace` run under rocprofv3 --kernel-trace: a chain
-    begins with k_png_filter and ends with k_png_copy_out, the scans in between are the encoder's; every input is
+    begins with k_png_filter and ends with k_copy_record_out, the scans in between are the encoder's; every input is
     dispatched `dispatches` times, the inputs in the order of main(); the first WARM_UP chains of an input are left out"""
     import csv
     import glob
@@ -106,12 +106,14 @@ def summarise_trace(directory, dispatches):
             continue
         if "k_png" in name:
             short = name[name.index("k_png"):].split("(")[0].split("E")[0]
+        elif "k_copy_record_out" in name:
+            short = "k_copy_record_out"
         elif "scan" in name.lower():
             short = "rocprim init_lookback_scan_state" if "init" in name.lower() else "rocprim scan"
         else:
             short = "other (clears)"
         chains[-1][short] = chains[-1].get(short, 0.0) + (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-3
-        if "k_png_copy_out" in name:
+        if "k_copy_record_out" in name:
             in_chain = False
     result = {}
     groups = [chains[i:i + dispatches] for i in range(0, len(chains), dispatches)]

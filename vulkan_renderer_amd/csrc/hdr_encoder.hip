@@ -4,13 +4,12 @@
 //   hipcub exclusive sum, 64 bit, over the rows
 //   k_hdr_write_rows     header, scanline headers, the coded planes at their offsets, size word
 // for the other widths k_hdr_raw alone: header, RGBE quadruples, size word.  Then
-//   k_hdr_copy_out       the size record and that many bytes into the slot's pinned staging memory
+//   k_copy_record_out    (output_slots.hip) the size record and that many bytes into the slot's pinned staging memory
 // The coding exists once, code_row<Load, Sink>: the first pass runs it with a sink that drops the bytes and keeps the
 // positions, the second with one that stores them, so that sizes and bytes cannot disagree.
 // This unit is compiled without contraction whatever the arithmetic mode of the pass: the bytes are the interface.
 #include "vkr_hdr.h"
-#include "host/vkr_internal.h"
-#include <hip/hip_runtime.h>
+#include "output_slots.h"
 #include <hip/hip_fp16.h>
 #include <hipcub/hipcub.hpp>
 #include <float.h>
@@ -19,7 +18,6 @@ namespace {
 
 constexpr uint32_t kChunk = VKR_HDR_CHUNK;
 constexpr uint32_t kSegment = VKR_HDR_SEGMENT;
-constexpr uint32_t kMaxSlots = VKR_MAX_FRAMES_IN_FLIGHT + 1;
 // pixels staged besides a segment: the left neighbour of its first one, and three behind it (whether the element
 // behind a chunk is part of a run depends on the three elements that follow the chunk)
 constexpr uint32_t kBefore = 1, kBehind = 3;
@@ -225,37 +223,34 @@ __global__ void __launch_bounds__(256) k_hdr_raw(hdr_source source, uint32_t wid
 		if (at + c < capacity) out[at + c] = (uint8_t) (rgbe >> (8u * c));
 }
 
-// record: the size in its first 8 of 16 bytes, then the file.  Sixteen bytes per lane into host memory.
-__global__ void __launch_bounds__(256) k_hdr_copy_out(const uint4* record, uint4* staging, uint64_t capacity_units) {
-	uint64_t units = min(1 + (*(const uint64_t*) record + 15) / 16, capacity_units);
-	for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < units; i += (uint64_t) gridDim.x * 256) staging[i] = record[i];
-}
-
 // ---- the encoder ------------------------------------------------------------------------------------------------------
 
+// the scratch memory of a slot besides what output_slots.h keeps
 struct hdr_slot {
 	uint32_t *rgbe, *plane_sizes;
 	uint64_t *row_sizes, *row_offsets;
-	uint8_t* record;
-	void* scan_storage;
-	// pinned host memory with the layout of record, and its address on the device
-	uint8_t *staging, *staging_device;
-	hipEvent_t done;
-	bool begun;
 };
 
 struct hdr_state {
-	void* stream;
-	uint8_t* header;
-	uint64_t record_units;
-	size_t scan_bytes;
-	void* scratch;
-	hdr_slot slots[kMaxSlots];
+	// (what its slots share: the header)
+	output_slots out;
+	hdr_slot slots[kMaxOutputSlots];
 };
 
-bool valid_extent(uint32_t width, uint32_t height) { return width != 0 && height != 0 && width <= 65535 && height <= 65535; }
+output_slots* slots_of(const hdr_encoder_t* encoder) { return encoder && encoder->state ? &((hdr_state*) encoder->state)->out : NULL; }
 
 bool run_length_coded(uint32_t width) { return width >= 8 && width < 32768; }
+
+// (raw widths need the record alone)
+void lay_out_slot(output_carver& carve, void* hdr_encoder_pointer, uint32_t slot_index) {
+	const hdr_encoder_t* encoder = (const hdr_encoder_t*) hdr_encoder_pointer;
+	hdr_slot& slot = ((hdr_state*) encoder->state)->slots[slot_index];
+	size_t pixels = encoder->run_length_coded ? (size_t) encoder->width * encoder->height : 0, rows = encoder->run_length_coded ? encoder->height : 0;
+	carve.take(slot.rgbe, pixels);
+	carve.take(slot.plane_sizes, rows * 4);
+	carve.take(slot.row_sizes, rows + 1);
+	carve.take(slot.row_offsets, rows + 1);
+}
 
 int enqueue_encode(hdr_encoder_t* encoder, uint32_t slot_index, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, VkBool32 through_half,
                    uint8_t* out, uint64_t capacity, uint64_t* size_word, bool copy_out, void* stream_or_null) {
@@ -270,32 +265,24 @@ int enqueue_encode(hdr_encoder_t* encoder, uint32_t slot_index, const void* devi
 		printf("A row stride of %llu bytes is less than a row of %u pixels of %u floats, or no multiple of four.\n", (unsigned long long) row_stride_bytes, encoder->width, channel_count);
 		return 1;
 	}
-	hipStream_t stream = (hipStream_t) (stream_or_null ? stream_or_null : state->stream);
-	hdr_slot& slot = state->slots[slot_index];
+	hipStream_t stream;
+	if (begin_output_enqueue(&state->out, slot_index, stream_or_null, &stream)) return 1;
+	const hdr_slot& slot = state->slots[slot_index];
+	const uint8_t* header = state->out.shared;
 	uint32_t width = encoder->width, height = encoder->height;
-	// the scratch memory of the slot is free once its previous encode is through
-	if (hip_failed(hipStreamWaitEvent(stream, slot.done, 0), "ordering an HDR encode behind the slot's previous one")) return 1;
 	hdr_source source = {(const uint8_t*) device_pixels, row_stride_bytes, channel_count, through_half ? 1u : 0u,
 		(channel_count == 4 && (uintptr_t) device_pixels % 16 == 0 && row_stride_bytes % 16 == 0) ? 1u : 0u};
 	if (encoder->run_length_coded) {
 		k_hdr_row_sizes<<<height, 256, 0, stream>>>(source, width, height, slot.rgbe, slot.plane_sizes, slot.row_sizes);
-		size_t scan_bytes = state->scan_bytes;
-		if (hip_failed(hipcub::DeviceScan::ExclusiveSum(slot.scan_storage, scan_bytes, slot.row_sizes, slot.row_offsets, (int) (height + 1), stream), "summing the sizes of the rows")) return 1;
-		k_hdr_write_rows<<<height, 256, 0, stream>>>(slot.rgbe, width, height, slot.plane_sizes, slot.row_offsets, state->header, encoder->header_size, out, capacity, size_word);
+		size_t scan_bytes = state->out.scan_bytes;
+		if (hip_failed(hipcub::DeviceScan::ExclusiveSum(state->out.slots[slot_index].scan_storage, scan_bytes, slot.row_sizes, slot.row_offsets, (int) (height + 1), stream), "summing the sizes of the rows")) return 1;
+		k_hdr_write_rows<<<height, 256, 0, stream>>>(slot.rgbe, width, height, slot.plane_sizes, slot.row_offsets, header, encoder->header_size, out, capacity, size_word);
 	}
 	else {
 		uint64_t pixel_count = (uint64_t) width * height;
-		k_hdr_raw<<<block_count(pixel_count > encoder->header_size ? pixel_count : encoder->header_size, 256), 256, 0, stream>>>(source, width, pixel_count, state->header, encoder->header_size, out, capacity, size_word);
+		k_hdr_raw<<<block_count(pixel_count > encoder->header_size ? pixel_count : encoder->header_size, 256), 256, 0, stream>>>(source, width, pixel_count, header, encoder->header_size, out, capacity, size_word);
 	}
-	if (copy_out) k_hdr_copy_out<<<256, 256, 0, stream>>>((const uint4*) slot.record, (uint4*) slot.staging_device, state->record_units);
-	if (hip_failed(hipGetLastError(), "encoding an HDR file")) return 1;
-	return hip_failed(hipEventRecord(slot.done, stream), "recording the end of an HDR encode");
-}
-
-int check_slot(const hdr_encoder_t* encoder, uint32_t slot) {
-	if (encoder && encoder->state && slot < encoder->slot_count) return 0;
-	printf("Slot %u is not a slot of this HDR encoder.\n", slot);
-	return 1;
+	return finish_output_enqueue(&state->out, slot_index, stream, copy_out ? 256 : 0);
 }
 
 }  // namespace
@@ -305,7 +292,7 @@ extern "C" uint32_t get_hdr_chunk_size(void) { return kChunk; }
 extern "C" uint32_t get_hdr_segment_size(void) { return kSegment; }
 
 extern "C" uint32_t get_hdr_header(char header[VKR_HDR_MAX_HEADER_SIZE], uint32_t width, uint32_t height) {
-	if (!valid_extent(width, height)) return 0;
+	if (!valid_output_extent(width, height)) return 0;
 	return (uint32_t) snprintf(header, VKR_HDR_MAX_HEADER_SIZE, "#?RADIANCE\n# Written by stb_image_write.h\nFORMAT=32-bit_rle_rgbe\nEXPOSURE=          1.0000000000000\n\n-Y %d +X %d\n", (int) height, (int) width);
 }
 
@@ -317,30 +304,12 @@ extern "C" uint64_t get_hdr_capacity(uint32_t width, uint32_t height) {
 	return header_size + (uint64_t) height * (4ull + 4ull * (width + (width + 127u) / 128u));
 }
 
-extern "C" int write_hdr_file(const char* path, const uint8_t* bytes, uint64_t size) {
-	FILE* file = (path && bytes) ? fopen(path, "wb") : NULL;
-	if (!file) {
-		printf("Failed to open %s for writing.\n", path ? path : "(null)");
-		return 1;
-	}
-	int failed = fwrite(bytes, 1, size, file) != size;
-	failed |= fclose(file) != 0;
-	if (failed) printf("Failed to write %s.\n", path);
-	return failed;
-}
+extern "C" int write_hdr_file(const char* path, const uint8_t* bytes, uint64_t size) { return vkr_write_file(path, bytes, size); }
 
 extern "C" void destroy_hdr_encoder(hdr_encoder_t* encoder) {
 	hdr_state* state = encoder ? (hdr_state*) encoder->state : NULL;
 	if (state) {
-		for (uint32_t i = 0; i != kMaxSlots; ++i) {
-			hdr_slot& slot = state->slots[i];
-			if (slot.done) {
-				(void) hipEventSynchronize(slot.done);
-				(void) hipEventDestroy(slot.done);
-			}
-			if (slot.staging) (void) hipHostFree(slot.staging);
-		}
-		if (state->scratch) (void) hipFree(state->scratch);
+		destroy_output_slots(&state->out);
 		free(state);
 	}
 	if (encoder) memset(encoder, 0, sizeof(*encoder));
@@ -348,18 +317,7 @@ extern "C" void destroy_hdr_encoder(hdr_encoder_t* encoder) {
 
 extern "C" int create_hdr_encoder(hdr_encoder_t* encoder, const device_t* device, uint32_t width, uint32_t height, uint32_t slot_count) {
 	memset(encoder, 0, sizeof(*encoder));
-	if (!device) {
-		printf("The HDR encoder runs on the device: it has no host build.\n");
-		return 1;
-	}
-	if (!valid_extent(width, height)) {
-		printf("An HDR file of this encoder is between 1 x 1 and 65535 x 65535 pixels, not %u x %u.\n", width, height);
-		return 1;
-	}
-	if (slot_count == 0 || slot_count > kMaxSlots) {
-		printf("An HDR encoder has 1 to %u slots, not %u.\n", kMaxSlots, slot_count);
-		return 1;
-	}
+	if (check_output_arguments("HDR", device, width, height, slot_count)) return 1;
 	hdr_state* state = (hdr_state*) calloc(1, sizeof(hdr_state));
 	if (!state) {
 		printf("Out of memory creating an HDR encoder.\n");
@@ -372,67 +330,20 @@ extern "C" int create_hdr_encoder(hdr_encoder_t* encoder, const device_t* device
 	encoder->run_length_coded = run_length_coded(width);
 	encoder->capacity = get_hdr_capacity(width, height);
 	encoder->state = state;
-	state->stream = device->stream;
-	state->record_units = 1 + (encoder->capacity + 15) / 16;
-	int failed = 0;
-	if (encoder->run_length_coded)
-		failed = hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, state->scan_bytes, (uint64_t*) NULL, (uint64_t*) NULL, (int) (height + 1), (hipStream_t) device->stream), "sizing the sum of the row sizes");
-	// one allocation: the header, then the scratch memory of every slot (raw widths need the record alone)
-	size_t pixels = encoder->run_length_coded ? (size_t) width * height : 0, rows = encoder->run_length_coded ? height : 0;
-	size_t total = 0, header_at = vkr_carve(&total, VKR_HDR_MAX_HEADER_SIZE), at[kMaxSlots][6];
-	for (uint32_t i = 0; i != slot_count; ++i) {
-		at[i][0] = vkr_carve(&total, pixels * sizeof(uint32_t));
-		at[i][1] = vkr_carve(&total, rows * 4 * sizeof(uint32_t));
-		at[i][2] = vkr_carve(&total, (rows + 1) * sizeof(uint64_t));
-		at[i][3] = vkr_carve(&total, (rows + 1) * sizeof(uint64_t));
-		at[i][4] = vkr_carve(&total, state->record_units * 16);
-		at[i][5] = vkr_carve(&total, state->scan_bytes ? state->scan_bytes : 1);
-	}
-	failed = failed || hip_failed(hipMalloc(&state->scratch, total), "allocating the scratch memory of an HDR encoder");
-	if (!failed) {
-		uint8_t* base = (uint8_t*) state->scratch;
-		state->header = base + header_at;
-		// k_hdr_copy_out copies whole 16-byte units, the rest of the size record and the tail behind the file included: no stale device memory reaches the host
-		failed = hip_failed(hipMemsetAsync(state->scratch, 0, total, (hipStream_t) device->stream), "clearing the scratch memory of an HDR encoder")
-			|| hip_failed(hipStreamSynchronize((hipStream_t) device->stream), "clearing the scratch memory of an HDR encoder")
-			|| hip_failed(hipMemcpy(state->header, header, VKR_HDR_MAX_HEADER_SIZE, hipMemcpyHostToDevice), "uploading the header of an HDR file");
-		for (uint32_t i = 0; i != slot_count && !failed; ++i) {
-			hdr_slot& slot = state->slots[i];
-			slot.rgbe = (uint32_t*) (base + at[i][0]);
-			slot.plane_sizes = (uint32_t*) (base + at[i][1]);
-			slot.row_sizes = (uint64_t*) (base + at[i][2]);
-			slot.row_offsets = (uint64_t*) (base + at[i][3]);
-			slot.record = base + at[i][4];
-			slot.scan_storage = base + at[i][5];
-			failed = hip_failed(hipHostMalloc((void**) &slot.staging, state->record_units * 16, hipHostMallocDefault), "allocating the pinned staging memory of an HDR encoder")
-				|| hip_failed(hipHostGetDevicePointer((void**) &slot.staging_device, slot.staging, 0), "mapping the staging memory of an HDR encoder")
-				|| hip_failed(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "creating the event of an HDR slot");
-		}
-	}
+	size_t scan_bytes = 0;
+	int failed = (encoder->run_length_coded && hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, scan_bytes, (uint64_t*) NULL, (uint64_t*) NULL, (int) (height + 1), (hipStream_t) device->stream), "sizing the sum of the row sizes"))
+		|| create_output_slots(&state->out, "HDR", device, slot_count, encoder->capacity, 0, scan_bytes, header, VKR_HDR_MAX_HEADER_SIZE, lay_out_slot, encoder);
 	if (failed) destroy_hdr_encoder(encoder);
 	return failed;
 }
 
 extern "C" int begin_hdr_encode(hdr_encoder_t* encoder, uint32_t slot, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, VkBool32 through_half, void* stream) {
-	if (check_slot(encoder, slot)) return 1;
-	hdr_slot& target = ((hdr_state*) encoder->state)->slots[slot];
-	if (enqueue_encode(encoder, slot, device_pixels, channel_count, row_stride_bytes, through_half, target.record + 16, encoder->capacity, (uint64_t*) target.record, true, stream)) return 1;
-	target.begun = true;
-	return 0;
+	if (check_output_slot(slots_of(encoder), slot)) return 1;
+	uint8_t* record = slots_of(encoder)->slots[slot].record;
+	return enqueue_encode(encoder, slot, device_pixels, channel_count, row_stride_bytes, through_half, record + 16, encoder->capacity, (uint64_t*) record, true, stream);
 }
 
-extern "C" int end_hdr_encode(hdr_encoder_t* encoder, uint32_t slot, const uint8_t** bytes, uint64_t* size) {
-	if (check_slot(encoder, slot)) return 1;
-	hdr_slot& source = ((hdr_state*) encoder->state)->slots[slot];
-	if (!source.begun) {
-		printf("end_hdr_encode() without begin_hdr_encode() on slot %u.\n", slot);
-		return 1;
-	}
-	if (hip_failed(hipEventSynchronize(source.done), "waiting for an HDR encode")) return 1;
-	*size = *(const uint64_t*) source.staging;
-	*bytes = source.staging + 16;
-	return 0;
-}
+extern "C" int end_hdr_encode(hdr_encoder_t* encoder, uint32_t slot, const uint8_t** bytes, uint64_t* size) { return end_output_encode(slots_of(encoder), slot, bytes, size); }
 
 extern "C" int encode_hdr(hdr_encoder_t* encoder, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, VkBool32 through_half, const uint8_t** bytes, uint64_t* size) {
 	return begin_hdr_encode(encoder, 0, device_pixels, channel_count, row_stride_bytes, through_half, NULL) || end_hdr_encode(encoder, 0, bytes, size);
@@ -440,7 +351,7 @@ extern "C" int encode_hdr(hdr_encoder_t* encoder, const void* device_pixels, uin
 
 extern "C" int encode_hdr_on_device(hdr_encoder_t* encoder, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, VkBool32 through_half,
                                     void* device_out, uint64_t capacity, uint64_t* device_size_word, void* stream) {
-	if (check_slot(encoder, 0)) return 1;
+	if (check_output_slot(slots_of(encoder), 0)) return 1;
 	if (!device_out || !device_size_word) {
 		printf("encode_hdr_on_device() needs device memory for the file and for its size.\n");
 		return 1;

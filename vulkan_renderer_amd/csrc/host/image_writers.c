@@ -326,6 +326,18 @@ int write_hdr_rgb32f(const char* path, uint32_t width, uint32_t height, const fl
 	return failed;
 }
 
+int vkr_write_file(const char* path, const uint8_t* bytes, uint64_t size) {
+	FILE* file = (path && bytes) ? fopen(path, "wb") : NULL;
+	if (!file) {
+		printf("Failed to open %s for writing.\n", path ? path : "(null)");
+		return 1;
+	}
+	int failed = fwrite(bytes, 1, size, file) != size;
+	failed |= fclose(file) != 0;
+	if (failed) printf("Failed to write %s.\n", path);
+	return failed;
+}
+
 /* ---- screenshots --------------------------------------------------------------------- */
 
 float half_to_float(uint16_t half) {

@@ -2,6 +2,7 @@
    Huffman code words from the specifications of ITU-T T.81 Annex K, the 607-byte file header, the worst-case size and
    the file writer.  The kernels are csrc/jpeg_encoder.hip. */
 #include "vkr_jpeg_tables.h"
+#include "vkr_internal.h"
 #include <stdio.h>
 #include <string.h>
 
@@ -156,14 +157,4 @@ int get_jpeg_header(uint8_t header[VKR_JPEG_HEADER_SIZE], uint32_t width, uint32
 	return 0;
 }
 
-int write_jpeg(const char* path, const uint8_t* bytes, uint64_t size) {
-	FILE* file = (path && bytes) ? fopen(path, "wb") : NULL;
-	if (!file) {
-		printf("Failed to open %s for writing.\n", path ? path : "(null)");
-		return 1;
-	}
-	int failed = fwrite(bytes, 1, size, file) != size;
-	failed |= fclose(file) != 0;
-	if (failed) printf("Failed to write %s.\n", path);
-	return failed;
-}
+int write_jpeg(const char* path, const uint8_t* bytes, uint64_t size) { return vkr_write_file(path, bytes, size); }

@@ -36,6 +36,10 @@ void vkr_host_free_pinned(void* pointer);
 int vkr_copy_to_device_async(void* device_pointer, const void* host, size_t size, const device_t* device);
 int vkr_copy_to_host(void* host, const void* device_pointer, size_t size, const device_t* device);
 
+/*! image_writers.c: what write_jpeg(), write_hdr_file() and write_png_file() are.  Writes the `size` bytes to a new file
+	at `path`; 1, behind a message, if that fails */
+int vkr_write_file(const char* path, const uint8_t* bytes, uint64_t size);
+
 /*! ltc_table.c: what load_ltc_table() and fit_ltc_table() share.  Quantises fresnel_count * resolution^2 fits of five
 	floats (the layout of the fit<i>.dat files) to host_rgba / host_rg, uploads them and sets the lookup constants.
 	Overwrites *table; on failure prints the reason, leaves it zeroed and returns 1. */

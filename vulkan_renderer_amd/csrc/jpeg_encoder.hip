@@ -6,18 +6,16 @@
 //   k_jpeg_pack             every data unit writes its bits at its offset
 //   k_jpeg_count_stuffing   0xFF bytes per chunk of VKR_JPEG_STUFFING_CHUNK bytes; hipcub exclusive sum
 //   k_jpeg_stuff            header, bytes with the inserted zeros, EOI, size word
-//   k_jpeg_copy_out         the size record and that many bytes into the slot's pinned staging memory
+//   k_copy_record_out       (output_slots.hip) the size record and that many bytes into the slot's pinned staging memory
 // This unit is compiled without contraction whatever the arithmetic mode of the pass: the bytes are the interface.
 #include "vkr_jpeg.h"
 #include "host/vkr_jpeg_tables.h"
-#include "host/vkr_internal.h"
-#include <hip/hip_runtime.h>
+#include "output_slots.h"
 #include <hipcub/hipcub.hpp>
 
 namespace {
 
 constexpr uint32_t kChunk = VKR_JPEG_STUFFING_CHUNK;
-constexpr uint32_t kMaxSlots = VKR_MAX_FRAMES_IN_FLIGHT + 1;
 
 struct jpeg_geometry {
 	uint32_t width, height, mcus_x, data_unit_count, subsampled;
@@ -326,35 +324,36 @@ __global__ void __launch_bounds__(256) k_jpeg_stuff(const uint32_t* words, const
 	}
 }
 
-// record: the size in its first 8 of 16 bytes, then the file.  Sixteen bytes per lane into host memory.
-__global__ void __launch_bounds__(256) k_jpeg_copy_out(const uint4* record, uint4* staging, uint64_t capacity_units) {
-	uint64_t units = min(1 + (*(const uint64_t*) record + 15) / 16, capacity_units);
-	for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < units; i += (uint64_t) gridDim.x * 256) staging[i] = record[i];
-}
-
 // ---- the encoder ------------------------------------------------------------------------------------------------------
 
+// the scratch memory of a slot besides what output_slots.h keeps
 struct jpeg_slot {
 	int16_t* coefficients;
 	uint64_t *lengths, *offsets;
 	uint32_t *words, *chunk_counts, *chunk_offsets;
-	uint8_t* record;
-	void* scan_storage;
-	// pinned host memory with the layout of record, and its address on the device
-	uint8_t *staging, *staging_device;
-	hipEvent_t done;
-	bool begun;
 };
 
 struct jpeg_state {
-	void* stream;
+	// (what its slots share: the vkr_jpeg_tables_t)
+	output_slots out;
 	jpeg_geometry geo;
-	vkr_jpeg_tables_t* tables;
-	uint64_t word_capacity, chunk_capacity, record_units;
-	size_t scan_bytes;
-	void* scratch;
-	jpeg_slot slots[kMaxSlots];
+	uint64_t word_capacity, chunk_capacity;
+	jpeg_slot slots[kMaxOutputSlots];
 };
+
+output_slots* slots_of(const jpeg_encoder_t* encoder) { return encoder && encoder->state ? &((jpeg_state*) encoder->state)->out : NULL; }
+
+void lay_out_slot(output_carver& carve, void* jpeg_state_pointer, uint32_t slot_index) {
+	jpeg_state* state = (jpeg_state*) jpeg_state_pointer;
+	jpeg_slot& slot = state->slots[slot_index];
+	size_t units = state->geo.data_unit_count;
+	carve.take(slot.coefficients, units * 64);
+	carve.take(slot.lengths, units + 1);
+	carve.take(slot.offsets, units + 1);
+	carve.take(slot.words, state->word_capacity);
+	carve.take(slot.chunk_counts, state->chunk_capacity + 1);
+	carve.take(slot.chunk_offsets, state->chunk_capacity + 1);
+}
 
 int enqueue_encode(jpeg_encoder_t* encoder, uint32_t slot_index, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes,
                    uint8_t* out, uint64_t capacity, uint64_t* size_word, bool copy_out, void* stream_or_null) {
@@ -368,29 +367,28 @@ int enqueue_encode(jpeg_encoder_t* encoder, uint32_t slot_index, const void* dev
 		printf("A row stride of %llu bytes is less than a row of %u pixels of %u channels.\n", (unsigned long long) row_stride_bytes, encoder->width, channel_count);
 		return 1;
 	}
-	hipStream_t stream = (hipStream_t) (stream_or_null ? stream_or_null : state->stream);
-	jpeg_slot& slot = state->slots[slot_index];
+	hipStream_t stream;
+	if (begin_output_enqueue(&state->out, slot_index, stream_or_null, &stream)) return 1;
+	const jpeg_slot& slot = state->slots[slot_index];
+	uint8_t* scan_storage = state->out.slots[slot_index].scan_storage;
+	const vkr_jpeg_tables_t* tables = (const vkr_jpeg_tables_t*) state->out.shared;
 	const jpeg_geometry& geo = state->geo;
 	uint32_t units = geo.data_unit_count;
-	// the scratch memory of the slot is free once its previous encode is through
-	if (hip_failed(hipStreamWaitEvent(stream, slot.done, 0), "ordering a JPEG encode behind the slot's previous one")) return 1;
 	bool dwords = channel_count == 4 && ((uintptr_t) device_pixels % 4 == 0) && row_stride_bytes % 4 == 0;
-	if (dwords) k_jpeg_coefficients<true><<<block_count(units, 32), 256, 0, stream>>>((const uint8_t*) device_pixels, row_stride_bytes, channel_count, geo, state->tables, slot.coefficients);
-	else k_jpeg_coefficients<false><<<block_count(units, 32), 256, 0, stream>>>((const uint8_t*) device_pixels, row_stride_bytes, channel_count, geo, state->tables, slot.coefficients);
-	k_jpeg_lengths<<<block_count((uint64_t) units + 1, 256), 256, 0, stream>>>(slot.coefficients, geo, state->tables, slot.lengths);
-	size_t scan_bytes = state->scan_bytes;
-	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(slot.scan_storage, scan_bytes, slot.lengths, slot.offsets, (int) (units + 1), stream), "summing the lengths of the data units")) return 1;
+	if (dwords) k_jpeg_coefficients<true><<<block_count(units, 32), 256, 0, stream>>>((const uint8_t*) device_pixels, row_stride_bytes, channel_count, geo, tables, slot.coefficients);
+	else k_jpeg_coefficients<false><<<block_count(units, 32), 256, 0, stream>>>((const uint8_t*) device_pixels, row_stride_bytes, channel_count, geo, tables, slot.coefficients);
+	k_jpeg_lengths<<<block_count((uint64_t) units + 1, 256), 256, 0, stream>>>(slot.coefficients, geo, tables, slot.lengths);
+	size_t scan_bytes = state->out.scan_bytes;
+	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(scan_storage, scan_bytes, slot.lengths, slot.offsets, (int) (units + 1), stream), "summing the lengths of the data units")) return 1;
 	const uint64_t* total_bits = slot.offsets + units;
 	k_jpeg_zero_words<<<256, 256, 0, stream>>>(slot.words, total_bits, state->word_capacity);
-	k_jpeg_pack<<<block_count(units, 256), 256, 0, stream>>>(slot.coefficients, geo, state->tables, slot.offsets, slot.words);
+	k_jpeg_pack<<<block_count(units, 256), 256, 0, stream>>>(slot.coefficients, geo, tables, slot.offsets, slot.words);
 	k_jpeg_count_stuffing<<<block_count(state->chunk_capacity + 1, 256), 256, 0, stream>>>(slot.words, total_bits, slot.chunk_counts, state->chunk_capacity);
-	scan_bytes = state->scan_bytes;
-	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(slot.scan_storage, scan_bytes, slot.chunk_counts, slot.chunk_offsets, (int) (state->chunk_capacity + 1), stream), "summing the stuffed bytes")) return 1;
+	scan_bytes = state->out.scan_bytes;
+	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(scan_storage, scan_bytes, slot.chunk_counts, slot.chunk_offsets, (int) (state->chunk_capacity + 1), stream), "summing the stuffed bytes")) return 1;
 	uint64_t lanes = state->chunk_capacity > VKR_JPEG_HEADER_SIZE ? state->chunk_capacity : VKR_JPEG_HEADER_SIZE;
-	k_jpeg_stuff<<<block_count(lanes, 256), 256, 0, stream>>>(slot.words, total_bits, slot.chunk_offsets, state->tables, out, capacity, size_word, state->chunk_capacity);
-	if (copy_out) k_jpeg_copy_out<<<128, 256, 0, stream>>>((const uint4*) slot.record, (uint4*) slot.staging_device, state->record_units);
-	if (hip_failed(hipGetLastError(), "encoding a JPEG")) return 1;
-	return hip_failed(hipEventRecord(slot.done, stream), "recording the end of a JPEG encode");
+	k_jpeg_stuff<<<block_count(lanes, 256), 256, 0, stream>>>(slot.words, total_bits, slot.chunk_offsets, tables, out, capacity, size_word, state->chunk_capacity);
+	return finish_output_enqueue(&state->out, slot_index, stream, copy_out ? 128 : 0);
 }
 
 }  // namespace
@@ -398,15 +396,7 @@ int enqueue_encode(jpeg_encoder_t* encoder, uint32_t slot_index, const void* dev
 extern "C" void destroy_jpeg_encoder(jpeg_encoder_t* encoder) {
 	jpeg_state* state = encoder ? (jpeg_state*) encoder->state : NULL;
 	if (state) {
-		for (uint32_t i = 0; i != kMaxSlots; ++i) {
-			jpeg_slot& slot = state->slots[i];
-			if (slot.done) {
-				(void) hipEventSynchronize(slot.done);
-				(void) hipEventDestroy(slot.done);
-			}
-			if (slot.staging) (void) hipHostFree(slot.staging);
-		}
-		if (state->scratch) (void) hipFree(state->scratch);
+		destroy_output_slots(&state->out);
 		free(state);
 	}
 	if (encoder) memset(encoder, 0, sizeof(*encoder));
@@ -414,18 +404,7 @@ extern "C" void destroy_jpeg_encoder(jpeg_encoder_t* encoder) {
 
 extern "C" int create_jpeg_encoder(jpeg_encoder_t* encoder, const device_t* device, uint32_t width, uint32_t height, int32_t quality, uint32_t slot_count) {
 	memset(encoder, 0, sizeof(*encoder));
-	if (!device) {
-		printf("The JPEG encoder runs on the device: it has no host build.\n");
-		return 1;
-	}
-	if (width == 0 || height == 0 || width > 65535 || height > 65535) {
-		printf("A JPEG is between 1 x 1 and 65535 x 65535 pixels, not %u x %u.\n", width, height);
-		return 1;
-	}
-	if (slot_count == 0 || slot_count > kMaxSlots) {
-		printf("A JPEG encoder has 1 to %u slots, not %u.\n", kMaxSlots, slot_count);
-		return 1;
-	}
+	if (check_output_arguments("JPEG", device, width, height, slot_count)) return 1;
 	jpeg_state* state = (jpeg_state*) calloc(1, sizeof(jpeg_state));
 	vkr_jpeg_tables_t* tables = (vkr_jpeg_tables_t*) malloc(sizeof(vkr_jpeg_tables_t));
 	if (!state || !tables) {
@@ -441,80 +420,27 @@ extern "C" int create_jpeg_encoder(jpeg_encoder_t* encoder, const device_t* devi
 	encoder->capacity = get_jpeg_capacity(width, height, quality);
 	encoder->state = state;
 	uint32_t mcu = tables->subsampled ? 16 : 8, units = encoder->data_unit_count;
-	state->stream = device->stream;
 	state->geo = {width, height, (width + mcu - 1) / mcu, units, tables->subsampled};
 	// the packed stream: whole chunks, so that the stuffing kernels load sixteen bytes at a time without a guard
 	uint64_t packed_bytes = (vkr_jpeg_worst_case_bits(units) + 7) / 8 + 1;
 	state->chunk_capacity = (packed_bytes + kChunk - 1) / kChunk;
 	state->word_capacity = state->chunk_capacity * (kChunk / 4);
-	state->record_units = 1 + (encoder->capacity + 15) / 16;
 	size_t lengths_bytes = 0, counts_bytes = 0;
 	int failed = hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, lengths_bytes, (uint64_t*) NULL, (uint64_t*) NULL, (int) (units + 1), (hipStream_t) device->stream), "sizing the sum of the lengths")
-		|| hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, counts_bytes, (uint32_t*) NULL, (uint32_t*) NULL, (int) (state->chunk_capacity + 1), (hipStream_t) device->stream), "sizing the sum of the stuffed bytes");
-	state->scan_bytes = lengths_bytes > counts_bytes ? lengths_bytes : counts_bytes;
-	// one allocation: the tables, then the scratch memory of every slot
-	size_t total = 0, tables_at = vkr_carve(&total, sizeof(vkr_jpeg_tables_t)), at[kMaxSlots][8];
-	for (uint32_t i = 0; i != slot_count; ++i) {
-		at[i][0] = vkr_carve(&total, (size_t) units * 64 * sizeof(int16_t));
-		at[i][1] = vkr_carve(&total, ((size_t) units + 1) * sizeof(uint64_t));
-		at[i][2] = vkr_carve(&total, ((size_t) units + 1) * sizeof(uint64_t));
-		at[i][3] = vkr_carve(&total, state->word_capacity * sizeof(uint32_t));
-		at[i][4] = vkr_carve(&total, (state->chunk_capacity + 1) * sizeof(uint32_t));
-		at[i][5] = vkr_carve(&total, (state->chunk_capacity + 1) * sizeof(uint32_t));
-		at[i][6] = vkr_carve(&total, state->record_units * 16);
-		at[i][7] = vkr_carve(&total, state->scan_bytes ? state->scan_bytes : 1);
-	}
-	failed = failed || hip_failed(hipMalloc(&state->scratch, total), "allocating the scratch memory of a JPEG encoder");
-	if (!failed) {
-		uint8_t* base = (uint8_t*) state->scratch;
-		state->tables = (vkr_jpeg_tables_t*) (base + tables_at);
-		failed = hip_failed(hipMemcpy(state->tables, tables, sizeof(vkr_jpeg_tables_t), hipMemcpyHostToDevice), "uploading the JPEG tables");
-		for (uint32_t i = 0; i != slot_count && !failed; ++i) {
-			jpeg_slot& slot = state->slots[i];
-			slot.coefficients = (int16_t*) (base + at[i][0]);
-			slot.lengths = (uint64_t*) (base + at[i][1]);
-			slot.offsets = (uint64_t*) (base + at[i][2]);
-			slot.words = (uint32_t*) (base + at[i][3]);
-			slot.chunk_counts = (uint32_t*) (base + at[i][4]);
-			slot.chunk_offsets = (uint32_t*) (base + at[i][5]);
-			slot.record = base + at[i][6];
-			slot.scan_storage = base + at[i][7];
-			failed = hip_failed(hipHostMalloc((void**) &slot.staging, state->record_units * 16, hipHostMallocDefault), "allocating the pinned staging memory of a JPEG encoder")
-				|| hip_failed(hipHostGetDevicePointer((void**) &slot.staging_device, slot.staging, 0), "mapping the staging memory of a JPEG encoder")
-				|| hip_failed(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "creating the event of a JPEG slot");
-		}
-	}
+		|| hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, counts_bytes, (uint32_t*) NULL, (uint32_t*) NULL, (int) (state->chunk_capacity + 1), (hipStream_t) device->stream), "sizing the sum of the stuffed bytes")
+		|| create_output_slots(&state->out, "JPEG", device, slot_count, encoder->capacity, 0, lengths_bytes > counts_bytes ? lengths_bytes : counts_bytes, tables, sizeof(vkr_jpeg_tables_t), lay_out_slot, state);
 	free(tables);
 	if (failed) destroy_jpeg_encoder(encoder);
 	return failed;
 }
 
-static int check_slot(const jpeg_encoder_t* encoder, uint32_t slot) {
-	if (encoder && encoder->state && slot < encoder->slot_count) return 0;
-	printf("Slot %u is not a slot of this JPEG encoder.\n", slot);
-	return 1;
-}
-
 extern "C" int begin_jpeg_encode(jpeg_encoder_t* encoder, uint32_t slot, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, void* stream) {
-	if (check_slot(encoder, slot)) return 1;
-	jpeg_slot& target = ((jpeg_state*) encoder->state)->slots[slot];
-	if (enqueue_encode(encoder, slot, device_pixels, channel_count, row_stride_bytes, target.record + 16, encoder->capacity, (uint64_t*) target.record, true, stream)) return 1;
-	target.begun = true;
-	return 0;
+	if (check_output_slot(slots_of(encoder), slot)) return 1;
+	uint8_t* record = slots_of(encoder)->slots[slot].record;
+	return enqueue_encode(encoder, slot, device_pixels, channel_count, row_stride_bytes, record + 16, encoder->capacity, (uint64_t*) record, true, stream);
 }
 
-extern "C" int end_jpeg_encode(jpeg_encoder_t* encoder, uint32_t slot, const uint8_t** bytes, uint64_t* size) {
-	if (check_slot(encoder, slot)) return 1;
-	jpeg_slot& source = ((jpeg_state*) encoder->state)->slots[slot];
-	if (!source.begun) {
-		printf("end_jpeg_encode() without begin_jpeg_encode() on slot %u.\n", slot);
-		return 1;
-	}
-	if (hip_failed(hipEventSynchronize(source.done), "waiting for a JPEG encode")) return 1;
-	*size = *(const uint64_t*) source.staging;
-	*bytes = source.staging + 16;
-	return 0;
-}
+extern "C" int end_jpeg_encode(jpeg_encoder_t* encoder, uint32_t slot, const uint8_t** bytes, uint64_t* size) { return end_output_encode(slots_of(encoder), slot, bytes, size); }
 
 extern "C" int encode_jpeg(jpeg_encoder_t* encoder, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, const uint8_t** bytes, uint64_t* size) {
 	return begin_jpeg_encode(encoder, 0, device_pixels, channel_count, row_stride_bytes, NULL) || end_jpeg_encode(encoder, 0, bytes, size);
@@ -522,7 +448,7 @@ extern "C" int encode_jpeg(jpeg_encoder_t* encoder, const void* device_pixels, u
 
 extern "C" int encode_jpeg_on_device(jpeg_encoder_t* encoder, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes,
                                      void* device_out, uint64_t capacity, uint64_t* device_size_word, void* stream) {
-	if (check_slot(encoder, 0)) return 1;
+	if (check_output_slot(slots_of(encoder), 0)) return 1;
 	if (!device_out || !device_size_word) {
 		printf("encode_jpeg_on_device() needs device memory for the file and for its size.\n");
 		return 1;

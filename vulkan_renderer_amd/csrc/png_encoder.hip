@@ -11,17 +11,15 @@
 //   k_png_adler       the Adler-32 from the units' sums
 //   k_png_frame       one workgroup per segment: chunk length, type and CRC-32 (slices per lane, combined by products
 //                     with x^(8 n) mod P), signature, IHDR, IEND, size word
-//   k_png_copy_out    the size record and that many bytes into the slot's pinned staging memory
+//   k_copy_record_out (output_slots.hip) the size record and that many bytes into the slot's pinned staging memory
 // The probe of the header enters behind the filter with a stream of the caller's.
 #include "vkr_png.h"
-#include "host/vkr_internal.h"
-#include <hip/hip_runtime.h>
+#include "output_slots.h"
 #include <hipcub/hipcub.hpp>
 
 namespace {
 
 constexpr uint32_t kUnit = VKR_PNG_UNIT;
-constexpr uint32_t kMaxSlots = VKR_MAX_FRAMES_IN_FLIGHT + 1;
 constexpr uint32_t kLiterals = 286, kDistances = 30, kSymbols = kLiterals + kDistances, kMetaSymbols = 19;
 constexpr uint32_t kEndOfBlock = 256, kMaxMatch = 258;
 // words of block header per segment: 3 + 14 + 57 + 316 * 7 bits at most
@@ -700,13 +698,7 @@ __global__ void __launch_bounds__(256) k_png_frame(png_shape shape, const uint64
 	if (threadIdx.x == 0u) store_big_endian(chunk + 8u + data_size, combined);
 }
 
-// record: the size in its first 8 of 16 bytes, then the file.  Sixteen bytes per lane into host memory.
-__global__ void __launch_bounds__(256) k_png_copy_out(const uint4* record, uint4* staging, uint64_t capacity_units) {
-	uint64_t units = min(1 + (*(const uint64_t*) record + 15) / 16, capacity_units);
-	for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < units; i += (uint64_t) gridDim.x * 256) staging[i] = record[i];
-}
-
-// the file into memory of the caller's, of any alignment: nothing at or beyond out + capacity is written
+// the file from the slot's record (output_slots.h) into memory of the caller's, of any alignment: nothing at or beyond out + capacity is written
 __global__ void __launch_bounds__(256) k_png_copy_on_device(const uint8_t* record, uint8_t* out, uint64_t capacity, uint64_t* size_word) {
 	uint64_t size = *(const uint64_t*) record, count = min(size, capacity);
 	for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t) gridDim.x * 256) out[i] = record[16u + i];
@@ -715,31 +707,40 @@ __global__ void __launch_bounds__(256) k_png_copy_on_device(const uint8_t* recor
 
 // ---- the encoder ------------------------------------------------------------------------------------------------------
 
+// the scratch memory of a slot besides what output_slots.h keeps
 struct png_slot {
 	uint8_t* filtered;
 	uint16_t* tokens;
 	uint32_t *histograms, *tables, *headers, *unit_sums;
 	png_segment* segments;
 	uint64_t *chunk_sizes, *chunk_offsets, *unit_bits, *unit_offsets;
-	uint8_t* record;
-	void* scan_storage;
-	// pinned host memory with the layout of record, and its address on the device
-	uint8_t *staging, *staging_device;
-	hipEvent_t done;
-	bool begun;
 };
 
 struct png_state {
-	void* stream;
+	// (what its slots share: the header)
+	output_slots out;
 	png_shape shape;
-	uint8_t* header;
-	uint64_t record_units;
-	size_t scan_bytes;
-	void* scratch;
-	png_slot slots[kMaxSlots];
+	png_slot slots[kMaxOutputSlots];
 };
 
-bool valid_extent(uint32_t width, uint32_t height) { return width != 0 && height != 0 && width <= 65535 && height <= 65535; }
+output_slots* slots_of(const png_encoder_t* encoder) { return encoder && encoder->state ? &((png_state*) encoder->state)->out : NULL; }
+
+void lay_out_slot(output_carver& carve, void* png_state_pointer, uint32_t slot_index) {
+	png_state* state = (png_state*) png_state_pointer;
+	png_slot& slot = state->slots[slot_index];
+	const size_t segments = state->shape.segment_count, units = state->shape.unit_count;
+	carve.take(slot.filtered, state->shape.stream_size);
+	carve.take(slot.tokens, state->shape.stream_size);
+	carve.take(slot.histograms, segments * kSymbols);
+	carve.take(slot.tables, segments * kSymbols);
+	carve.take(slot.headers, segments * kHeaderWords);
+	carve.take(slot.unit_sums, units * 2);
+	carve.take(slot.segments, segments);
+	carve.take(slot.chunk_sizes, segments + 1);
+	carve.take(slot.chunk_offsets, segments + 1);
+	carve.take(slot.unit_bits, units + 1);
+	carve.take(slot.unit_offsets, units + 1);
+}
 
 bool valid_stream(uint32_t row_length, uint32_t rows) { return row_length != 0 && rows != 0 && row_length <= kMaxProbeRowLength && rows <= 65535; }
 
@@ -802,13 +803,14 @@ int enqueue_encode(png_encoder_t* encoder, uint32_t slot_index, const void* devi
 		printf("A row stride of %llu bytes is less than a row of %u pixels of %u bytes.\n", (unsigned long long) row_stride_bytes, encoder->width, channel_count);
 		return 1;
 	}
-	hipStream_t stream = (hipStream_t) (stream_or_null ? stream_or_null : state->stream);
-	png_slot& slot = state->slots[slot_index];
+	hipStream_t stream;
+	if (begin_output_enqueue(&state->out, slot_index, stream_or_null, &stream)) return 1;
+	const png_slot& slot = state->slots[slot_index];
 	const png_shape& shape = state->shape;
-	// the scratch memory of the slot is free once its previous encode is through
-	if (hip_failed(hipStreamWaitEvent(stream, slot.done, 0), "ordering a PNG encode behind the slot's previous one")) return 1;
+	uint8_t *record = state->out.slots[slot_index].record, *scan_storage = state->out.slots[slot_index].scan_storage;
+	const uint64_t record_units = state->out.record_units;
 	// bits are ORed into the file and counts added to the histograms
-	if (hip_failed(hipMemsetAsync(slot.record, 0, state->record_units * 16, stream), "clearing a PNG file")
+	if (hip_failed(hipMemsetAsync(record, 0, record_units * 16, stream), "clearing a PNG file")
 		|| hip_failed(hipMemsetAsync(slot.histograms, 0, (size_t) shape.segment_count * kSymbols * sizeof(uint32_t), stream), "clearing the counts of a PNG encode")) return 1;
 	if (!from_stream) {
 		png_source source = {(const uint8_t*) device_pixels, row_stride_bytes, channel_count};
@@ -816,27 +818,19 @@ int enqueue_encode(png_encoder_t* encoder, uint32_t slot_index, const void* devi
 	}
 	k_png_parse<<<shape.unit_count, 256, 0, stream>>>(shape, slot.filtered, slot.tokens, slot.histograms, slot.unit_sums);
 	k_png_codes<<<shape.segment_count, 256, 0, stream>>>(shape, slot.histograms, slot.tables, slot.headers, slot.segments, slot.chunk_sizes);
-	size_t scan_bytes = state->scan_bytes;
-	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(slot.scan_storage, scan_bytes, slot.chunk_sizes, slot.chunk_offsets, (int) (shape.segment_count + 1), stream), "summing the sizes of the chunks")) return 1;
+	size_t scan_bytes = state->out.scan_bytes;
+	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(scan_storage, scan_bytes, slot.chunk_sizes, slot.chunk_offsets, (int) (shape.segment_count + 1), stream), "summing the sizes of the chunks")) return 1;
 	k_png_unit_bits<<<shape.unit_count, 256, 0, stream>>>(shape, slot.filtered, slot.tokens, slot.tables, slot.unit_bits);
-	scan_bytes = state->scan_bytes;
-	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(slot.scan_storage, scan_bytes, slot.unit_bits, slot.unit_offsets, (int) (shape.unit_count + 1), stream), "summing the bits of the units")) return 1;
-	uint8_t* file = slot.record + 16;
+	scan_bytes = state->out.scan_bytes;
+	if (hip_failed(hipcub::DeviceScan::ExclusiveSum(scan_storage, scan_bytes, slot.unit_bits, slot.unit_offsets, (int) (shape.unit_count + 1), stream), "summing the bits of the units")) return 1;
+	uint8_t* file = record + 16;
 	// (the words of the file and the spare sixteen bytes behind it)
-	bit_stream words = {(uint32_t*) file, state->record_units * 4};
+	bit_stream words = {(uint32_t*) file, record_units * 4};
 	k_png_pack<<<shape.unit_count, 256, 0, stream>>>(shape, slot.filtered, slot.tokens, slot.tables, slot.headers, slot.segments, slot.chunk_offsets, slot.unit_offsets, words);
 	k_png_adler<<<1, 256, 0, stream>>>(shape, slot.unit_sums, slot.chunk_offsets, file);
-	k_png_frame<<<shape.segment_count, 256, 0, stream>>>(shape, slot.chunk_offsets, state->header, file, (uint64_t*) slot.record);
-	if (copy_out) k_png_copy_out<<<256, 256, 0, stream>>>((const uint4*) slot.record, (uint4*) slot.staging_device, state->record_units);
-	else k_png_copy_on_device<<<256, 256, 0, stream>>>(slot.record, out, capacity, size_word);
-	if (hip_failed(hipGetLastError(), "encoding a PNG file")) return 1;
-	return hip_failed(hipEventRecord(slot.done, stream), "recording the end of a PNG encode");
-}
-
-int check_slot(const png_encoder_t* encoder, uint32_t slot) {
-	if (encoder && encoder->state && slot < encoder->slot_count) return 0;
-	printf("Slot %u is not a slot of this PNG encoder.\n", slot);
-	return 1;
+	k_png_frame<<<shape.segment_count, 256, 0, stream>>>(shape, slot.chunk_offsets, state->out.shared, file, (uint64_t*) record);
+	if (!copy_out) k_png_copy_on_device<<<256, 256, 0, stream>>>(record, out, capacity, size_word);
+	return finish_output_enqueue(&state->out, slot_index, stream, copy_out ? 256 : 0);
 }
 
 int create_for_stream(png_encoder_t* encoder, const device_t* device, uint32_t row_length, uint32_t rows, uint32_t header_width, uint32_t header_height, uint32_t slot_count) {
@@ -854,59 +848,12 @@ int create_for_stream(png_encoder_t* encoder, const device_t* device, uint32_t r
 	encoder->segment_count = shape.segment_count;
 	encoder->capacity = capacity_of(shape);
 	encoder->state = state;
-	state->stream = device->stream;
 	state->shape = shape;
-	state->record_units = 1 + (encoder->capacity + 15) / 16;
-	const uint64_t segments = shape.segment_count, units = shape.unit_count;
 	size_t unit_scan = 0, chunk_scan = 0;
-	int failed = hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, unit_scan, (uint64_t*) NULL, (uint64_t*) NULL, (int) (units + 1), (hipStream_t) device->stream), "sizing the sum of the unit bits")
-		|| hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, chunk_scan, (uint64_t*) NULL, (uint64_t*) NULL, (int) (segments + 1), (hipStream_t) device->stream), "sizing the sum of the chunk sizes");
-	state->scan_bytes = unit_scan > chunk_scan ? unit_scan : chunk_scan;
-	// one allocation: the header, then the scratch memory of every slot
-	size_t total = 0, header_at = vkr_carve(&total, VKR_PNG_HEADER_SIZE), at[kMaxSlots][13];
-	for (uint32_t i = 0; i != slot_count; ++i) {
-		at[i][0] = vkr_carve(&total, shape.stream_size);
-		at[i][1] = vkr_carve(&total, shape.stream_size * sizeof(uint16_t));
-		at[i][2] = vkr_carve(&total, segments * kSymbols * sizeof(uint32_t));
-		at[i][3] = vkr_carve(&total, segments * kSymbols * sizeof(uint32_t));
-		at[i][4] = vkr_carve(&total, segments * kHeaderWords * sizeof(uint32_t));
-		at[i][5] = vkr_carve(&total, units * 2 * sizeof(uint32_t));
-		at[i][6] = vkr_carve(&total, segments * sizeof(png_segment));
-		at[i][7] = vkr_carve(&total, (segments + 1) * sizeof(uint64_t));
-		at[i][8] = vkr_carve(&total, (segments + 1) * sizeof(uint64_t));
-		at[i][9] = vkr_carve(&total, (units + 1) * sizeof(uint64_t));
-		at[i][10] = vkr_carve(&total, (units + 1) * sizeof(uint64_t));
-		// (k_png_pack ORs whole words: up to three bytes behind the last unit of sixteen are touched, with zeros)
-		at[i][11] = vkr_carve(&total, state->record_units * 16 + 16);
-		at[i][12] = vkr_carve(&total, state->scan_bytes ? state->scan_bytes : 1);
-	}
-	failed = failed || hip_failed(hipMalloc(&state->scratch, total), "allocating the scratch memory of a PNG encoder");
-	if (!failed) {
-		uint8_t* base = (uint8_t*) state->scratch;
-		state->header = base + header_at;
-		failed = hip_failed(hipMemsetAsync(state->scratch, 0, total, (hipStream_t) device->stream), "clearing the scratch memory of a PNG encoder")
-			|| hip_failed(hipStreamSynchronize((hipStream_t) device->stream), "clearing the scratch memory of a PNG encoder")
-			|| hip_failed(hipMemcpy(state->header, header, VKR_PNG_HEADER_SIZE, hipMemcpyHostToDevice), "uploading the header of a PNG file");
-		for (uint32_t i = 0; i != slot_count && !failed; ++i) {
-			png_slot& slot = state->slots[i];
-			slot.filtered = base + at[i][0];
-			slot.tokens = (uint16_t*) (base + at[i][1]);
-			slot.histograms = (uint32_t*) (base + at[i][2]);
-			slot.tables = (uint32_t*) (base + at[i][3]);
-			slot.headers = (uint32_t*) (base + at[i][4]);
-			slot.unit_sums = (uint32_t*) (base + at[i][5]);
-			slot.segments = (png_segment*) (base + at[i][6]);
-			slot.chunk_sizes = (uint64_t*) (base + at[i][7]);
-			slot.chunk_offsets = (uint64_t*) (base + at[i][8]);
-			slot.unit_bits = (uint64_t*) (base + at[i][9]);
-			slot.unit_offsets = (uint64_t*) (base + at[i][10]);
-			slot.record = base + at[i][11];
-			slot.scan_storage = base + at[i][12];
-			failed = hip_failed(hipHostMalloc((void**) &slot.staging, state->record_units * 16, hipHostMallocDefault), "allocating the pinned staging memory of a PNG encoder")
-				|| hip_failed(hipHostGetDevicePointer((void**) &slot.staging_device, slot.staging, 0), "mapping the staging memory of a PNG encoder")
-				|| hip_failed(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "creating the event of a PNG slot");
-		}
-	}
+	// (sixteen spare bytes behind the record: k_png_pack ORs whole words, so up to three bytes behind the last unit of sixteen are touched, with zeros)
+	int failed = hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, unit_scan, (uint64_t*) NULL, (uint64_t*) NULL, (int) (shape.unit_count + 1), (hipStream_t) device->stream), "sizing the sum of the unit bits")
+		|| hip_failed(hipcub::DeviceScan::ExclusiveSum(NULL, chunk_scan, (uint64_t*) NULL, (uint64_t*) NULL, (int) (shape.segment_count + 1), (hipStream_t) device->stream), "sizing the sum of the chunk sizes")
+		|| create_output_slots(&state->out, "PNG", device, slot_count, encoder->capacity, 16, unit_scan > chunk_scan ? unit_scan : chunk_scan, header, VKR_PNG_HEADER_SIZE, lay_out_slot, state);
 	if (failed) destroy_png_encoder(encoder);
 	return failed;
 }
@@ -914,39 +861,21 @@ int create_for_stream(png_encoder_t* encoder, const device_t* device, uint32_t r
 }  // namespace
 
 extern "C" int get_png_header(uint8_t header[VKR_PNG_HEADER_SIZE], uint32_t width, uint32_t height) {
-	if (!valid_extent(width, height)) return 1;
+	if (!valid_output_extent(width, height)) return 1;
 	make_header(header, width, height);
 	return 0;
 }
 
-extern "C" uint64_t get_png_capacity(uint32_t width, uint32_t height) { return valid_extent(width, height) ? capacity_of(shape_of(3 * width + 1, height)) : 0; }
+extern "C" uint64_t get_png_capacity(uint32_t width, uint32_t height) { return valid_output_extent(width, height) ? capacity_of(shape_of(3 * width + 1, height)) : 0; }
 
 extern "C" uint64_t get_png_stream_capacity(uint32_t row_length, uint32_t rows) { return valid_stream(row_length, rows) ? capacity_of(shape_of(row_length, rows)) : 0; }
 
-extern "C" int write_png_file(const char* path, const uint8_t* bytes, uint64_t size) {
-	FILE* file = (path && bytes) ? fopen(path, "wb") : NULL;
-	if (!file) {
-		printf("Failed to open %s for writing.\n", path ? path : "(null)");
-		return 1;
-	}
-	int failed = fwrite(bytes, 1, size, file) != size;
-	failed |= fclose(file) != 0;
-	if (failed) printf("Failed to write %s.\n", path);
-	return failed;
-}
+extern "C" int write_png_file(const char* path, const uint8_t* bytes, uint64_t size) { return vkr_write_file(path, bytes, size); }
 
 extern "C" void destroy_png_encoder(png_encoder_t* encoder) {
 	png_state* state = encoder ? (png_state*) encoder->state : NULL;
 	if (state) {
-		for (uint32_t i = 0; i != kMaxSlots; ++i) {
-			png_slot& slot = state->slots[i];
-			if (slot.done) {
-				(void) hipEventSynchronize(slot.done);
-				(void) hipEventDestroy(slot.done);
-			}
-			if (slot.staging) (void) hipHostFree(slot.staging);
-		}
-		if (state->scratch) (void) hipFree(state->scratch);
+		destroy_output_slots(&state->out);
 		free(state);
 	}
 	if (encoder) memset(encoder, 0, sizeof(*encoder));
@@ -954,42 +883,17 @@ extern "C" void destroy_png_encoder(png_encoder_t* encoder) {
 
 extern "C" int create_png_encoder(png_encoder_t* encoder, const device_t* device, uint32_t width, uint32_t height, uint32_t slot_count) {
 	memset(encoder, 0, sizeof(*encoder));
-	if (!device) {
-		printf("The PNG encoder runs on the device: it has no host build.\n");
-		return 1;
-	}
-	if (!valid_extent(width, height)) {
-		printf("A PNG file of this encoder is between 1 x 1 and 65535 x 65535 pixels, not %u x %u.\n", width, height);
-		return 1;
-	}
-	if (slot_count == 0 || slot_count > kMaxSlots) {
-		printf("A PNG encoder has 1 to %u slots, not %u.\n", kMaxSlots, slot_count);
-		return 1;
-	}
+	if (check_output_arguments("PNG", device, width, height, slot_count)) return 1;
 	encoder->width = width; encoder->height = height;
 	return create_for_stream(encoder, device, 3 * width + 1, height, width, height, slot_count);
 }
 
 extern "C" int begin_png_encode(png_encoder_t* encoder, uint32_t slot, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, void* stream) {
-	if (check_slot(encoder, slot)) return 1;
-	png_slot& target = ((png_state*) encoder->state)->slots[slot];
-	if (enqueue_encode(encoder, slot, device_pixels, channel_count, row_stride_bytes, false, NULL, 0, NULL, true, stream)) return 1;
-	target.begun = true;
-	return 0;
+	if (check_output_slot(slots_of(encoder), slot)) return 1;
+	return enqueue_encode(encoder, slot, device_pixels, channel_count, row_stride_bytes, false, NULL, 0, NULL, true, stream);
 }
 
-extern "C" int end_png_encode(png_encoder_t* encoder, uint32_t slot, const uint8_t** bytes, uint64_t* size) {
-	if (check_slot(encoder, slot)) return 1;
-	png_slot& source = ((png_state*) encoder->state)->slots[slot];
-	if (!source.begun) {
-		printf("end_png_encode() without begin_png_encode() on slot %u.\n", slot);
-		return 1;
-	}
-	if (hip_failed(hipEventSynchronize(source.done), "waiting for a PNG encode")) return 1;
-	*size = *(const uint64_t*) source.staging;
-	*bytes = source.staging + 16;
-	return 0;
-}
+extern "C" int end_png_encode(png_encoder_t* encoder, uint32_t slot, const uint8_t** bytes, uint64_t* size) { return end_output_encode(slots_of(encoder), slot, bytes, size); }
 
 extern "C" int encode_png(png_encoder_t* encoder, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes, const uint8_t** bytes, uint64_t* size) {
 	return begin_png_encode(encoder, 0, device_pixels, channel_count, row_stride_bytes, NULL) || end_png_encode(encoder, 0, bytes, size);
@@ -997,7 +901,7 @@ extern "C" int encode_png(png_encoder_t* encoder, const void* device_pixels, uin
 
 extern "C" int encode_png_on_device(png_encoder_t* encoder, const void* device_pixels, uint32_t channel_count, uint64_t row_stride_bytes,
                                     void* device_out, uint64_t capacity, uint64_t* device_size_word, void* stream) {
-	if (check_slot(encoder, 0)) return 1;
+	if (check_output_slot(slots_of(encoder), 0)) return 1;
 	if (!device_out || !device_size_word) {
 		printf("encode_png_on_device() needs device memory for the file and for its size.\n");
 		return 1;
@@ -1018,11 +922,8 @@ extern "C" int probe_png_stream(const device_t* device, const uint8_t* host_stre
 	const uint8_t* bytes = NULL;
 	uint64_t size = 0;
 	int failed = hip_failed(hipMemcpyAsync(state->slots[0].filtered, host_stream, state->shape.stream_size, hipMemcpyHostToDevice, (hipStream_t) device->stream), "uploading a filtered stream")
-		|| enqueue_encode(&encoder, 0, NULL, 3, 0, true, NULL, 0, NULL, true, NULL);
-	if (!failed) {
-		state->slots[0].begun = true;
-		failed = end_png_encode(&encoder, 0, &bytes, &size);
-	}
+		|| enqueue_encode(&encoder, 0, NULL, 3, 0, true, NULL, 0, NULL, true, NULL)
+		|| end_png_encode(&encoder, 0, &bytes, &size);
 	if (!failed) {
 		*out_size = size;
 		memcpy(out, bytes, size < out_capacity ? size : out_capacity);

@@ -242,6 +242,8 @@ class Renderer(HostScene):
 
     def __init__(self, hip_device=0, stream=None, fast_math=False, inline_rays=False, timing_stride=1, frames_in_flight=1, binary_traversal=False, arithmetic=None, band_count=0):
         super().__init__()
+        # the open JPEG, HDR and PNG encoders, and those that encode_jpeg(), encode_hdr() and encode_png() keep
+        self._file_encoders, self._file_encoder_cache = [], {}
         self.binary_traversal = binary_traversal
         self.exchange = None
         self.timing_stride = timing_stride
@@ -707,34 +709,47 @@ class Renderer(HostScene):
         self.app.screenshot.frame_bits = 0
         return out
 
-    # -- JPEG files (include/vkr_jpeg.h) ---------------------------------------------------
+    # -- JPEG, Radiance and PNG files (include/vkr_jpeg.h, vkr_hdr.h, vkr_png.h) ------------------
+    def _create_file_encoder(self, encoder_class, width, height, *arguments):
+        """An open encoder of that class for one extent (default: the frame's); `arguments`: what its constructor takes
+        behind the extent"""
+        e = self.app.swapchain.extent
+        encoder = encoder_class(self, int(width or e.width), int(height or e.height), *arguments)
+        self._file_encoders.append(encoder)
+        return encoder
+
+    def _cached_file_encoder(self, encoder_class, *key):
+        """The one-slot encoder of that class that is kept per `key`: the extent, for JPEG also the quality"""
+        key = (encoder_class,) + tuple(int(k) for k in key)
+        cache = self._file_encoder_cache
+        if key not in cache or cache[key].closed:
+            cache[key] = self._create_file_encoder(*key)
+        return cache[key]
+
+    def _encode_file(self, encoder_class, image_or_pointer, width, height, channel_count, row_stride_bytes, key=(), format_arguments=()):
+        """The file of a numpy image, which is uploaded, or of device memory at an address; key: what the cached encoder is
+        kept by besides the extent; format_arguments: what the format's C functions take besides the pixels"""
+        if isinstance(image_or_pointer, np.ndarray):
+            image = np.ascontiguousarray(image_or_pointer, encoder_class.DTYPE)
+            if image.ndim != 3 or image.shape[2] not in (3, 4):
+                raise ValueError("%s files are made from %s images of shape (height, width, 3 or 4)" % (encoder_class.FORMAT.upper(), encoder_class.DTYPE.__name__))
+            return self._cached_file_encoder(encoder_class, image.shape[1], image.shape[0], *key)._encode_image(image, 0, *format_arguments)
+        e = self.app.swapchain.extent
+        encoder = self._cached_file_encoder(encoder_class, width or e.width, height or e.height, *key)
+        encoder._begin(0, image_or_pointer, channel_count, row_stride_bytes, None, *format_arguments)
+        return encoder.end(0)
+
     def create_jpeg_encoder(self, width=None, height=None, quality=70, slot_count=1):
         """An encoder for frames of one extent (default: the frame's) and quality with `slot_count` output slots: a
         JpegEncoder, which exposes begin() and end() per slot.  The caller closes it (Renderer.close() closes what is left)."""
-        e = self.app.swapchain.extent
-        encoder = JpegEncoder(self, int(width or e.width), int(height or e.height), quality, slot_count)
-        self._jpeg_encoders = getattr(self, "_jpeg_encoders", []) + [encoder]
-        return encoder
-
-    def _cached_jpeg_encoder(self, width, height, quality):
-        cache = self.__dict__.setdefault("_jpeg_cache", {})
-        key = (int(width), int(height), int(quality))
-        if key not in cache or cache[key].closed:
-            cache[key] = self.create_jpeg_encoder(width, height, quality)
-        return cache[key]
+        return self._create_file_encoder(JpegEncoder, width, height, quality, slot_count)
 
     def encode_jpeg(self, image_or_pointer, quality=70, width=None, height=None, channel_count=4, row_stride_bytes=0):
         """The bytes of the JPEG file of an image - a uint8 array (height, width, 3 or 4), which is uploaded - or of
         device memory (an address; width, height default to the frame's extent; channel_count 3 or 4, rows
         row_stride_bytes apart).  Byte for byte what jpeg.encode() gives.  The encoder is kept for the next call with
         the same extent and quality."""
-        if isinstance(image_or_pointer, np.ndarray):
-            image = np.ascontiguousarray(image_or_pointer, np.uint8)
-            if image.ndim != 3 or image.shape[2] not in (3, 4):
-                raise ValueError("a JPEG is made from a uint8 image of shape (height, width, 3 or 4)")
-            return self._cached_jpeg_encoder(image.shape[1], image.shape[0], quality).encode_image(image)
-        e = self.app.swapchain.extent
-        return self._cached_jpeg_encoder(width or e.width, height or e.height, quality).encode(image_or_pointer, channel_count, row_stride_bytes)
+        return self._encode_file(JpegEncoder, image_or_pointer, width, height, channel_count, row_stride_bytes, key=(quality,))
 
     def read_jpeg(self, quality=70):
         """The current frame as a JPEG file: the sRGB-encoded frame of read_encoded(), encoded on the device, so that
@@ -744,34 +759,17 @@ class Renderer(HostScene):
             raise RuntimeError("encode_output failed")
         return self.encode_jpeg(self.app.render_targets.encoded, quality)
 
-    # -- Radiance files (include/vkr_hdr.h) --------------------------------------------------
     def create_hdr_encoder(self, width=None, height=None, slot_count=1):
         """An encoder for float frames of one extent (default: the frame's) with `slot_count` output slots: an HdrEncoder,
         which exposes begin() and end() per slot.  The caller closes it (Renderer.close() closes what is left)."""
-        e = self.app.swapchain.extent
-        encoder = HdrEncoder(self, int(width or e.width), int(height or e.height), slot_count)
-        self._hdr_encoders = getattr(self, "_hdr_encoders", []) + [encoder]
-        return encoder
-
-    def _cached_hdr_encoder(self, width, height):
-        cache = self.__dict__.setdefault("_hdr_cache", {})
-        key = (int(width), int(height))
-        if key not in cache or cache[key].closed:
-            cache[key] = self.create_hdr_encoder(width, height)
-        return cache[key]
+        return self._create_file_encoder(HdrEncoder, width, height, slot_count)
 
     def encode_hdr(self, image_or_pointer, through_half=False, width=None, height=None, channel_count=4, row_stride_bytes=0):
         """The bytes of the Radiance file of an image - a float32 array (height, width, 3 or 4), which is uploaded - or of
         device memory (an address; width, height default to the frame's extent; channel_count 3 or 4 floats, rows
         row_stride_bytes apart).  Byte for byte what hdr.encode() gives.  The encoder is kept for the next call with
         the same extent."""
-        if isinstance(image_or_pointer, np.ndarray):
-            image = np.ascontiguousarray(image_or_pointer, np.float32)
-            if image.ndim != 3 or image.shape[2] not in (3, 4):
-                raise ValueError("an HDR file is made from a float image of shape (height, width, 3 or 4)")
-            return self._cached_hdr_encoder(image.shape[1], image.shape[0]).encode_image(image, through_half=through_half)
-        e = self.app.swapchain.extent
-        return self._cached_hdr_encoder(width or e.width, height or e.height).encode(image_or_pointer, channel_count, row_stride_bytes, through_half)
+        return self._encode_file(HdrEncoder, image_or_pointer, width, height, channel_count, row_stride_bytes, format_arguments=(int(bool(through_half)),))
 
     def read_hdr(self, through_half=False):
         """The current radiance target as a Radiance file, encoded on the device, so that only the file crosses the bus;
@@ -780,34 +778,17 @@ class Renderer(HostScene):
             raise RuntimeError("finish_frames failed")
         return self.encode_hdr(self.app.render_targets.radiance, through_half)
 
-    # -- PNG files (include/vkr_png.h) -------------------------------------------------------
     def create_png_encoder(self, width=None, height=None, slot_count=1):
         """An encoder for 8-bit frames of one extent (default: the frame's) with `slot_count` output slots: a PngEncoder,
         which exposes begin() and end() per slot.  The caller closes it (Renderer.close() closes what is left)."""
-        e = self.app.swapchain.extent
-        encoder = PngEncoder(self, int(width or e.width), int(height or e.height), slot_count)
-        self._png_encoders = getattr(self, "_png_encoders", []) + [encoder]
-        return encoder
-
-    def _cached_png_encoder(self, width, height):
-        cache = self.__dict__.setdefault("_png_cache", {})
-        key = (int(width), int(height))
-        if key not in cache or cache[key].closed:
-            cache[key] = self.create_png_encoder(width, height)
-        return cache[key]
+        return self._create_file_encoder(PngEncoder, width, height, slot_count)
 
     def encode_png(self, image_or_pointer, width=None, height=None, channel_count=4, row_stride_bytes=0):
         """The bytes of the PNG file of an image - a uint8 array (height, width, 3 or 4), which is uploaded - or of device
         memory (an address; width, height default to the frame's extent; channel_count 3 or 4 bytes, rows
         row_stride_bytes apart).  Byte for byte what png.encode() gives.  The encoder is kept for the next call with the
         same extent."""
-        if isinstance(image_or_pointer, np.ndarray):
-            image = np.ascontiguousarray(image_or_pointer, np.uint8)
-            if image.ndim != 3 or image.shape[2] not in (3, 4):
-                raise ValueError("a PNG file is made from a uint8 image of shape (height, width, 3 or 4)")
-            return self._cached_png_encoder(image.shape[1], image.shape[0]).encode_image(image)
-        e = self.app.swapchain.extent
-        return self._cached_png_encoder(width or e.width, height or e.height).encode(image_or_pointer, channel_count, row_stride_bytes)
+        return self._encode_file(PngEncoder, image_or_pointer, width, height, channel_count, row_stride_bytes)
 
     def read_png(self, output_linear_rgb=False):
         """The current frame as a PNG file of its sRGB8 encoding (the RGB of read_encoded()), encoded on the device, so that
@@ -879,155 +860,17 @@ class Renderer(HostScene):
     def close(self):
         for statistics in list(getattr(self, "_statistics", ())):
             statistics.close()
-        for encoder in getattr(self, "_jpeg_encoders", ()):
-            encoder.close()
-        for encoder in getattr(self, "_hdr_encoders", ()):
-            encoder.close()
-        for encoder in getattr(self, "_png_encoders", ()):
+        for encoder in self._file_encoders:
             encoder.close()
         super().close()
-
-
-class JpegEncoder:
-    """create_jpeg_encoder() of include/vkr_jpeg.h for a Renderer: encode() for one frame at a time, begin() and end()
-    per slot for frames in flight, encode_on_device() for a file that stays in device memory."""
-
-    def __init__(self, owner, width, height, quality=70, slot_count=1):
-        self.owner, self.lib = owner, owner.lib
-        self.encoder = capi.JpegEncoder()
-        self.closed = True
-        if self.lib.create_jpeg_encoder(C.byref(self.encoder), owner._dev(), width, height, int(quality), slot_count):
-            raise RuntimeError("create_jpeg_encoder failed")
-        self.closed = False
-
-    @property
-    def capacity(self):
-        return int(self.encoder.capacity)
-
-    def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, stream=None):
-        """Enqueues the encode of device memory on `stream` (None: the device's) into the slot and returns at once"""
-        if self.lib.begin_jpeg_encode(C.byref(self.encoder), slot, pointer, channel_count, row_stride_bytes, stream):
-            raise RuntimeError("begin_jpeg_encode failed")
-
-    def end(self, slot, copy=True):
-        """Waits for the slot: the bytes of the file (copy=False: a numpy VIEW of the pinned staging memory, valid until
-        the slot's next begin())"""
-        address, size = C.c_void_p(), C.c_uint64()
-        if self.lib.end_jpeg_encode(C.byref(self.encoder), slot, C.byref(address), C.byref(size)):
-            raise RuntimeError("end_jpeg_encode failed")
-        if copy:
-            return C.string_at(address.value, size.value)
-        return np.frombuffer((C.c_uint8 * size.value).from_address(address.value), np.uint8)
-
-    def encode(self, pointer, channel_count=4, row_stride_bytes=0):
-        self.begin(0, pointer, channel_count, row_stride_bytes)
-        return self.end(0)
-
-    def encode_image(self, image, row_stride_bytes=0):
-        """Uploads a uint8 image (height, width, 3 or 4), rows row_stride_bytes apart on the device, and encodes it"""
-        image = np.ascontiguousarray(image, np.uint8)
-        if image.shape[0] != self.encoder.height or image.shape[1] != self.encoder.width:
-            raise ValueError("this encoder is for %d x %d images" % (self.encoder.width, self.encoder.height))
-        row = image.shape[1] * image.shape[2]
-        stride = int(row_stride_bytes) or row
-        padded = np.zeros((image.shape[0], stride), np.uint8)
-        padded[:, :row] = image.reshape(image.shape[0], row)
-        hip = C.CDLL("libamdhip64.so")
-        pointer = C.c_void_p()
-        if hip.hipMalloc(C.byref(pointer), C.c_size_t(padded.nbytes)):
-            raise RuntimeError("out of device memory for an image of %d bytes" % padded.nbytes)
-        try:
-            if hip.hipMemcpy(pointer, C.c_void_p(padded.ctypes.data), C.c_size_t(padded.nbytes), 1):
-                raise RuntimeError("uploading the image failed")
-            return self.encode(pointer, image.shape[2], stride)
-        finally:
-            hip.hipFree(pointer)
-
-    def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, stream=None):
-        """encode_jpeg_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
-        size_pointer, both device memory; returns once it is enqueued"""
-        if self.lib.encode_jpeg_on_device(C.byref(self.encoder), pointer, channel_count, row_stride_bytes, out_pointer, capacity, size_pointer, stream):
-            raise RuntimeError("encode_jpeg_on_device failed")
-
-    def close(self):
-        if not self.closed:
-            self.lib.destroy_jpeg_encoder(C.byref(self.encoder))
-            self.closed = True
-
-
-class HdrEncoder:
-    """create_hdr_encoder() of include/vkr_hdr.h for a Renderer: encode() for one frame at a time, begin() and end() per
-    slot for frames in flight, encode_on_device() for a file that stays in device memory."""
-
-    def __init__(self, owner, width, height, slot_count=1):
-        self.owner, self.lib = owner, owner.lib
-        self.encoder = capi.HdrEncoder()
-        self.closed = True
-        if self.lib.create_hdr_encoder(C.byref(self.encoder), owner._dev(), width, height, slot_count):
-            raise RuntimeError("create_hdr_encoder failed")
-        self.closed = False
-
-    @property
-    def capacity(self):
-        return int(self.encoder.capacity)
-
-    def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
-        """Enqueues the encode of device memory on `stream` (None: the device's) into the slot and returns at once"""
-        if self.lib.begin_hdr_encode(C.byref(self.encoder), slot, pointer, channel_count, row_stride_bytes, int(bool(through_half)), stream):
-            raise RuntimeError("begin_hdr_encode failed")
-
-    def end(self, slot, copy=True):
-        """Waits for the slot: the bytes of the file (copy=False: a numpy VIEW of the pinned staging memory, valid until
-        the slot's next begin())"""
-        address, size = C.c_void_p(), C.c_uint64()
-        if self.lib.end_hdr_encode(C.byref(self.encoder), slot, C.byref(address), C.byref(size)):
-            raise RuntimeError("end_hdr_encode failed")
-        if copy:
-            return C.string_at(address.value, size.value)
-        return np.frombuffer((C.c_uint8 * size.value).from_address(address.value), np.uint8)
-
-    def encode(self, pointer, channel_count=4, row_stride_bytes=0, through_half=False):
-        self.begin(0, pointer, channel_count, row_stride_bytes, through_half)
-        return self.end(0)
-
-    def encode_image(self, image, row_stride_bytes=0, through_half=False):
-        """Uploads a float32 image (height, width, 3 or 4), rows row_stride_bytes apart on the device, and encodes it"""
-        image = np.ascontiguousarray(image, np.float32)
-        if image.shape[0] != self.encoder.height or image.shape[1] != self.encoder.width:
-            raise ValueError("this encoder is for %d x %d images" % (self.encoder.width, self.encoder.height))
-        row = image.shape[1] * image.shape[2] * 4
-        stride = int(row_stride_bytes) or row
-        padded = np.zeros((image.shape[0], stride), np.uint8)
-        padded[:, :row] = image.view(np.uint8).reshape(image.shape[0], row)
-        hip = C.CDLL("libamdhip64.so")
-        pointer = C.c_void_p()
-        if hip.hipMalloc(C.byref(pointer), C.c_size_t(padded.nbytes)):
-            raise RuntimeError("out of device memory for an image of %d bytes" % padded.nbytes)
-        try:
-            if hip.hipMemcpy(pointer, C.c_void_p(padded.ctypes.data), C.c_size_t(padded.nbytes), 1):
-                raise RuntimeError("uploading the image failed")
-            return self.encode(pointer, image.shape[2], stride, through_half)
-        finally:
-            hip.hipFree(pointer)
-
-    def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
-        """encode_hdr_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
-        size_pointer, both device memory; returns once it is enqueued"""
-        if self.lib.encode_hdr_on_device(C.byref(self.encoder), pointer, channel_count, row_stride_bytes, int(bool(through_half)), out_pointer, capacity, size_pointer, stream):
-            raise RuntimeError("encode_hdr_on_device failed")
-
-    def close(self):
-        if not self.closed:
-            self.lib.destroy_hdr_encoder(C.byref(self.encoder))
-            self.closed = True
 
 
 _HIP_RUNTIME = None
 
 
 def _hip_runtime():
-    """The HIP runtime that the library has loaded, opened once, with the signatures of the three calls that
-    PngEncoder.encode_image() makes"""
+    """The HIP runtime that the library has loaded, opened once, with the signatures of the three calls that the file
+    encoders' encode_image() makes"""
     global _HIP_RUNTIME
     if _HIP_RUNTIME is None:
         hip = C.CDLL("libamdhip64.so")
@@ -1038,50 +881,60 @@ def _hip_runtime():
     return _HIP_RUNTIME
 
 
-class PngEncoder:
-    """create_png_encoder() of include/vkr_png.h for a Renderer: encode() for one frame at a time, begin() and end() per
-    slot for frames in flight, encode_on_device() for a file that stays in device memory."""
+class _FileEncoder:
+    """What JpegEncoder, HdrEncoder and PngEncoder are: create_<format>_encoder() of include/vkr_<format>.h for a
+    Renderer.  encode() for one frame at a time, begin() and end() per slot for frames in flight, encode_on_device() for a
+    file that stays in device memory.  `format_arguments` are what the format's C functions take besides the pixels."""
+    # the format's name in the C function names, its struct of capi and the type of an image's channels
+    FORMAT = STRUCT = DTYPE = None
+    # what create_<format>_encoder() takes between the extent and the slot count
+    create_arguments = ()
 
     def __init__(self, owner, width, height, slot_count=1):
         self.owner, self.lib = owner, owner.lib
-        self.encoder = capi.PngEncoder()
+        self.encoder = self.STRUCT()
         self.closed = True
-        if self.lib.create_png_encoder(C.byref(self.encoder), owner._dev(), width, height, slot_count):
-            raise RuntimeError("create_png_encoder failed")
+        self._call("create_%s_encoder", owner._dev(), width, height, *self.create_arguments, slot_count)
         self.closed = False
+
+    def _call(self, name, *arguments):
+        name = name % self.FORMAT
+        if getattr(self.lib, name)(C.byref(self.encoder), *arguments):
+            raise RuntimeError(name + " failed")
 
     @property
     def capacity(self):
         return int(self.encoder.capacity)
 
+    def _begin(self, slot, pointer, channel_count, row_stride_bytes, stream, *format_arguments):
+        self._call("begin_%s_encode", slot, pointer, channel_count, row_stride_bytes, *format_arguments, stream)
+
     def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, stream=None):
         """Enqueues the encode of device memory on `stream` (None: the device's) into the slot and returns at once"""
-        if self.lib.begin_png_encode(C.byref(self.encoder), slot, pointer, channel_count, row_stride_bytes, stream):
-            raise RuntimeError("begin_png_encode failed")
+        self._begin(slot, pointer, channel_count, row_stride_bytes, stream)
 
     def end(self, slot, copy=True):
         """Waits for the slot: the bytes of the file (copy=False: a numpy VIEW of the pinned staging memory, valid until
         the slot's next begin())"""
         address, size = C.c_void_p(), C.c_uint64()
-        if self.lib.end_png_encode(C.byref(self.encoder), slot, C.byref(address), C.byref(size)):
-            raise RuntimeError("end_png_encode failed")
+        self._call("end_%s_encode", slot, C.byref(address), C.byref(size))
         if copy:
             return C.string_at(address.value, size.value)
         return np.frombuffer((C.c_uint8 * size.value).from_address(address.value), np.uint8)
 
     def encode(self, pointer, channel_count=4, row_stride_bytes=0):
-        self.begin(0, pointer, channel_count, row_stride_bytes)
+        self._begin(0, pointer, channel_count, row_stride_bytes, None)
         return self.end(0)
 
-    def encode_image(self, image, row_stride_bytes=0):
-        """Uploads a uint8 image (height, width, 3 or 4), rows row_stride_bytes apart on the device, and encodes it"""
-        image = np.ascontiguousarray(image, np.uint8)
+    def _encode_image(self, image, row_stride_bytes, *format_arguments):
+        image = np.ascontiguousarray(image, self.DTYPE)
         if image.shape[0] != self.encoder.height or image.shape[1] != self.encoder.width:
             raise ValueError("this encoder is for %d x %d images" % (self.encoder.width, self.encoder.height))
-        row = image.shape[1] * image.shape[2]
+        row = image.shape[1] * image.shape[2] * image.itemsize
         stride = int(row_stride_bytes) or row
+        # (a value in the padding between rows that would show if it were read)
         padded = np.full((image.shape[0], stride), 0xA5, np.uint8)
-        padded[:, :row] = image.reshape(image.shape[0], row)
+        padded[:, :row] = image.view(np.uint8).reshape(image.shape[0], row)
         hip = _hip_runtime()
         pointer = C.c_void_p()
         if hip.hipMalloc(C.byref(pointer), padded.nbytes):
@@ -1089,20 +942,60 @@ class PngEncoder:
         try:
             if hip.hipMemcpy(pointer, padded.ctypes.data, padded.nbytes, 1):
                 raise RuntimeError("uploading the image failed")
-            return self.encode(pointer, image.shape[2], stride)
+            self._begin(0, pointer, image.shape[2], stride, None, *format_arguments)
+            return self.end(0)
         finally:
             hip.hipFree(pointer)
 
+    def encode_image(self, image, row_stride_bytes=0):
+        """Uploads an image (height, width, 3 or 4) of the format's type, rows row_stride_bytes apart on the device, and
+        encodes it"""
+        return self._encode_image(image, row_stride_bytes)
+
+    def _encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count, row_stride_bytes, stream, *format_arguments):
+        self._call("encode_%s_on_device", pointer, channel_count, row_stride_bytes, *format_arguments, out_pointer, capacity, size_pointer, stream)
+
     def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, stream=None):
-        """encode_png_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
+        """encode_<format>_on_device(): at most `capacity` bytes of the file to out_pointer, its size to the 8 bytes at
         size_pointer, both device memory; returns once it is enqueued"""
-        if self.lib.encode_png_on_device(C.byref(self.encoder), pointer, channel_count, row_stride_bytes, out_pointer, capacity, size_pointer, stream):
-            raise RuntimeError("encode_png_on_device failed")
+        self._encode_on_device(pointer, out_pointer, capacity, size_pointer, channel_count, row_stride_bytes, stream)
 
     def close(self):
         if not self.closed:
-            self.lib.destroy_png_encoder(C.byref(self.encoder))
+            self._call("destroy_%s_encoder")
             self.closed = True
+
+
+class JpegEncoder(_FileEncoder):
+    """uint8 images as JPEG files of one quality"""
+    FORMAT, STRUCT, DTYPE = "jpeg", capi.JpegEncoder, np.uint8
+
+    def __init__(self, owner, width, height, quality=70, slot_count=1):
+        self.create_arguments = (int(quality),)
+        super().__init__(owner, width, height, slot_count)
+
+
+class PngEncoder(_FileEncoder):
+    """uint8 images as PNG files"""
+    FORMAT, STRUCT, DTYPE = "png", capi.PngEncoder, np.uint8
+
+
+class HdrEncoder(_FileEncoder):
+    """float32 images as Radiance files; through_half: every channel through half precision first"""
+    FORMAT, STRUCT, DTYPE = "hdr", capi.HdrEncoder, np.float32
+
+    def begin(self, slot, pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
+        self._begin(slot, pointer, channel_count, row_stride_bytes, stream, int(bool(through_half)))
+
+    def encode(self, pointer, channel_count=4, row_stride_bytes=0, through_half=False):
+        self.begin(0, pointer, channel_count, row_stride_bytes, through_half)
+        return self.end(0)
+
+    def encode_image(self, image, row_stride_bytes=0, through_half=False):
+        return self._encode_image(image, row_stride_bytes, int(bool(through_half)))
+
+    def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
+        self._encode_on_device(pointer, out_pointer, capacity, size_pointer, channel_count, row_stride_bytes, stream, int(bool(through_half)))
 
 
 class FrameStatistics:
