@@ -39,7 +39,8 @@ typedef struct ray_query_options_s {
 
    rays, out_hits and out_blocked are device pointers to `count` records, rays and out_hits aligned to 16 bytes.  The
    kernels (csrc/ray_queries.hip) are enqueued on `stream`, a hipStream_t, or on device->stream if it is NULL, and the
-   calls return once they are enqueued: ordering the buffers against other work is the caller's business.  The tree does not change after load_scene().  options NULL:
+   calls return once they are enqueued: ordering the buffers against other work is the caller's business.  The tree changes only in update_scene_geometry()
+   (vkr_scene_update.h), which waits for the device first.  options NULL:
    the defaults (ray_walk_auto, 0).  The stack entries beyond LDS of the wide walk live in one buffer per HIP device (at
    most 256 MiB; more rays run in pieces) that the first call which needs it allocates and destroy_hip_device() frees;
    calls on different streams are ordered behind each other on the device for its sake.

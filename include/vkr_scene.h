@@ -102,6 +102,14 @@ typedef struct acceleration_structure_s {
 		later one was built into the allocations that an earlier one has freed.  What the shading pass keeps from frame
 		to frame because the tree has not changed (the verdicts of its light shafts) is tied to it. */
 	uint32_t build_serial;
+	/*! One uint32_t per leaf slot, written by the build for update_scene_geometry() (include/vkr_scene_update.h): slab
+		j << 16 | count of the fragment of a split triangle that the leaf was built for, count == 1 for a whole triangle */
+	void* leaf_fragments;
+	/*! What update_scene_geometry() derives from the tree on its first call and keeps (csrc/bvh_refit.hip): parents of the
+		nodes of both layouts, arrival counters, leaf boxes.  NULL until then. */
+	void* refit_state;
+	/*! The cost (include/vkr_scene_update.h) of the tree as built, taken by the first update; 0 until then */
+	double built_cost;
 } acceleration_structure_t;
 
 /*! reference scene.h:161-166 */

@@ -84,7 +84,8 @@ class AccelerationStructure(C.Structure):
                 ("node_count", C.c_uint32), ("root", C.c_uint32),
                 ("grid_origin", C.c_float * 3), ("grid_inverse_cell", C.c_float * 3),
                 ("wide_nodes", C.c_void_p), ("wide_node_count", C.c_uint32), ("wide_stack_need", C.c_uint32),
-                ("builder", C.c_uint32), ("build_milliseconds", C.c_float), ("leaf_count", C.c_uint32), ("build_serial", C.c_uint32)]
+                ("builder", C.c_uint32), ("build_milliseconds", C.c_float), ("leaf_count", C.c_uint32), ("build_serial", C.c_uint32),
+                ("leaf_fragments", C.c_void_p), ("refit_state", C.c_void_p), ("built_cost", C.c_double)]
 
 
 class Scene(C.Structure):
@@ -250,10 +251,21 @@ class PngEncoder(C.Structure):
 
 PNG_HEADER_SIZE = 33  # VKR_PNG_HEADER_SIZE
 
+
+class SceneUpdateOptions(C.Structure):
+    _fields_ = [("policy", C.c_uint32), ("inputs_on_device", C.c_uint32), ("refresh_host_copy", C.c_uint32),
+                ("measure_cost", C.c_uint32), ("rebuild_above", C.c_float)]
+
+
+class SceneUpdateReport(C.Structure):
+    _fields_ = [("rebuilt", C.c_uint32), ("build_serial", C.c_uint32), ("milliseconds", C.c_float),
+                ("cost", C.c_double), ("built_cost", C.c_double)]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
-               SlabExchangeId, SlabExchange, FrameStatistics]
+               SlabExchangeId, SlabExchange, SceneUpdateOptions, SceneUpdateReport, FrameStatistics]
 
 # every symbol include/*.h declares, with (restype, argtypes)
 P = C.POINTER
@@ -412,6 +424,7 @@ SIGNATURES = {
     "write_png_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
     "probe_png_stream": (C.c_int, [P(Device), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
     "take_png_screenshot": (C.c_int, [P(Application), C.c_char_p]),
+    "update_scene_geometry": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_void_p, P(SceneUpdateOptions), P(SceneUpdateReport)]),
 }
 
 _lib = None

@@ -7,7 +7,7 @@
 //   - the binned SAH on the host (host/sah_bvh.c), the plain C statement of the first one
 // and two kernels turn it into what the traversal reads (lbvh.h): k_quantize_nodes (16-byte
 // binary nodes) and k_collapse_level (64-byte four-wide nodes).
-#include "lbvh.h"
+#include "bvh_leaf_boxes.h"
 #include "host/vkr_internal.h"
 #include <hipcub/hipcub.hpp>
 #include <atomic>
@@ -28,16 +28,12 @@ struct build_params {
 	// fragment_boxes[6 t ... 6 t + 5] (lo.xyz, hi.xyz).  NULL: every primitive is a whole triangle.
 	const uint32_t* fragment_triangle;
 	const float* fragment_boxes;
+	// Per leaf slot, which fragment the leaf was built for (pack_leaf_fragment; what a refit needs to cut the moved triangle
+	// the same way, bvh_refit.hip).  Only written where fragment_triangle is set: the others are whole triangles.
+	uint32_t* leaf_fragments;
 };
 
-// De-quantisation with two roundings (multiply, then add) like scene.c:176-187; the
-// shading path uses a fused decode instead (mesh_quantization.glsl:38-45).
-__device__ __forceinline__ f3 dequantize(uint2 q, const build_params& p) {
-	float x = (float) (q.x & 0x1FFFFF);
-	float y = (float) (((q.x & 0xFFE00000u) >> 21) | ((q.y & 0x3FF) << 11));
-	float z = (float) ((q.y & 0x7FFFFC00u) >> 10);
-	return mk3(__fadd_rn(__fmul_rn(x, p.factor[0]), p.summand[0]), __fadd_rn(__fmul_rn(y, p.factor[1]), p.summand[1]), __fadd_rn(__fmul_rn(z, p.factor[2]), p.summand[2]));
-}
+__device__ __forceinline__ f3 dequantize(uint2 q, const build_params& p) { return dequantize_position(q, p.factor, p.summand); }
 
 __device__ __forceinline__ uint32_t spread_bits_10(uint32_t v) {
 	v &= 0x3FF;
@@ -189,13 +185,7 @@ __global__ void __launch_bounds__(256) k_quantize_nodes(uint32_t node_count, con
 	float lo[3] = {a.x, a.y, a.z}, hi[3] = {a.w, b.x, b.y};
 	float g0[3] = {origin.x, origin.y, origin.z}, scale[3] = {inverse_cell.x, inverse_cell.y, inverse_cell.z};
 	uint32_t packed[3];
-	for (int j = 0; j != 3; ++j) {
-		float q0 = floorf((lo[j] - g0[j]) * scale[j] - kGridMargin);
-		float q1 = ceilf((hi[j] - g0[j]) * scale[j] + kGridMargin);
-		q0 = fminf(fmaxf(q0, 0.0f), kGridMax);
-		q1 = fminf(fmaxf(q1, 0.0f), kGridMax);
-		packed[j] = (uint32_t) q0 | ((uint32_t) q1 << 16);
-	}
+	for (int j = 0; j != 3; ++j) packed[j] = quantize_box_axis(lo[j], hi[j], g0[j], scale[j]);
 	uint32_t skip = __float_as_uint(b.z), leaf = __float_as_uint(b.w);
 	quantized[id] = make_uint4(packed[0], packed[1], packed[2], leaf != kNoLeaf ? (kLeafBit | leaf) : skip);
 }
@@ -232,14 +222,6 @@ struct sah_bin {
 	uint32_t count;
 	uint32_t lo[3], hi[3];
 };
-
-__device__ __forceinline__ uint32_t ordered(float f) {
-	uint32_t bits = __float_as_uint(f);
-	return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(uint32_t u) {
-	return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
 
 __device__ __forceinline__ void reset_open_node(sah_open_node* node, uint32_t position, uint32_t first, uint32_t count) {
 	node->position = position; node->first = first; node->count = count; node->fallback_rank = 0;
@@ -287,6 +269,15 @@ __device__ __forceinline__ void write_leaf(const build_params& p, uint32_t t, co
 	triangles[3 * (size_t) slot + 0] = make_float4(v[0].x, v[0].y, v[0].z, __uint_as_float(source_triangle(p, t)));
 	triangles[3 * (size_t) slot + 1] = make_float4(v[1].x, v[1].y, v[1].z, 0.0f);
 	triangles[3 * (size_t) slot + 2] = make_float4(v[2].x, v[2].y, v[2].z, 0.0f);
+	if (p.fragment_triangle) {
+		// the fragments of a triangle are consecutive primitives, at most kMostFragments of them
+		const uint32_t triangle = p.fragment_triangle[t];
+		uint32_t j = 0, count = 1;
+		while (j != kMostFragments && t > j && p.fragment_triangle[t - j - 1u] == triangle) ++j;
+		count += j;
+		for (uint32_t next = t + 1u; count != kMostFragments && next < p.triangle_count && p.fragment_triangle[next] == triangle; ++next) ++count;
+		p.leaf_fragments[slot] = pack_leaf_fragment(j, count);
+	}
 }
 
 // ---- contributions of a workgroup combined in LDS ------------------------------------------
@@ -608,8 +599,6 @@ __global__ void __launch_bounds__(256) k_sah_assign(build_params p, uint32_t* tr
 // triangle INSIDE the slab - its box, exactly (the triangle clipped by the two planes), so every point of the
 // triangle lies in the box of some fragment, and a leaf per fragment names the whole triangle.  Ray queries
 // return what they returned (the same triangles are tested, some by more than one leaf); the tree is what changes.
-constexpr uint32_t kMostFragments = 16;
-
 // `most`: the cap per triangle (kMostFragments, or less for a mesh that would otherwise grow more than fourfold)
 __device__ __forceinline__ uint32_t fragments_wanted(const f3 (&v)[3], f3 lo, f3 hi, float least_extent, uint32_t most, int& out_axis) {
 	f3 e = hi - lo;
@@ -634,38 +623,6 @@ __global__ void __launch_bounds__(256) k_count_fragments(build_params p, float l
 	counts[t] = fragments_wanted(v, lo, hi, least_extent, most, axis);
 }
 
-// bounds of the part of the triangle with s0 <= x_axis <= s1 (the triangle is cut by the two planes)
-__device__ __forceinline__ void slab_bounds(const f3 (&v)[3], int axis, float s0, float s1, f3& lo, f3& hi) {
-	float px[8], py[8], pz[8], qx[8], qy[8], qz[8];
-	int count = 3;
-	for (int i = 0; i != 3; ++i) { px[i] = v[i].x; py[i] = v[i].y; pz[i] = v[i].z; }
-	for (int side = 0; side != 2; ++side) {
-		// keep x_axis >= s0 (side 0), x_axis <= s1 (side 1)
-		float plane = side ? s1 : s0, sign = side ? -1.0f : 1.0f;
-		int kept = 0;
-		for (int i = 0; i != count; ++i) {
-			int j = (i + 1 == count) ? 0 : i + 1;
-			float ci = axis == 0 ? px[i] : (axis == 1 ? py[i] : pz[i]), cj = axis == 0 ? px[j] : (axis == 1 ? py[j] : pz[j]);
-			float di = sign * (ci - plane), dj = sign * (cj - plane);
-			if (di >= 0.0f) { qx[kept] = px[i]; qy[kept] = py[i]; qz[kept] = pz[i]; ++kept; }
-			if ((di >= 0.0f) != (dj >= 0.0f)) {
-				float w = di / (di - dj);
-				qx[kept] = fmaf(w, px[j] - px[i], px[i]); qy[kept] = fmaf(w, py[j] - py[i], py[i]); qz[kept] = fmaf(w, pz[j] - pz[i], pz[i]);
-				// (the point lies on the plane: say so exactly, whatever the interpolation rounded to)
-				if (axis == 0) qx[kept] = plane; else if (axis == 1) qy[kept] = plane; else qz[kept] = plane;
-				++kept;
-			}
-		}
-		count = kept;
-		for (int i = 0; i != count; ++i) { px[i] = qx[i]; py[i] = qy[i]; pz[i] = qz[i]; }
-	}
-	lo = mk3(3.0e38f, 3.0e38f, 3.0e38f); hi = mk3(-3.0e38f, -3.0e38f, -3.0e38f);
-	for (int i = 0; i != count; ++i) {
-		lo = mk3(fminf(lo.x, px[i]), fminf(lo.y, py[i]), fminf(lo.z, pz[i]));
-		hi = mk3(fmaxf(hi.x, px[i]), fmaxf(hi.y, py[i]), fmaxf(hi.z, pz[i]));
-	}
-}
-
 // first[t]: exclusive prefix sum of the counts
 __global__ void __launch_bounds__(256) k_write_fragments(build_params p, float least_extent, uint32_t most, const uint32_t* first, uint32_t* fragment_triangle, float* fragment_boxes) {
 	uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -675,20 +632,9 @@ __global__ void __launch_bounds__(256) k_write_fragments(build_params p, float l
 	int axis;
 	uint32_t count = fragments_wanted(v, lo, hi, least_extent, most, axis);
 	uint32_t base = first[t];
-	float a0 = axis == 0 ? lo.x : (axis == 1 ? lo.y : lo.z), a1 = axis == 0 ? hi.x : (axis == 1 ? hi.y : hi.z);
 	for (uint32_t j = 0; j != count; ++j) {
 		f3 flo = lo, fhi = hi;
-		if (count > 1u) {
-			// (the planes between the slabs are shared: slab j ends where slab j + 1 begins, bit for bit)
-			float s0 = j == 0u ? a0 : fmaf((float) j / (float) count, a1 - a0, a0);
-			float s1 = j + 1u == count ? a1 : fmaf((float) (j + 1u) / (float) count, a1 - a0, a0);
-			slab_bounds(v, axis, s0, s1, flo, fhi);
-			// a slab that the clipping left empty (rounding at the ends) keeps a point of the triangle's box
-			if (!(flo.x <= fhi.x)) { flo = lo; fhi = lo; }
-			// never beyond the triangle's own box
-			flo = mk3(fmaxf(flo.x, lo.x), fmaxf(flo.y, lo.y), fmaxf(flo.z, lo.z));
-			fhi = mk3(fminf(fhi.x, hi.x), fminf(fhi.y, hi.y), fminf(fhi.z, hi.z));
-		}
+		if (count > 1u) fragment_bounds(v, lo, hi, axis, j, count, flo, fhi);
 		fragment_triangle[base + j] = t;
 		float* box = fragment_boxes + 6 * (size_t) (base + j);
 		box[0] = flo.x; box[1] = flo.y; box[2] = flo.z; box[3] = fhi.x; box[4] = fhi.y; box[5] = fhi.z;
@@ -781,6 +727,11 @@ __global__ void __launch_bounds__(64) k_publish_counters(uint32_t* counters, uin
 	}
 }
 
+__global__ void __launch_bounds__(256) k_fill_words(uint32_t* words, uint32_t count, uint32_t value) {
+	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < count) words[i] = value;
+}
+
 }  // namespace
 
 // ---- host ---------------------------------------------------------------------------------------
@@ -797,6 +748,7 @@ static build_params make_build_params(const mesh_t* mesh, float* out_extent) {
 	p.triangle_count = (uint32_t) mesh->triangle_count;
 	p.fragment_triangle = NULL;
 	p.fragment_boxes = NULL;
+	p.leaf_fragments = NULL;
 	float extent = 0.0f;
 	for (int j = 0; j != 3; ++j) {
 		p.factor[j] = mesh->dequantization_factor[j];
@@ -981,6 +933,27 @@ static int build_sah_on_host(acceleration_structure_t* structure, const device_t
 	return upload_failed;
 }
 
+extern "C" float vkr_bvh_padding(const mesh_t* mesh) {
+	float extent;
+	return make_build_params(mesh, &extent).pad;
+}
+
+extern "C" void vkr_choose_bvh_grid(acceleration_structure_t* structure, const float lo[3], const float hi[3]) {
+	for (int j = 0; j != 3; ++j) {
+		// one spare cell on either side keeps every box strictly inside [0, kGridMax]
+		float extent = fmaxf(hi[j] - lo[j], 1.0e-20f);
+		float cell = extent / (kGridMax - 2.0f);
+		structure->grid_origin[j] = lo[j] - cell;
+		structure->grid_inverse_cell[j] = 1.0f / cell;
+	}
+}
+
+extern "C" uint32_t vkr_next_build_serial(void) {
+	// (ranks of one process build their trees on threads of their own: vkr_multi_gpu)
+	static std::atomic<uint32_t> builds{0};
+	return builds.fetch_add(1u) + 1u;
+}
+
 // Replaces structure->nodes (fp32 threaded nodes on the device) by the quantised nodes
 static int quantize_nodes(acceleration_structure_t* structure, const device_t* device) {
 	hipStream_t stream = (hipStream_t) device->stream;
@@ -990,13 +963,7 @@ static int quantize_nodes(acceleration_structure_t* structure, const device_t* d
 		|| vkr_device_alloc(&quantized, device, sizeof(uint4) * (size_t) structure->node_count, "the quantised BVH nodes");
 	if (!failed) {
 		const float lo[3] = {root[0], root[1], root[2]}, hi[3] = {root[3], root[4], root[5]};
-		for (int j = 0; j != 3; ++j) {
-			// one spare cell on either side keeps every box strictly inside [0, kGridMax]
-			float extent = fmaxf(hi[j] - lo[j], 1.0e-20f);
-			float cell = extent / (kGridMax - 2.0f);
-			structure->grid_origin[j] = lo[j] - cell;
-			structure->grid_inverse_cell[j] = 1.0f / cell;
-		}
+		vkr_choose_bvh_grid(structure, lo, hi);
 		k_quantize_nodes<<<block_count(structure->node_count, 256), 256, 0, stream>>>(structure->node_count, (const float4*) structure->nodes,
 			f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]},
 			f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]}, (uint4*) quantized);
@@ -1057,6 +1024,8 @@ extern "C" void vkr_destroy_acceleration_structure(acceleration_structure_t* str
 	vkr_device_free(structure->triangle_vertices, device);
 	vkr_device_free(structure->nodes, device);
 	vkr_device_free(structure->wide_nodes, device);
+	vkr_device_free(structure->leaf_fragments, device);
+	vkr_free_refit_state(structure, device);
 	memset(structure, 0, sizeof(*structure));
 }
 
@@ -1084,8 +1053,14 @@ extern "C" int vkr_build_acceleration_structure(acceleration_structure_t* struct
 	// VKR_BVH_BUILD_TRACE=1 prints the wall-clock time of the three phases (diagnostics)
 	const bool trace = getenv("VKR_BVH_BUILD_TRACE") != NULL;
 	void* fragments = split_long_triangles(p, device, builder, extent, trace);
-	int failed = builder == (int) acceleration_structure_sah_host ? build_sah_on_host(structure, device, mesh, p.pad)
-		: (builder == (int) acceleration_structure_lbvh_device ? build_lbvh_on_device(structure, device, p) : build_sah_on_device(structure, device, p, host_words));
+	// every leaf slot is a whole triangle unless the device SAH build says otherwise where it writes the leaf
+	int failed = vkr_device_alloc(&structure->leaf_fragments, device, sizeof(uint32_t) * (size_t) p.triangle_count, "the fragment records of the BVH leaves");
+	if (!failed) {
+		p.leaf_fragments = (uint32_t*) structure->leaf_fragments;
+		k_fill_words<<<block_count(p.triangle_count, 256), 256, 0, (hipStream_t) device->stream>>>(p.leaf_fragments, p.triangle_count, pack_leaf_fragment(0u, 1u));
+	}
+	failed = failed || (builder == (int) acceleration_structure_sah_host ? build_sah_on_host(structure, device, mesh, p.pad)
+		: (builder == (int) acceleration_structure_lbvh_device ? build_lbvh_on_device(structure, device, p) : build_sah_on_device(structure, device, p, host_words)));
 	vkr_device_free(fragments, device);
 	const struct timespec tree_built = now();
 	failed = failed || quantize_nodes(structure, device);
@@ -1102,9 +1077,7 @@ extern "C" int vkr_build_acceleration_structure(acceleration_structure_t* struct
 	}
 	structure->builder = (uint32_t) builder;
 	structure->leaf_count = (structure->node_count + 1u) / 2u;
-	// (ranks of one process build their trees on threads of their own: vkr_multi_gpu)
-	static std::atomic<uint32_t> builds{0};
-	structure->build_serial = builds.fetch_add(1u) + 1u;
+	structure->build_serial = vkr_next_build_serial();
 	structure->build_milliseconds = (float) milliseconds(start, now());
 	return 0;
 }

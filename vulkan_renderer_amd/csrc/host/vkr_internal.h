@@ -82,6 +82,13 @@ int vkr_build_acceleration_structure(acceleration_structure_t* structure, const 
 /*! sah_bvh.c: malloc'ed nodes (8 floats each, depth-first) and triangles (12 floats per leaf slot) */
 int vkr_build_sah_bvh_host(const mesh_t* mesh, float pad, float** out_nodes, float** out_triangles, uint32_t* out_node_count);
 void vkr_destroy_acceleration_structure(acceleration_structure_t* structure, const device_t* device);
+/*! bvh_build.hip, shared with the refit of bvh_refit.hip: the next acceleration_structure_t.build_serial of the process
+	(thread-safe), the padding of the boxes of a mesh, and grid_origin / grid_inverse_cell for a padded root box */
+uint32_t vkr_next_build_serial(void);
+float vkr_bvh_padding(const mesh_t* mesh);
+void vkr_choose_bvh_grid(acceleration_structure_t* structure, const float lo[3], const float hi[3]);
+/*! bvh_refit.hip: frees acceleration_structure_t.refit_state (vkr_destroy_acceleration_structure() calls it) */
+void vkr_free_refit_state(acceleration_structure_t* structure, const device_t* device);
 
 /*! slab_assembly.hip: scatters all-gathered slabs (format: slab_format_t of vkr_slab_exchange.h)
 	into a frame on the given hipStream_t */

@@ -698,6 +698,60 @@ class Renderer(HostScene):
         ray = self.pixel_rays()[y * e.width + x:y * e.width + x + 1]
         return self.trace_closest_hits(ray["origin"], ray["direction"], ray["t_min"], ray["t_max"], cull_back_faces=True)[0]
 
+    # -- moving geometry (include/vkr_scene_update.h) -------------------------------------
+    def update_geometry(self, positions, normals_and_tex_coords=None, policy="refit", on_device=False, measure_cost=False, rebuild_above=0.0, refresh_host_copy=True):
+        """New vertex positions for the loaded mesh (update_scene_geometry): the file's words, (3 T, 2) uint32 - see
+        scene_update.pack_positions() - or, with on_device, the address of such an array in device memory; likewise
+        normals_and_tex_coords, (3 T, 4) uint16, or None to keep them.  policy: "refit", "rebuild" or "auto" (rebuild when
+        the refitted tree costs more than rebuild_above times the tree as built).  Waits for the frames in flight first.
+        -> the report as a dict; call render_visibility() before the next render()."""
+        from . import scene_update
+        self.finish_frames()
+        vertex_count = 3 * int(self.app.scene.mesh.triangle_count)
+        keep = []
+
+        def pointer(array, dtype, width):
+            if array is None:
+                return None
+            if on_device:
+                return C.cast(array, C.c_void_p).value if isinstance(array, (C._SimpleCData, C._Pointer)) else int(array)
+            array = np.ascontiguousarray(array, dtype)
+            if array.size != vertex_count * width:
+                raise ValueError("expected %d x %d %s for the %d triangles of the mesh, got %d values" % (vertex_count, width, np.dtype(dtype).name, vertex_count // 3, array.size))
+            keep.append(array)
+            return array.ctypes.data
+        options = capi.SceneUpdateOptions(_enum(scene_update.POLICY, policy), int(bool(on_device)), int(bool(refresh_host_copy)), int(bool(measure_cost)), float(rebuild_above))
+        report = capi.SceneUpdateReport()
+        if self.lib.update_scene_geometry(C.byref(self.app.scene), self._dev(), pointer(positions, np.uint32, 2), pointer(normals_and_tex_coords, np.uint16, 4), C.byref(options), C.byref(report)):
+            raise RuntimeError("update_scene_geometry failed")
+        return {"rebuilt": bool(report.rebuilt), "build_serial": int(report.build_serial), "milliseconds": float(report.milliseconds),
+                "cost": float(report.cost), "built_cost": float(report.built_cost)}
+
+    def read_acceleration_structure(self):
+        """The acceleration structure as numpy arrays, read back from the device: nodes (N, 4) uint32 and wide_nodes
+        (W, 16) uint32 (csrc/lbvh.h; None without a wide tree), triangle_vertices (3 L, 4) float32, leaf_fragments (L,)
+        uint32 (slab j << 16 | count per leaf slot), grid_origin and grid_inverse_cell (3,) float32, and the counts, the
+        builder and build_serial as ints"""
+        s = self.app.scene.acceleration_structure
+        if not s.nodes:
+            raise RuntimeError("the scene has no acceleration structure")
+        hip = _hip_runtime()
+        self.finish_frames()
+        self.sync()
+
+        def read(address, shape, dtype):
+            out = np.zeros(shape, dtype)
+            if out.nbytes and hip.hipMemcpy(out.ctypes.data, address, out.nbytes, 2):
+                raise RuntimeError("reading the acceleration structure back failed")
+            return out
+        tree = {k: int(getattr(s, k)) for k in ("node_count", "leaf_count", "wide_node_count", "wide_stack_need", "builder", "build_serial")}
+        tree["nodes"] = read(s.nodes, (s.node_count, 4), np.uint32)
+        tree["wide_nodes"] = read(s.wide_nodes, (s.wide_node_count, 16), np.uint32) if s.wide_nodes else None
+        tree["triangle_vertices"] = read(s.triangle_vertices, (3 * s.leaf_count, 4), np.float32)
+        tree["leaf_fragments"] = read(s.leaf_fragments, (s.leaf_count,), np.uint32)
+        tree["grid_origin"], tree["grid_inverse_cell"] = np.array(s.grid_origin[:], np.float32), np.array(s.grid_inverse_cell[:], np.float32)
+        return tree
+
     def read_encoded(self, output_linear_rgb=False, frame_bits=0):
         e = self.app.swapchain.extent
         self.app.screenshot.frame_bits = frame_bits
