@@ -438,6 +438,11 @@ VKR_API uint64_t read_back_light_shafts(application_t* app, uint32_t* out_words,
 	(0 nothing stored, 1 being stored, 2 stored), the budget in MiB (environment VKR_PREPARED_POLYGONS_MIB, 0: off)}.
 	0 on success, 1 (all zero) before the first frame with wavefront rays. */
 VKR_API int get_prepared_polygon_statistics(application_t* app, uint64_t out_statistics[8]);
+/*! The sector terms that are kept with the prepared polygons where both fit the budgets (environment
+	VKR_SECTOR_TERMS=0: none are): {bytes of the buffer that holds them (0: none allocated), launches of the pass so far
+	that loaded their polygons with terms, and without}.  The two counts add up to the loading launches of
+	get_prepared_polygon_statistics().  0 on success, 1 (all zero) before the first frame with wavefront rays. */
+VKR_API int get_sector_terms_statistics(application_t* app, uint64_t out_statistics[3]);
 /*! (diagnostics, only with VKR_SHAFT_COUNTERS=1 in the environment) work of the shaft kernel of the most recent
 	launch: {steps of its walks (16 nodes each), batches of triangles, walks}.  0 on success. */
 VKR_API int get_light_shaft_work(application_t* app, uint64_t out_work[3]);

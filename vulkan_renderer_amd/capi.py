@@ -337,6 +337,7 @@ SIGNATURES = {
     "read_back_light_shafts": (C.c_uint64, [P(Application), C.c_void_p, C.c_uint64]),
     "get_light_shaft_work": (C.c_int, [P(Application), P(C.c_uint64)]),
     "get_prepared_polygon_statistics": (C.c_int, [P(Application), P(C.c_uint64)]),
+    "get_sector_terms_statistics": (C.c_int, [P(Application), P(C.c_uint64)]),
     "get_dispatch_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),
     "get_shading_kernel_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),
     "get_frame_period_milliseconds": (C.c_uint32, [P(Application), P(C.c_float), C.c_uint32]),

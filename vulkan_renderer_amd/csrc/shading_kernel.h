@@ -821,6 +821,9 @@ struct pixel_context {
 	noise_accessor* noise;
 	// the prepared polygons of the launch in device memory, [light][quad][thread of the launch]; NULL in the plain kernel
 	prepared_quad* prepared;
+	// the sector terms of the launch in device memory ("Sector terms that are still true"), [light][polygon][sector][half][thread
+	// of the launch]; NULL in every kernel but the one that loads with terms
+	const sector_terms_quad* terms;
 };
 
 // get_polygon_radiance_visibility_brdf_product, shading_pass.frag.glsl:203-231, without
@@ -1174,7 +1177,8 @@ VKR_DEV f3 display_sampling_error(const shade_params& p, const psa_polygon<V>& p
 // in quads of four words, [light][quad][thread]: a wave's loads and stores are 1 024 contiguous bytes each.  The values
 // travel as bits, and the units that use this are compiled without contraction (not the fast mode's, whose compiler may
 // fuse a product of the preparation into a sum of the sampling): the loading kernel's samples are the plain kernel's.
-enum { kPreparedPlain = 0, kPreparedStoring = 1, kPreparedLoading = 2 };
+// kPreparedLoadingTerms: "Sector terms that are still true" below
+enum { kPreparedPlain = 0, kPreparedStoring = 1, kPreparedLoading = 2, kPreparedLoadingTerms = 3 };
 constexpr int kPreparedCompactWords(int v) { return 2 * v + 8; }
 constexpr int kPreparedQuads(int v) { return (kPreparedCompactWords(v) + 4 * kPsaTableSlots(v) + 3) / 4; }
 // the first quad that holds slots of the specular polygon's table only
@@ -1238,9 +1242,7 @@ VKR_DEV void store_prepared(const pixel_context& ctx, psa_compact<V>& pd, psa_co
 
 // kPreparedLoading: in place of the preparation of a light; false: the light adds nothing to this pixel
 template <int V>
-VKR_DEV bool load_prepared(const pixel_context& ctx, psa_compact<V>& pd, psa_compact<V>& ps, float2* tables_d, float2* tables_s) {
-	const shade_params& p = ctx.p;
-	const prepared_quad* column = ctx.prepared + (size_t) ctx.light_index * kPreparedQuads(V) * p.thread_count + ctx.tid;
+VKR_DEV bool load_prepared_column(const prepared_quad* column, uint32_t thread_count, psa_compact<V>& pd, psa_compact<V>& ps, float2* tables_d, float2* tables_s) {
 	// (read once per launch: past the caches)
 	prepared_quad first = __builtin_nontemporal_load(column);
 	if (first.x == 0u) return false;
@@ -1250,11 +1252,53 @@ VKR_DEV bool load_prepared(const pixel_context& ctx, psa_compact<V>& pd, psa_com
 #pragma unroll
 	for (int q = 1; q < kPreparedQuads(V); ++q) {
 		prepared_quad quad = (prepared_quad) (0u);
-		if (q < kPreparedSpecularQuad(V) || specular) quad = __builtin_nontemporal_load(column + (size_t) q * p.thread_count);
+		if (q < kPreparedSpecularQuad(V) || specular) quad = __builtin_nontemporal_load(column + (size_t) q * thread_count);
 		w[4 * q] = quad.x; w[4 * q + 1] = quad.y; w[4 * q + 2] = quad.z; w[4 * q + 3] = quad.w;
 	}
 	exchange_prepared_words<V, true>(w, pd, ps, tables_d, tables_s, specular);
 	return true;
+}
+template <int V>
+VKR_DEV bool load_prepared(const pixel_context& ctx, psa_compact<V>& pd, psa_compact<V>& ps, float2* tables_d, float2* tables_s) {
+	const shade_params& p = ctx.p;
+	return load_prepared_column<V>(ctx.prepared + (size_t) ctx.light_index * kPreparedQuads(V) * p.thread_count + ctx.tid, p.thread_count, pd, ps, tables_d, tables_s);
+}
+
+// ---- Sector terms that are still true ----------------------------------------------------------
+// Eight of the roughly ten inverse square roots of a decentral sample (sector_terms, polygon_sampling.h) depend on the
+// sample's sector only, and a sector is true exactly as long as the kept polygon that it belongs to.  Behind the storing
+// launch, fill_sector_terms() derives them from the kept words - with the functions that the sampler calls, in a unit
+// that is compiled as the sampler's is - for every sector that a sample can reach, into a buffer of its own
+// ([light][polygon][sector][half][thread], polygon_sampling.h).  The loading kernel's fourth instantiation,
+// kPreparedLoadingTerms, takes that buffer as a third argument and reads a sample's two quads instead of computing them.
+// Nothing is written for central polygons, culled specular polygons, pairs whose first word is 0 and sectors at or
+// behind vertex_count - 1: no sample reads them.
+template <int V>
+VKR_DEV void fill_sector_terms(const prepared_quad* column, sector_terms_quad* terms_column, uint32_t thread_count, float2* tables_d, float2* tables_s) {
+	psa_compact<V> pd, ps;
+	ps.vertex_count = 0; ps.inner_slots = 0; ps.outer_slots = 0;
+	if (!load_prepared_column<V>(column, thread_count, pd, ps, tables_d, tables_s)) return;
+#pragma unroll
+	for (int polygon = 0; polygon != 2; ++polygon) {
+		const psa_compact<V>& c = (polygon == 0) ? pd : ps;
+		const float2* table = (polygon == 0) ? tables_d : tables_s;
+		// (a culled specular polygon has vertex count 0.  The storing launch writes nothing for threads outside the frame and
+		// for pixels that show the sky, and no launch reads their terms: whatever their columns hold, every index stays inside
+		// the tables)
+		if (c.vertex_count < 3u || c.vertex_count > (uint32_t) V || (c.inner_slots >> 31)) continue;
+#pragma unroll
+		for (int k = 0; k < V - 1; ++k) {
+			if ((uint32_t) (k + 1) >= c.vertex_count) continue;
+			// (the inner ellipse is that of an edge, 0 ... V - 1, or inner_ellipse_0 in slot 2 V = V + V; the outer one is an edge's)
+			uint32_t in = min((c.inner_slots >> (4u * k)) & 15u, (uint32_t) V), out = min((c.outer_slots >> (4u * k)) & 15u, (uint32_t) (V - 1));
+			float2 ei = table[(V + in) * kPsaTableStride], eo = table[(V + out) * kPsaTableStride];
+			float2 v0 = table[k * kPsaTableStride], v1 = table[(k + 1) * kPsaTableStride];
+			sector_terms t = compute_sector_terms(mk2(ei.x, ei.y), mk2(eo.x, eo.y), mk2(v0.x, v0.y), mk2(v1.x, v1.y));
+			sector_terms_quad half0 = {t.fin0, t.fin1, t.fin2, t.fout0}, half1 = {t.fout1, t.fout2, t.in_rs, t.out_rs};
+			terms_column[(size_t) sector_terms_quad_index(V, polygon, (uint32_t) k, 0) * thread_count] = half0;
+			terms_column[(size_t) sector_terms_quad_index(V, polygon, (uint32_t) k, 1) * thread_count] = half1;
+		}
+	}
 }
 
 // evaluate_polygonal_light_shading, shading_pass.frag.glsl:329-711
@@ -1497,7 +1541,11 @@ VKR_DEV f3 evaluate_light(pixel_context& ctx, const shading_data& sd, const ltc_
 			// ... unless there is room for one table only (psa_table_in_memory(): V >= 6): then the specular polygon's table
 			// is this thread's column of a table in device memory
 			float2* const tables_s = psa_table_in_memory(V) ? ctx.psa_table_memory : ctx.psa_tables + kPsaTableSlots(V) * kPsaTableStride;
-			if constexpr (PREPARED == kPreparedLoading) {
+			constexpr bool kTerms = PREPARED == kPreparedLoadingTerms;
+			// (with terms: this thread's quad of this light's diffuse and specular polygon, sector 0, half 0)
+			const sector_terms_quad* const terms_d = kTerms ? ctx.terms + (size_t) ctx.light_index * kSectorTermQuads(V) * p.thread_count + ctx.tid : nullptr;
+			const sector_terms_quad* const terms_s = kTerms ? terms_d + (size_t) sector_terms_quad_index(V, 1, 0u, 0) * p.thread_count : nullptr;
+			if constexpr (PREPARED == kPreparedLoading || PREPARED == kPreparedLoadingTerms) {
 				// (an earlier launch with the same inputs has left both polygons in device memory)
 				if (!load_prepared<V>(ctx, pd, ps, tables_d, tables_s)) return zero;
 			}
@@ -1527,7 +1575,12 @@ VKR_DEV f3 evaluate_light(pixel_context& ctx, const shading_data& sd, const ltc_
 			float specular_weight = specular_albedo * ps.total;
 			if constexpr (STRATEGY == kStrategySeparately) {
 				for (uint32_t s = 0; s != S; ++s) {
-					f3 dd = sample_psa_tables<V, kBiased>(pd, tables_d, next_noise_2(p, noise));
+					f3 dd;
+					if constexpr (kTerms) {
+						f2 u = next_noise_2(p, noise);
+						dd = sample_psa_tables_with_terms<V, kBiased>(pd, tables_d, u, request_sector_terms<V>(pd, u.x, terms_d, p.thread_count));
+					}
+					else dd = sample_psa_tables<V, kBiased>(pd, tables_d, next_noise_2(p, noise));
 					dd = mul_transposed(world_to_shading, dd);
 					settle_noise(noise);
 					float lambert;
@@ -1535,7 +1588,12 @@ VKR_DEV f3 evaluate_light(pixel_context& ctx, const shading_data& sd, const ltc_
 					f3 rb = radiance_brdf<true, false, kTextured>(p, lambert, candidate, dd, sd, light);
 					accumulate<RAYS>(ctx, result, candidate, rb * pd.total, zero * pd.total, dd, sd, light);
 					if (ps.total > 0.0f) {
-						f3 dc = sample_psa_tables<V, kBiased>(ps, tables_s, next_noise_2(p, noise));
+						f3 dc;
+						if constexpr (kTerms) {
+							f2 u = next_noise_2(p, noise);
+							dc = sample_psa_tables_with_terms<V, kBiased>(ps, tables_s, u, request_sector_terms<V>(ps, u.x, terms_s, p.thread_count));
+						}
+						else dc = sample_psa_tables<V, kBiased>(ps, tables_s, next_noise_2(p, noise));
 						f3 ds = normalize(cosine_to_shading(ltc_in, dc));
 						float ltc_density = evaluate_ltc_density(ltc_in, ds, 1.0f);
 						f3 dw = mul_transposed(world_to_shading, ds);
@@ -1569,11 +1627,26 @@ VKR_DEV f3 evaluate_light(pixel_context& ctx, const shading_data& sd, const ltc_
 					specular_weight_rgb = specular_weight_rgb * radiance_over_pi;
 				}
 				for (uint32_t s = 0; s != S; ++s) {
-					f3 dir_d = sample_psa_tables<V, kBiased>(pd, tables_d, next_noise_2(p, noise));
-					f3 dir_s = zero;
+					f3 dir_d, dir_s = zero;
+					if constexpr (kTerms) {
+						// both random numbers are known here: both sectors are found and their four quads asked for before
+						// either sample is drawn
+						f2 u_d = next_noise_2(p, noise), u_s = mk2(0.0f, 0.0f);
+						const psa_sector_request<V> request_d = request_sector_terms<V>(pd, u_d.x, terms_d, p.thread_count);
+						if (ps.total > 0.0f) u_s = next_noise_2(p, noise);
+						const psa_sector_request<V> request_s = request_sector_terms<V>(ps, u_s.x, terms_s, p.thread_count, ps.total > 0.0f);
+						dir_d = sample_psa_tables_with_terms<V, kBiased>(pd, tables_d, u_d, request_d);
+						if (ps.total > 0.0f) {
+							dir_s = sample_psa_tables_with_terms<V, kBiased>(ps, tables_s, u_s, request_s);
+							dir_s = normalize(cosine_to_shading(ltc_in, dir_s));
+						}
+					}
+					else {
+					dir_d = sample_psa_tables<V, kBiased>(pd, tables_d, next_noise_2(p, noise));
 					if (ps.total > 0.0f) {
 						dir_s = sample_psa_tables<V, kBiased>(ps, tables_s, next_noise_2(p, noise));
 						dir_s = normalize(cosine_to_shading(ltc_in, dir_s));
+					}
 					}
 					settle_noise(noise);
 					for (uint32_t j = 0; j != technique_count; ++j) {
@@ -1612,7 +1685,12 @@ VKR_DEV f3 evaluate_light(pixel_context& ctx, const shading_data& sd, const ltc_
 					bool specular_selected = u.x >= diffuse_ratio;
 					float offset = specular_selected ? 1.0f : 0.0f;
 					u.x = divide(u.x - offset, diffuse_ratio - offset);
-					f3 ds = specular_selected ? sample_psa_tables<V, kBiased>(ps, tables_s, u) : sample_psa_tables<V, kBiased>(pd, tables_d, u);
+					f3 ds;
+					if constexpr (kTerms) {
+						ds = specular_selected ? sample_psa_tables_with_terms<V, kBiased>(ps, tables_s, u, request_sector_terms<V>(ps, u.x, terms_s, p.thread_count))
+							: sample_psa_tables_with_terms<V, kBiased>(pd, tables_d, u, request_sector_terms<V>(pd, u.x, terms_d, p.thread_count));
+					}
+					else ds = specular_selected ? sample_psa_tables<V, kBiased>(ps, tables_s, u) : sample_psa_tables<V, kBiased>(pd, tables_d, u);
 					if (specular_selected) ds = normalize(cosine_to_shading(ltc_in, ds));
 					settle_noise(noise);
 					float lambert = ds.z;
@@ -1736,14 +1814,32 @@ constexpr bool prepared_polygons_apply(int strategy, int technique, int v, int r
 }
 // bytes of the buffer of the prepared polygons per thread of the launch and light
 constexpr uint32_t prepared_bytes_per_pair(int v) { return (uint32_t) kPreparedQuads(v) * 16u; }
+// ... and of the buffer of the sector terms
+constexpr uint32_t sector_terms_bytes_per_pair(int v) { return (uint32_t) kSectorTermQuads(v) * 16u; }
+// Fills the sector terms of a launch from its kept polygons: one thread per (thread of the launch, light), grid
+// (thread_count / 64, light_count), the tables of a pair in LDS as the shading kernel has them
+template <int V>
+__global__ void __launch_bounds__(kShadeThreads) k_sector_terms(const prepared_quad* prepared, sector_terms_quad* terms, uint32_t thread_count) {
+	extern __shared__ float2 psa_tables[];
+	const uint32_t tid = blockIdx.x * kShadeThreads + threadIdx.x, light = blockIdx.y;
+	if (tid >= thread_count) return;
+	float2* const tables_d = psa_tables + threadIdx.x;
+	fill_sector_terms<V>(prepared + (size_t) light * kPreparedQuads(V) * thread_count + tid, terms + (size_t) light * kSectorTermQuads(V) * thread_count + tid, thread_count,
+		tables_d, tables_d + kPsaTableSlots(V) * kPsaTableStride);
+}
 // the pointer that the storing and the loading instantiation get as their second argument; the plain one gets none
 VKR_DEV prepared_quad* prepared_argument() { return nullptr; }
 VKR_DEV prepared_quad* prepared_argument(prepared_quad* prepared) { return prepared; }
+VKR_DEV prepared_quad* prepared_argument(prepared_quad* prepared, const sector_terms_quad*) { return prepared; }
+VKR_DEV const sector_terms_quad* terms_argument() { return nullptr; }
+VKR_DEV const sector_terms_quad* terms_argument(prepared_quad*) { return nullptr; }
+VKR_DEV const sector_terms_quad* terms_argument(prepared_quad*, const sector_terms_quad* terms) { return terms; }
 // PREPARED: kPreparedPlain - then BUFFER is empty and the kernel is the one that it always was -, or kPreparedStoring /
-// kPreparedLoading where prepared_polygons_apply(), with the buffer of the prepared polygons as the second argument
+// kPreparedLoading where prepared_polygons_apply(), with the buffer of the prepared polygons as the second argument, or
+// kPreparedLoadingTerms with the buffer of the sector terms as the third
 template <int STRATEGY, int TECHNIQUE, int V, int RAYS, int ERROR = kErrorNone, int PREPARED = kPreparedPlain, typename... BUFFER>
 __global__ void __launch_bounds__(kShadeThreads, shade_min_workgroups(STRATEGY, TECHNIQUE, V, RAYS, ERROR)) shade_pixels(const shade_params p, BUFFER... prepared) {
-	static_assert(PREPARED == kPreparedPlain ? sizeof...(BUFFER) == 0 : (sizeof...(BUFFER) == 1 && prepared_polygons_apply(STRATEGY, TECHNIQUE, V, RAYS, ERROR)), "no such variant");
+	static_assert(PREPARED == kPreparedPlain ? sizeof...(BUFFER) == 0 : (sizeof...(BUFFER) == (PREPARED == kPreparedLoadingTerms ? 2 : 1) && prepared_polygons_apply(STRATEGY, TECHNIQUE, V, RAYS, ERROR)), "no such variant");
 	// A workgroup is ONE wave: the four 8x8 patches of a 16x16 block differ a lot in cost (background,
 	// culled lights), and a wave that is done early gives its registers and LDS back at once instead
 	// of waiting for its block (mean resident waves per SIMD 2.3 -> see profiles/).  Workgroup b runs
@@ -1768,7 +1864,7 @@ __global__ void __launch_bounds__(kShadeThreads, shade_min_workgroups(STRATEGY, 
 	extern __shared__ float2 psa_tables[];
 	// (the wavefront buffers are indexed by the thread's number within this launch)
 	pixel_context ctx = {p, 0, local_block * 256u + thread, 0, 0, false, false, 0u, 0u, nullptr, queue, mk3(0.0f, 0.0f, 0.0f), 2u, kTables ? psa_tables + threadIdx.x : nullptr,
-		(kTables && psa_table_in_memory(V) && p.psa_table_memory) ? p.psa_table_memory + (size_t) b * (kPsaTableSlots(V) * kPsaTableStride) + threadIdx.x : nullptr, nullptr, prepared_argument(prepared...)};
+		(kTables && psa_table_in_memory(V) && p.psa_table_memory) ? p.psa_table_memory + (size_t) b * (kPsaTableSlots(V) * kPsaTableStride) + threadIdx.x : nullptr, nullptr, prepared_argument(prepared...), terms_argument(prepared...)};
 	if constexpr (RAYS == kRaysDeferredBlocks) {
 		// (the waves of a workgroup never touch each other's entry: no barrier)
 		lds_state_word* state = ray_block_state();

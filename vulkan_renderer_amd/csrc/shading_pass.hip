@@ -18,6 +18,7 @@ static const launch_function_t g_launchers[6][5] = {
 // [arithmetic_mode_t][strategy - kStrategySeparately]: the kernels with kept prepared polygons; none in the fast mode
 #define VKR_PREPARED_ROW(mode) {vkr_launch_shade_prepared_##mode##_2, vkr_launch_shade_prepared_##mode##_3, vkr_launch_shade_prepared_##mode##_4}
 static const prepared_launch_function_t g_prepared_launchers[3][3] = {VKR_PREPARED_ROW(libm), {NULL, NULL, NULL}, VKR_PREPARED_ROW(exact)};
+static const sector_terms_launch_function_t g_sector_terms_launchers[3] = {vkr_launch_sector_terms_libm, NULL, vkr_launch_sector_terms_exact};
 static const error_launch_function_t g_error_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_error_display);
 static const resolve_launch_function_t g_resolve_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_resolve_materials);
 
@@ -126,6 +127,11 @@ enum { kCacheEmpty = 0, kCachePending = 1, kCacheValid = 2 };
 struct prepared_cache {
 	uint4* buffer;  // the second argument of the storing and the loading kernel, allocated when a launch first stores
 	size_t buffer_quads;
+	// the sector terms of the polygons in `buffer` (shading_kernel.h "Sector terms that are still true"): the third argument of
+	// the kernel that loads with terms, allocated, retained and released by the rules of `buffer`, and filled behind the storing
+	// launch, in front of `stored`.  terms_quads: its size, 0: the launches of this arrangement load without terms
+	float4* terms;
+	size_t terms_quads;
 	// a byte image of everything the preparation reads (prepared_arrangement below), of the most recent launch that the
 	// cache could serve: seen_size bytes, 0: none
 	uint8_t* seen;
@@ -143,6 +149,9 @@ struct prepared_cache {
 	// the storing launch had not completed yet
 	uint32_t last_mode;
 	uint64_t launches[3], waited;
+	// VKR_SECTOR_TERMS=0: no terms are kept; for get_sector_terms_statistics(): loading launches with and without terms
+	uint32_t terms_enabled;
+	uint64_t loaded_with_terms, loaded_without_terms;
 };
 
 // What a frame in flight owns.  With frames_in_flight = n >= 2 consecutive frames take turns
@@ -220,6 +229,7 @@ static void destroy_wavefront(shading_pass_t* pass) {
 	if (frames->readers_done) (void) hipEventDestroy(frames->readers_done);
 	free(frames->shaft_scratch);
 	(void) hipFree(frames->prepared.buffer);
+	(void) hipFree(frames->prepared.terms);
 	if (frames->prepared.stored) (void) hipEventDestroy(frames->prepared.stored);
 	free(frames->prepared.seen);
 	free(frames->prepared.scratch);
@@ -261,7 +271,10 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 	frames->band_count = environment_knob("VKR_BAND_COUNT", 0u, 0u, 4096u);
 	// VKR_PREPARED_POLYGONS_MIB: most device memory that the kept prepared polygons of a launch may take; 0: nothing is kept,
 	// every launch prepares its polygons itself.  (Config 3 at 1920x1080 keeps 2 040 MiB: 2.09 M threads x 4 lights x 256 B.)
+	// (with the sector terms of those polygons - as much again at V = 5 - where both fit: 4 080 MiB)
 	frames->prepared.budget_mib = environment_knob("VKR_PREPARED_POLYGONS_MIB", 4096u, 0u, 262144u);
+	// VKR_SECTOR_TERMS=0: the loading launches compute the terms of their sectors themselves
+	frames->prepared.terms_enabled = environment_knob("VKR_SECTOR_TERMS", 1u, 0u, 1u);
 	return frames;
 }
 
@@ -869,6 +882,10 @@ struct frame_plan {
 	// quads (16 B) of the buffer that the prepared polygons of the frame's one launch may take: plan_bands() has found room for
 	// them in the budgets; 0: this frame keeps none
 	size_t prepared_quads;
+	// ... and the sector terms of those polygons: the buffer of the kernel that loads with terms, and its quads - 0: the budgets
+	// hold the polygons alone (or VKR_SECTOR_TERMS=0), and the launches load without terms
+	const float4* terms;
+	size_t terms_quads;
 	// (table_in_memory: the kernel variants that keep one of their two polygon tables in device memory, shading_kernel.h psa_table_in_memory)
 	bool table_in_memory, hidden_terms, base_color, use_wide_tree, textured, pipelined;
 	uint32_t grid_blocks, table_bytes_per_workgroup, max_terms;
@@ -1056,7 +1073,7 @@ static int plan_bands(application_t* app, frame_plan* f) {
 	// time, and config 4, the frame that is rendered in bands, has no such kernel variant): one buffer per pass, counted against
 	// the budget of the wavefront buffers like the shafts' tables, and against VKR_PREPARED_POLYGONS_MIB.  (bind_textures() runs
 	// after this: a frame with light textures is turned away by choose_prepared_mode().)
-	f->prepared_quads = 0;
+	f->prepared_quads = f->terms_quads = 0;
 	if (f->band_count == 1 && frames->prepared.budget_mib != 0u && prepared_polygons_possible(app, f)) {
 		const uint32_t thread_count = f->blocks_per_band * 256u;
 		const size_t quads = (size_t) thread_count * f->p.light_count * (prepared_bytes_per_pair(f->capacity) / 16u);
@@ -1064,6 +1081,12 @@ static int plan_bands(application_t* app, frame_plan* f) {
 		if (bytes <= (double) frames->prepared.budget_mib * 1048576.0
 			&& f->depth * wavefront_bytes(thread_count, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, 0u) + bytes <= budget)
 			f->prepared_quads = quads;
+		// the terms count against both budgets together with the polygons; where only the polygons fit, the launch loads without
+		const size_t terms_quads = (size_t) thread_count * f->p.light_count * (sector_terms_bytes_per_pair(f->capacity) / 16u);
+		const double both = bytes + 16.0 * (double) terms_quads;
+		if (f->prepared_quads != 0 && frames->prepared.terms_enabled && both <= (double) frames->prepared.budget_mib * 1048576.0
+			&& f->depth * wavefront_bytes(thread_count, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, 0u) + both <= budget)
+			f->terms_quads = terms_quads;
 	}
 	return 0;
 }
@@ -1347,10 +1370,12 @@ static void forget_prepared_polygons(frame_pipeline* frames) {
 // moves and stops would free and allocate 2 GB each time.  (hipFree waits for the device: no launch still loads from it.)
 static void release_prepared_polygons(frame_pipeline* frames) {
 	forget_prepared_polygons(frames);
-	if (!frames || !frames->prepared.buffer) return;
+	if (!frames || (!frames->prepared.buffer && !frames->prepared.terms)) return;
 	(void) hipFree(frames->prepared.buffer);
+	(void) hipFree(frames->prepared.terms);
 	frames->prepared.buffer = NULL;
-	frames->prepared.buffer_quads = 0;
+	frames->prepared.terms = NULL;
+	frames->prepared.buffer_quads = frames->prepared.terms_quads = 0;
 }
 
 // Band step 4b: decides how this launch gets its prepared polygons -> f->prepared_mode, f->prepared
@@ -1362,6 +1387,7 @@ static int choose_prepared_mode(application_t* app, frame_plan* f, frame_context
 	const shade_params& p = f->p;
 	f->prepared_mode = kPreparedPlain;
 	f->prepared = NULL;
+	f->terms = NULL;
 	frame_pipeline* frames = f->frames;
 	if (!frames) return 0;
 	prepared_cache* cache = &frames->prepared;
@@ -1419,8 +1445,13 @@ static int choose_prepared_mode(application_t* app, frame_plan* f, frame_context
 		}
 	}
 	if (cache->state == kCacheValid || (cache->state == kCachePending && stream == cache->stored_stream)) {
-		f->prepared_mode = cache->last_mode = kPreparedLoading;
+		// (the terms were filled behind the storing launch, in front of the event: they are as complete as the polygons)
+		const bool with_terms = cache->terms != NULL && cache->terms_quads != 0;
+		f->prepared_mode = with_terms ? kPreparedLoadingTerms : kPreparedLoading;
+		cache->last_mode = kPreparedLoading;
 		f->prepared = cache->buffer;
+		f->terms = with_terms ? cache->terms : NULL;
+		++(with_terms ? cache->loaded_with_terms : cache->loaded_without_terms);
 	}
 	else if (cache->state == kCacheEmpty) {
 		// (plan_bands() has found room for the buffer.  One of another size goes first: freeing waits for the device, so no launch
@@ -1431,6 +1462,13 @@ static int choose_prepared_mode(application_t* app, frame_plan* f, frame_context
 			cache->buffer_quads = 0;
 		}
 		if (grow_device_buffer(&cache->buffer, &cache->buffer_quads, f->prepared_quads, sizeof(uint4), "Failed to allocate %.1f MiB for the prepared polygons.\n")) return 1;
+		// the terms by the same rules; an arrangement without room for them keeps none
+		if (cache->terms && cache->terms_quads != f->terms_quads) {
+			(void) hipFree(cache->terms);
+			cache->terms = NULL;
+			cache->terms_quads = 0;
+		}
+		if (f->terms_quads != 0 && grow_device_buffer(&cache->terms, &cache->terms_quads, f->terms_quads, sizeof(float4), "Failed to allocate %.1f MiB for the sector terms.\n")) return 1;
 		// launches in flight on other streams may still load what an earlier arrangement stored here.  (A launch outside the
 		// pipeline runs behind finish_frames(), join_frame_pipeline(): it waits for events that it is behind already.)
 		for (uint32_t c = 0; c != VKR_MAX_FRAMES_IN_FLIGHT; ++c) {
@@ -1440,17 +1478,28 @@ static int choose_prepared_mode(application_t* app, frame_plan* f, frame_context
 		f->prepared_mode = cache->last_mode = kPreparedStoring;
 		f->prepared = cache->buffer;
 	}
-	++cache->launches[f->prepared_mode];
+	// (mode 2 covers both loading kinds)
+	++cache->launches[f->prepared_mode == kPreparedLoadingTerms ? kPreparedLoading : f->prepared_mode];
 	return 0;
 }
 
-// ... and behind the launch: the event of a storing launch, or nothing kept after a launch that failed
-static void note_prepared_launch(frame_plan* f, int status, hipStream_t stream) {
+// ... and behind the launch: the terms kernel and the event of a storing launch, or nothing kept after a launch that failed
+static void note_prepared_launch(const application_t* app, frame_plan* f, int status, hipStream_t stream) {
 	frame_pipeline* frames = f->frames;
 	if (!frames) return;
 	if (status != 0) forget_prepared_polygons(frames);
 	else if (f->prepared_mode == kPreparedStoring) {
 		frames->prepared.stored_stream = stream;
+		// the sector terms of what the launch has stored, on its stream: the event that lets other streams load lies behind both
+		if (frames->prepared.terms) {
+			const sector_terms_launch_function_t fill = g_sector_terms_launchers[app->shading_pass.arithmetic_mode];
+			// (a kernel that the library lacks is an error, not a reason to load without terms)
+			if (!fill || fill(f->capacity, frames->prepared.buffer, frames->prepared.terms, f->p.thread_count, f->p.light_count, stream) != 0) {
+				printf("Failed to launch the kernel that fills the sector terms.\n");
+				forget_prepared_polygons(frames);
+				return;
+			}
+		}
 		if (hipEventRecord(frames->prepared.stored, stream) == hipSuccess) frames->prepared.state = kCachePending;
 		else forget_prepared_polygons(frames);
 	}
@@ -1465,7 +1514,7 @@ static int launch_shading(const application_t* app, const frame_plan* f, hipStre
 	if (f->prepared_mode != kPreparedPlain) {
 		// (a variant that prepared_polygons_possible() promises and the library lacks is an error, not a reason to run plain)
 		const prepared_launch_function_t launch = g_prepared_launchers[mode][f->strategy - kStrategySeparately];
-		return launch ? launch(f->technique, f->capacity, f->prepared_mode, f->prepared, p, p->block_count, stream) : -1;
+		return launch ? launch(f->technique, f->capacity, f->prepared_mode, f->prepared, f->terms, p, p->block_count, stream) : -1;
 	}
 	return g_launchers[mode + (p->light_texture_descriptors ? 3 : 0)][f->strategy](f->technique, f->capacity, f->ray_mode, p, p->block_count, stream);
 }
@@ -1577,7 +1626,7 @@ static int render_pass(application_t* app, void* out_radiance, void* out_rgb8) {
 		if (timed && band == 0) (void) hipEventRecord(timing_event(pass, slot, kTimingShadingStart), stream);
 		if (choose_prepared_mode(app, &f, frame, stream)) return 1;
 		status = launch_shading(app, &f, stream);
-		note_prepared_launch(&f, status, stream);
+		note_prepared_launch(app, &f, status, stream);
 		if (timed && band + 1 == f.band_count) (void) hipEventRecord(timing_event(pass, slot, kTimingShadingEnd), stream);
 		if (status == 0 && is_deferred(f.ray_mode)) {
 			launch_tracing(app, &f, frame, stream);
@@ -1882,6 +1931,18 @@ extern "C" int get_prepared_polygon_statistics(application_t* app, uint64_t out_
 	out_statistics[5] = cache->waited;
 	out_statistics[6] = cache->state;
 	out_statistics[7] = cache->budget_mib;
+	return 0;
+}
+
+// {bytes of the buffer of the sector terms, loading launches with terms, loading launches without} (include/vkr_shading_pass.h)
+extern "C" int get_sector_terms_statistics(application_t* app, uint64_t out_statistics[3]) {
+	memset(out_statistics, 0, 3 * sizeof(uint64_t));
+	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
+	if (!frames) return 1;
+	const prepared_cache* cache = &frames->prepared;
+	out_statistics[0] = (uint64_t) cache->terms_quads * sizeof(float4);
+	out_statistics[1] = cache->loaded_with_terms;
+	out_statistics[2] = cache->loaded_without_terms;
 	return 0;
 }
 

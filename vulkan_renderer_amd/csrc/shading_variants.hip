@@ -110,23 +110,42 @@ extern "C" int VKR_LAUNCH_NAME(int technique, int capacity, int rays, const shad
 #define VKR_PREPARED_LAUNCH_NAME VKR_CAT(vkr_launch_shade_prepared_exact_, VKR_STRATEGY, , )
 #endif
 template <int TECHNIQUE, int V>
-static int launch_prepared(int prepared_mode, prepared_quad* prepared, const shade_params& p, unsigned int grid_x, hipStream_t stream) {
+static int launch_prepared(int prepared_mode, prepared_quad* prepared, const sector_terms_quad* terms, const shade_params& p, unsigned int grid_x, hipStream_t stream) {
 	if constexpr (prepared_polygons_apply(VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE)) {
 		const dim3 grid(shade_grid_size(grid_x));
 		const uint32_t lds = shade_lds_bytes(VKR_STRATEGY, TECHNIQUE, V, VKR_MODE);
 		if (prepared_mode == kPreparedStoring) shade_pixels<VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE, kPreparedStoring><<<grid, kShadeThreads, lds, stream>>>(p, prepared);
 		else if (prepared_mode == kPreparedLoading) shade_pixels<VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE, kPreparedLoading><<<grid, kShadeThreads, lds, stream>>>(p, prepared);
+		else if (prepared_mode == kPreparedLoadingTerms && terms) shade_pixels<VKR_STRATEGY, TECHNIQUE, V, kRaysDeferredBlocks, VKR_MODE, kPreparedLoadingTerms><<<grid, kShadeThreads, lds, stream>>>(p, prepared, terms);
 		else return -1;
 		return hipGetLastError() != hipSuccess;
 	}
 	else return -1;
 }
 
-extern "C" int VKR_PREPARED_LAUNCH_NAME(int technique, int capacity, int prepared_mode, void* prepared, const shade_params* p, unsigned int grid_x, void* stream) {
+extern "C" int VKR_PREPARED_LAUNCH_NAME(int technique, int capacity, int prepared_mode, void* prepared, const void* terms, const shade_params* p, unsigned int grid_x, void* stream) {
 	if (!prepared || (technique != kTechniquePsa && technique != kTechniquePsaBiased) || (capacity != 4 && capacity != 5)) return -1;
 	prepared_quad* buffer = (prepared_quad*) prepared;
+	const sector_terms_quad* t = (const sector_terms_quad*) terms;
 	hipStream_t s = (hipStream_t) stream;
-	if (technique == kTechniquePsa) return capacity == 4 ? launch_prepared<kTechniquePsa, 4>(prepared_mode, buffer, *p, grid_x, s) : launch_prepared<kTechniquePsa, 5>(prepared_mode, buffer, *p, grid_x, s);
-	return capacity == 4 ? launch_prepared<kTechniquePsaBiased, 4>(prepared_mode, buffer, *p, grid_x, s) : launch_prepared<kTechniquePsaBiased, 5>(prepared_mode, buffer, *p, grid_x, s);
+	if (technique == kTechniquePsa) return capacity == 4 ? launch_prepared<kTechniquePsa, 4>(prepared_mode, buffer, t, *p, grid_x, s) : launch_prepared<kTechniquePsa, 5>(prepared_mode, buffer, t, *p, grid_x, s);
+	return capacity == 4 ? launch_prepared<kTechniquePsaBiased, 4>(prepared_mode, buffer, t, *p, grid_x, s) : launch_prepared<kTechniquePsaBiased, 5>(prepared_mode, buffer, t, *p, grid_x, s);
 }
+
+// The kernel that fills the sector terms, once per arithmetic mode: in the unit of the first strategy that keeps polygons
+#if VKR_STRATEGY == 2
+#if VKR_MATH_MODE == 2
+#define VKR_SECTOR_TERMS_LAUNCH_NAME vkr_launch_sector_terms_libm
+#else
+#define VKR_SECTOR_TERMS_LAUNCH_NAME vkr_launch_sector_terms_exact
+#endif
+extern "C" int VKR_SECTOR_TERMS_LAUNCH_NAME(int capacity, const void* prepared, void* terms, unsigned int thread_count, unsigned int light_count, void* stream) {
+	if (!prepared || !terms || (capacity != 4 && capacity != 5) || thread_count == 0 || light_count == 0) return -1;
+	const dim3 grid((thread_count + kShadeThreads - 1u) / kShadeThreads, light_count);
+	hipStream_t s = (hipStream_t) stream;
+	if (capacity == 4) k_sector_terms<4><<<grid, kShadeThreads, 2u * kPsaTableSlots(4) * kShadeThreads * 8u, s>>>((const prepared_quad*) prepared, (sector_terms_quad*) terms, thread_count);
+	else k_sector_terms<5><<<grid, kShadeThreads, 2u * kPsaTableSlots(5) * kShadeThreads * 8u, s>>>((const prepared_quad*) prepared, (sector_terms_quad*) terms, thread_count);
+	return hipGetLastError() != hipSuccess;
+}
+#endif
 #endif

@@ -498,6 +498,13 @@ class Renderer(HostScene):
                 "launches": {"plain": int(out[2]), "storing": int(out[3]), "loading": int(out[4])}, "waited": int(out[5]),
                 "state": ("empty", "pending", "valid")[int(out[6])], "budget_mib": int(out[7])}
 
+    def sector_terms_statistics(self):
+        """The sector terms that are kept with the prepared polygons where both fit: bytes of their buffer and the loading
+        launches so far with and without terms (include/vkr_shading_pass.h get_sector_terms_statistics)"""
+        out = (C.c_uint64 * 3)()
+        self.lib.get_sector_terms_statistics(C.byref(self.app), out)
+        return {"buffer_bytes": int(out[0]), "loaded_with_terms": int(out[1]), "loaded_without_terms": int(out[2])}
+
     def light_shaft_words(self):
         """The verdict words of the last launch as a (patches, lights) uint32 array (include/vkr_shading_pass.h
         read_back_light_shafts); empty when that launch ran without the shaft test"""
