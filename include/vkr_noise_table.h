@@ -41,8 +41,8 @@ VKR_API void set_noise_constants(uint32_t resolution_mask[2], uint32_t* texture_
    generate_noise_table() fills device_data by HIP kernels (csrc/noise_generators.hip, on device->stream), host_data by one
    read-back, sets resolution and random_seed = 3124705 like load_noise_table() and returns 0.  It returns 1 after printing
    one line, with the struct zeroed, for: device == NULL (there is no host build of the generators), noise_type_white
-   (load_noise_table() generates it), noise_type_ahmed and noise_type_blue_noise_dithered (blob types), and resolutions
-   outside the ranges below.  The rules that follow, the order of operations included, are the interface: the numpy
+   (load_noise_table() generates it), noise_type_ahmed (a blob type), noise_type_blue_noise_dithered (its annealing needs a
+   round count: generate_dithered_noise_table() below), and resolutions outside the ranges below.  The rules that follow, the order of operations included, are the interface: the numpy
    restatement vulkan_renderer_amd/noise_tables.py gives the same bytes.  wang() is vkr_wang_random_number (reference
    math_utilities.h:50-57); all integers are uint32_t.
 
@@ -84,5 +84,51 @@ VKR_API int generate_noise_table(noise_table_t* noise, const device_t* device, V
    file name for this type and resolution below the working directory (data/noise/..., the directories are created), so
    that load_noise_table() - and the reference itself - can read it back.  Returns 0 on success, 1 after printing one line */
 VKR_API int write_noise_table(const noise_table_t* noise, noise_type_t noise_type, const char* file_path);
+
+/* ---- noise_type_blue_noise_dithered: "a 2D blue noise dither array" (reference noise_table.h:48-51) after Georgiev and
+   Fajardo, Blue-noise dithered sampling, SIGGRAPH 2016 Talks: every pixel holds a 2D sample point, arranged by swaps that
+   lower an energy, so that neighbouring pixels hold distant points.  There is no reference file to match; the rule below
+   is the interface and vulkan_renderer_amd/noise_tables.py restates it.  It uses integers only, so the shape of a
+   parallel sum does not enter the result.  wang() and the Sobol sequence and Owen scrambling are those above; all
+   integers are uint32_t unless stated.
+
+   Resolution: W and H powers of two in 16 ... 256 with 512 <= W H <= 32768, D a power of two, 1 <= D <= 2^24;
+   round_count <= 2^22.  Layer k holds two independent arrays a = 2 k + p; channels 2 p and 2 p + 1 of a texel are x and y of
+   that pixel's 16-bit value.  N = W H, s = wang(wang(generator_seed) + a).
+
+   Value set: point j (j = 0 ... N - 1) is (c'_0 >> 16, c'_1 >> 16) of point j of the Sobol sequence, Owen-scrambled with
+   seed_d = wang(s + 0x9E3779B9 * (d + 1)).  Dimensions 0 and 1 are a (0,2)-sequence: the top log2(N) bits of either
+   channel are a permutation of 0 ... N - 1.
+   Initial assignment: pixel i = y W + x has the key wang(s + i); the pixel with the j-th smallest (key, pixel) gets point j.
+
+   Weights, computed in double and rounded to nearest: in space, for |dx|, |dy| <= 6,
+   Kq[dy][dx] = rint(65536 exp(-(dx^2 + dy^2) / 2.1^2)) with the centre set to 0; in value, for i = 0 ... 1448,
+   Gq[i] = rint(65536 exp(-((i + 0.5) / 2048) / 1^2)).  Both stay below 2^16: a product fits 32 bits.  Two values are
+   ax = min(|x - x'|, 65536 - |x - x'|) and ay likewise apart, r is the largest integer with r^2 <= ax^2 + ay^2, their weight
+   is Gq[r >> 5].  The local energy L(p, v) of pixel p holding v is the sum over the 13x13 toroidal window around p of
+   Kq[dy][dx] Gq[r(v, value of that neighbour) >> 5] as int64_t.
+
+   Round k (k = 0 ... round_count - 1) cuts the image into 16x16 tiles, T = (W / 16) (H / 16) of them, numbered row by row.
+   g = wang(wang(s ^ 0x9E3779B9) + k) moves the grid by ox = g & 15, oy = (g >> 4) & 15 and pairs the tiles by
+   mask = 1 + ((((g >> 8) & 0xFFFF) (T - 1)) >> 16).  Tile t = ty (W / 16) + tx offers the pixel
+   ((16 tx + ox + cx) mod W, (16 ty + oy + cy) mod H) with h = wang(wang(s + k) + t), cx = ((h & 0xFFFF) 10) >> 16,
+   cy = ((h >> 16) 10) >> 16.  For every pair (t, t ^ mask) with t < t ^ mask, with p and q their pixels holding v_p and v_q:
+   delta = L(p, v_q) + L(q, v_p) - L(p, v_p) - L(q, v_q), and the two values are exchanged iff delta < 0.  The pixels of a
+   round lie in the 10x10 cores of their tiles, more than 6 apart on the torus: no window holds another pixel of the
+   round, the swaps of a round do not see each other, and the sum of all local energies never rises.  n rounds are the
+   first n rounds of any longer run.
+
+   generate_dithered_noise_table() follows the conventions of generate_noise_table(): device_data by HIP kernels on
+   device->stream (at most VKR_DITHERED_ROUNDS_PER_LAUNCH rounds per launch; the table itself is the state between
+   launches), host_data by one read-back, random_seed = 3124705, 0 on success; 1 after printing one line, with the struct
+   zeroed, for device == NULL, a resolution outside the range and more than 2^22 rounds. */
+#define VKR_DITHERED_ROUNDS_PER_LAUNCH 4096
+VKR_API int generate_dithered_noise_table(noise_table_t* noise, const device_t* device, VkExtent3D resolution,
+                                          uint32_t generator_seed, uint32_t round_count);
+/* 2^19 for every resolution: the round count beyond which twice the rounds raise the mean distance between the values of
+   neighbouring pixels by less than 1 % (which also says why a renderer is served better by about 2^10) */
+VKR_API uint32_t get_default_dithered_round_count(VkExtent3D resolution);
+/* Kq, row by row from dy = -6, and Gq as the generator uses them */
+VKR_API void get_dithered_noise_weights(uint32_t spatial[169], uint32_t value[1449]);
 
 #endif

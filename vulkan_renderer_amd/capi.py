@@ -294,6 +294,9 @@ SIGNATURES = {
     "destroy_noise_table": (None, [P(NoiseTable), P(Device)]),
     "generate_noise_table": (C.c_int, [P(NoiseTable), P(Device), Extent3D, C.c_int32, C.c_uint32]),
     "write_noise_table": (C.c_int, [P(NoiseTable), C.c_int32, C.c_char_p]),
+    "generate_dithered_noise_table": (C.c_int, [P(NoiseTable), P(Device), Extent3D, C.c_uint32, C.c_uint32]),
+    "get_default_dithered_round_count": (C.c_uint32, [Extent3D]),
+    "get_dithered_noise_weights": (None, [P(C.c_uint32), P(C.c_uint32)]),
     "set_noise_constants": (None, [P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(NoiseTable), C.c_uint32]),
     "get_material_texture_suffix": (C.c_char_p, [C.c_int32]),
     "load_scene": (C.c_int, [P(Scene), P(Device), C.c_char_p, C.c_char_p, C.c_uint32]),

@@ -1,5 +1,6 @@
 // Noise tables generated on the device (include/vkr_noise_table.h generate_noise_table): the Sobol family, one thread per
-// point, and void-and-cluster blue noise, one workgroup per dither array.  Compiled without contraction like
+// point, and void-and-cluster blue noise, one workgroup per dither array; generate_dithered_noise_table: blue-noise
+// dithered sampling, one workgroup per array that anneals it in LDS, integers only.  Compiled without contraction like
 // frame_statistics.hip; every table is restated in numpy bit for bit (vulkan_renderer_amd/noise_tables.py).
 #include "vkr_noise_table.h"
 #include "host/vkr_internal.h"
@@ -280,6 +281,140 @@ template <uint32_t T> __global__ void __launch_bounds__(T) k_blue_arrays(blue_ar
 	}
 }
 
+// ---- blue-noise dithered sampling ----------------------------------------------------------------------------------
+
+constexpr uint32_t kDitheredRadius = 6, kDitheredSide = 2 * kDitheredRadius + 1, kDitheredWindow = kDitheredSide * kDitheredSide;
+constexpr uint32_t kDitheredValueWeights = 1449;
+
+struct dithered_args {
+	uint32_t log2_width, log2_height;
+	uint32_t seed;
+	uint32_t first_round, round_count;
+	// v[1][b] of the Sobol sequence for the bits b of a point index
+	uint32_t direction[16];
+	// Kq, then Gq
+	const uint32_t* weights;
+	// the table as packed values x | y << 16: word 2 * (layer * N + pixel) + pair
+	uint32_t* table;
+};
+
+__device__ static inline uint32_t* dithered_array_values(const dithered_args& a, uint32_t array) {
+	return a.table + ((((size_t) (array >> 1)) << (a.log2_width + a.log2_height)) << 1) + (array & 1u);
+}
+
+// The initial assignment, one lane per pixel: its rank j among the keys, then point j of the value set
+__global__ void __launch_bounds__(256) k_dithered_initial(dithered_args a) {
+	const uint32_t N = 1u << (a.log2_width + a.log2_height);
+	const uint32_t array = blockIdx.x, pixel = blockIdx.y * 256 + threadIdx.x;
+	const uint32_t s = wang(wang(a.seed) + array);
+	uint32_t key = wang(s + pixel), j = 0;
+	for (uint32_t q = 0; q != N; ++q) {
+		uint32_t other = wang(s + q);
+		j += (other < key || (other == key && q < pixel)) ? 1u : 0u;
+	}
+	// (dimension 0 is van der Corput: the XOR of 2^(31 - b) over the set bits b)
+	uint32_t c0 = __brev(j), c1 = 0;
+#pragma unroll
+	for (uint32_t b = 0; b != 16; ++b)
+		if ((j >> b) & 1u) c1 ^= a.direction[b];
+	uint32_t x = owen_scramble(c0, wang(s + 0x9E3779B9u), 16) >> 16;
+	uint32_t y = owen_scramble(c1, wang(s + 0x9E3779B9u * 2u), 16) >> 16;
+	dithered_array_values(a, array)[(size_t) pixel * 2] = x | (y << 16);
+}
+
+// Toroidal distance of two 16-bit coordinates held in the upper halves of a and b: min(|d|, 65536 - |d|) is the magnitude
+// of the difference as a signed 16-bit number
+__device__ static inline uint32_t dithered_axis_distance(uint32_t a_upper, uint32_t b_upper) {
+	int d = (int) (a_upper - b_upper) >> 16;
+	return (uint32_t) (d < 0 ? -d : d);
+}
+
+// (__umul24 returns an int)
+__device__ static inline uint32_t dithered_mul24(uint32_t a, uint32_t b) { return (uint32_t) __umul24(a, b); }
+
+// Gq's index of a value and a neighbour, both as (x << 16, y << 16): r >> 5 with r the largest integer whose square is at
+// most ax^2 + ay^2 <= 2^31.  The square root instruction is within 0.01 of the root, so its floor is at most one off.
+// (Every factor is below 2^24: the 24-bit multiplier runs at the full rate, the 32-bit one does not.)
+__device__ static inline uint32_t dithered_value_index(uint32_t ax_upper, uint32_t ay_upper, uint32_t bx_upper, uint32_t by_upper) {
+	uint32_t ax = dithered_axis_distance(ax_upper, bx_upper), ay = dithered_axis_distance(ay_upper, by_upper);
+	uint32_t squared = dithered_mul24(ax, ax) + dithered_mul24(ay, ay);
+	uint32_t r = (uint32_t) __builtin_amdgcn_sqrtf((float) squared), rr = dithered_mul24(r, r);
+	// (at most one of the two holds; (r + 1)^2 = rr + 2 r + 1)
+	return (r - (rr > squared ? 1u : 0u) + (rr + 2u * r + 1u <= squared ? 1u : 0u)) >> 5;
+}
+
+// One workgroup per array, G lanes per swap: blockDim.x = G * T / 2 with T the tile count, G a divisor of 64.  The values
+// of the array stay in LDS for round_count rounds.  The 169 entries of a window are dealt to the lanes of a swap once,
+// before the first round; a lane sums its part of delta, first around p, then around q, the group adds up by shuffles
+// and lane 0 exchanges the values.  One barrier per round: no window of a round holds a pixel that the round may change.
+template <uint32_t G> __global__ void __launch_bounds__(1024) k_dithered_rounds(dithered_args a) {
+	extern __shared__ __align__(16) unsigned char lds[];
+	constexpr uint32_t kSteps = (kDitheredWindow + G - 1) / G;
+	const uint32_t log2_width = a.log2_width, N = 1u << (log2_width + a.log2_height);
+	const uint32_t width_mask = (1u << log2_width) - 1u, height_mask = (1u << a.log2_height) - 1u;
+	const uint32_t tiles = N >> 8, tiles_x_mask = (width_mask >> 4), log2_tiles_x = log2_width - 4;
+	uint32_t* V = (uint32_t*) lds;
+	uint32_t* Gq = V + N;
+	const uint32_t array = blockIdx.x, lane = threadIdx.x % G, swap = threadIdx.x / G;
+	uint32_t* values = dithered_array_values(a, array);
+	for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) V[i] = values[(size_t) i * 2];
+	for (uint32_t i = threadIdx.x; i < kDitheredValueWeights; i += blockDim.x) Gq[i] = a.weights[kDitheredWindow + i];
+	// entry w = lane + G * j of either window: the offsets to add to the centre modulo W and H, and Kq; entries past the
+	// end have weight 0
+	uint32_t offset_x[kSteps], offset_y[kSteps], weight[kSteps];
+#pragma unroll
+	for (uint32_t j = 0; j != kSteps; ++j) {
+		uint32_t w = lane + G * j;
+		bool valid = w < kDitheredWindow;
+		if (!valid) w = 0;
+		offset_x[j] = (w % kDitheredSide - kDitheredRadius) & width_mask;
+		offset_y[j] = (w / kDitheredSide - kDitheredRadius) & height_mask;
+		weight[j] = valid ? a.weights[w] : 0u;
+	}
+	const uint32_t s = wang(wang(a.seed) + array), grid_base = wang(s ^ 0x9E3779B9u);
+	__syncthreads();
+	for (uint32_t k = a.first_round; k != a.first_round + a.round_count; ++k) {
+		uint32_t g = wang(grid_base + k), tile_base = wang(s + k);
+		uint32_t mask = 1u + ((((g >> 8) & 0xFFFFu) * (tiles - 1u)) >> 16);
+		// the pairs (t, t ^ mask) with t < t ^ mask: the highest bit of the mask is clear in t
+		uint32_t high = 31u - (uint32_t) __clz((int) mask);
+		uint32_t tile[2], x[2], y[2], pixel[2], value[2];
+		tile[0] = ((swap >> high) << (high + 1u)) | (swap & ((1u << high) - 1u));
+		tile[1] = tile[0] ^ mask;
+#pragma unroll
+		for (uint32_t i = 0; i != 2; ++i) {
+			uint32_t h = wang(tile_base + tile[i]);
+			x[i] = (16u * (tile[i] & tiles_x_mask) + (g & 15u) + (((h & 0xFFFFu) * 10u) >> 16)) & width_mask;
+			y[i] = (16u * (tile[i] >> log2_tiles_x) + ((g >> 4) & 15u) + (((h >> 16) * 10u) >> 16)) & height_mask;
+			pixel[i] = (y[i] << log2_width) | x[i];
+			value[i] = V[pixel[i]];
+		}
+		const uint32_t value_x[2] = {value[0] << 16, value[1] << 16}, value_y[2] = {value[0] & 0xFFFF0000u, value[1] & 0xFFFF0000u};
+		long long delta = 0;
+#pragma unroll
+		for (uint32_t i = 0; i != 2; ++i) {
+#pragma unroll
+			for (uint32_t j = 0; j != kSteps; ++j) {
+				uint32_t nx = (x[i] + offset_x[j]) & width_mask, ny = (y[i] + offset_y[j]) & height_mask;
+				uint32_t neighbour = V[(ny << log2_width) | nx];
+				uint32_t neighbour_x = neighbour << 16, neighbour_y = neighbour & 0xFFFF0000u;
+				// the pixel's own value leaves, the other one comes (32-bit products, 64-bit sum)
+				uint32_t comes = Gq[dithered_value_index(value_x[1 - i], value_y[1 - i], neighbour_x, neighbour_y)];
+				uint32_t leaves = Gq[dithered_value_index(value_x[i], value_y[i], neighbour_x, neighbour_y)];
+				delta += (long long) dithered_mul24(weight[j], comes) - (long long) dithered_mul24(weight[j], leaves);
+			}
+		}
+#pragma unroll
+		for (uint32_t offset = G / 2; offset != 0; offset >>= 1) delta += __shfl_xor(delta, (int) offset);
+		if (lane == 0 && delta < 0) {
+			V[pixel[0]] = value[1];
+			V[pixel[1]] = value[0];
+		}
+		__syncthreads();
+	}
+	for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) values[(size_t) i * 2] = V[i];
+}
+
 static uint32_t log2_of(uint32_t x) {
 	uint32_t l = 0;
 	while ((1u << l) < x) ++l;
@@ -372,6 +507,91 @@ extern "C" int generate_noise_table(noise_table_t* noise, const device_t* device
 	if (!noise->host_data) printf("Out of memory for a noise table of %llu bytes.\n", (unsigned long long) bytes);
 	failed = failed || (sobol_family ? generate_sobol(noise->device_data, stream, resolution, noise_type, generator_seed) : generate_blue(noise->device_data, stream, resolution, generator_seed))
 		|| vkr_copy_to_host(noise->host_data, noise->device_data, bytes, device);
+	if (failed) {
+		destroy_noise_table(noise, device);
+		return 1;
+	}
+	noise->resolution = resolution;
+	noise->random_seed = 3124705;
+	return 0;
+}
+
+extern "C" void get_dithered_noise_weights(uint32_t spatial[169], uint32_t value[1449]) {
+	for (uint32_t w = 0; w != kDitheredWindow; ++w) {
+		double dx = (double) (w % kDitheredSide) - (double) kDitheredRadius, dy = (double) (w / kDitheredSide) - (double) kDitheredRadius;
+		spatial[w] = (uint32_t) rint(65536.0 * exp(-(dx * dx + dy * dy) / (2.1 * 2.1)));
+	}
+	spatial[kDitheredWindow / 2] = 0;
+	for (uint32_t i = 0; i != kDitheredValueWeights; ++i)
+		value[i] = (uint32_t) rint(65536.0 * exp(-(((double) i + 0.5) / 2048.0) / (1.0 * 1.0)));
+}
+
+extern "C" uint32_t get_default_dithered_round_count(VkExtent3D resolution) {
+	// A round offers one pixel per 16x16 tile whatever the resolution, so the rounds a pixel needs do not grow with
+	// the table; measured at 128x128, where 2^20 rounds gain 0.9 % over these
+	(void) resolution;
+	return 1u << 19;
+}
+
+template <uint32_t G> static int launch_dithered_rounds(const dithered_args& args, uint32_t array_count, uint32_t threads, size_t lds_bytes, hipStream_t stream) {
+	// (64 KiB of values and the value weights at 128x128: beyond the default limit of a workgroup)
+	if (hip_failed(hipFuncSetAttribute((const void*) k_dithered_rounds<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes), "raising the LDS limit of the dithered sampling kernel"))
+		return 1;
+	k_dithered_rounds<G><<<array_count, threads, lds_bytes, stream>>>(args);
+	return hip_failed(hipGetLastError(), "annealing the dithered sampling table");
+}
+
+extern "C" int generate_dithered_noise_table(noise_table_t* noise, const device_t* device, VkExtent3D resolution, uint32_t generator_seed, uint32_t round_count) {
+	memset(noise, 0, sizeof(*noise));
+	uint32_t W = resolution.width, H = resolution.height, D = resolution.depth;
+	if (!device) {
+		printf("generate_dithered_noise_table() needs a device: the generator is a HIP kernel.\n");
+		return 1;
+	}
+	if (!(is_power_of_two(W) && is_power_of_two(H) && W >= 16 && W <= 256 && H >= 16 && H <= 256 && W * H >= 512 && W * H <= 32768 && is_power_of_two(D) && D <= (1u << 24))) {
+		printf("A dithered sampling table needs W and H powers of two in 16 ... 256 with 512 <= W H <= 32768 and D a power of two, not %ux%ux%u.\n", W, H, D);
+		return 1;
+	}
+	if (round_count > (1u << 22)) {
+		printf("A dithered sampling table takes at most %u rounds, not %u.\n", 1u << 22, round_count);
+		return 1;
+	}
+	uint32_t N = W * H, array_count = 2 * D, swap_count = N / 512;
+	size_t bytes = sizeof(uint16_t) * 4 * (size_t) N * D;
+	hipStream_t stream = (hipStream_t) device->stream;
+	uint32_t weights_host[kDitheredWindow + kDitheredValueWeights];
+	get_dithered_noise_weights(weights_host, weights_host + kDitheredWindow);
+	uint32_t v[4][32];
+	fill_direction_numbers(v);
+	dithered_args args;
+	args.log2_width = log2_of(W); args.log2_height = log2_of(H);
+	args.seed = generator_seed;
+	args.first_round = 0; args.round_count = 0;
+	for (uint32_t b = 0; b != 16; ++b) args.direction[b] = v[1][b];
+	uint32_t* weights = NULL;
+	noise->host_data = (uint16_t*) malloc(bytes);
+	if (!noise->host_data) printf("Out of memory for a noise table of %llu bytes.\n", (unsigned long long) bytes);
+	int failed = !noise->host_data || vkr_device_alloc(&noise->device_data, device, bytes, "the noise table")
+		|| hip_failed(hipMalloc(&weights, sizeof(weights_host)), "allocating the weights of the dithered sampling table")
+		|| hip_failed(hipMemcpyAsync(weights, weights_host, sizeof(weights_host), hipMemcpyHostToDevice, stream), "uploading the weights of the dithered sampling table");
+	args.weights = weights; args.table = (uint32_t*) noise->device_data;
+	if (!failed) {
+		k_dithered_initial<<<dim3(array_count, N / 256), 256, 0, stream>>>(args);
+		failed = hip_failed(hipGetLastError(), "assigning the values of the dithered sampling table");
+	}
+	// as many lanes per swap as a workgroup of 1024 has for it, at most a wave
+	size_t lds_bytes = sizeof(uint32_t) * ((size_t) N + kDitheredValueWeights);
+	for (uint32_t first = 0; !failed && first < round_count; first += VKR_DITHERED_ROUNDS_PER_LAUNCH) {
+		args.first_round = first;
+		args.round_count = round_count - first < VKR_DITHERED_ROUNDS_PER_LAUNCH ? round_count - first : VKR_DITHERED_ROUNDS_PER_LAUNCH;
+		if (swap_count <= 16) failed = launch_dithered_rounds<64>(args, array_count, 64 * swap_count, lds_bytes, stream);
+		else if (swap_count == 32) failed = launch_dithered_rounds<32>(args, array_count, 1024, lds_bytes, stream);
+		else failed = launch_dithered_rounds<16>(args, array_count, 1024, lds_bytes, stream);
+	}
+	// (the upload reads weights_host, the kernels the weights)
+	failed = hip_failed(hipStreamSynchronize(stream), "generating the dithered sampling table") || failed;
+	if (weights) (void) hipFree(weights);
+	failed = failed || vkr_copy_to_host(noise->host_data, noise->device_data, bytes, device);
 	if (failed) {
 		destroy_noise_table(noise, device);
 		return 1;

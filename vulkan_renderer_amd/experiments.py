@@ -12,7 +12,7 @@ with the reference's relative paths (data/attic.vks, data/quicksaves/..., data/g
 data/noise/...).  --synthetic writes a generated stand-in data set (one synthetic scene
 under every scene name, white noise instead of the Ahmed table, default light) so the
 whole procedure can be exercised without the downloaded assets.  --noise TYPE replaces the experiment's noise table by
-one generated on the device (blue, sobol, owen, burley_owen: include/vkr_noise_table.h generate_noise_table).  The table, the path
+one generated on the device (blue, sobol, owen, burley_owen, blue_noise_dithered: include/vkr_noise_table.h).  The table, the path
 handling, the screenshot encoders and the file writers are C code in libvkr_shading.so;
 this module only sequences the calls."""
 import argparse
@@ -190,7 +190,7 @@ def main(argv=None):
     ap.add_argument("--jpg", action="store_true", help="store a *.jpg, encoded on the device at quality 70, next to the *.png (not with --hdr)")
     ap.add_argument("--no-png", action="store_true", help="with --jpg: store the *.jpg instead of the *.png")
     ap.add_argument("--accumulate", type=int, default=0, metavar="N", help="store the mean of N frames with animated noise instead of the last frame")
-    ap.add_argument("--noise", default=None, choices=["blue", "sobol", "owen", "burley_owen"], help="generate this noise table on the device instead of loading the experiment's")
+    ap.add_argument("--noise", default=None, choices=["blue", "sobol", "owen", "burley_owen", "blue_noise_dithered"], help="generate this noise table on the device instead of loading the experiment's")
     ap.add_argument("--ltc", default="synthetic", choices=["synthetic", "fitted"], help="fitted: fit the LTC table on the device instead of reading data/ggx_ltc_fit (synthetic: the files of the data root, which --synthetic fills with placeholder fits)")
     args = ap.parse_args(argv)
     if args.jpg and (args.hdr or args.device_hdr):

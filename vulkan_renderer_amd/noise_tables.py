@@ -1,11 +1,14 @@
 """The generated noise tables (include/vkr_noise_table.h generate_noise_table, csrc/noise_generators.hip) restated in
-numpy, bit for bit: the Sobol family (sobol, owen, burley_owen) and the void-and-cluster blue noise arrays.  Every rule
-here is a rule of the header; the order of the float32 additions of the blue noise energies is part of it.
+numpy, bit for bit: the Sobol family (sobol, owen, burley_owen), the void-and-cluster blue noise arrays and the annealed
+arrays of blue-noise dithered sampling (generate_dithered_noise_table).  Every rule here is a rule of the header; the
+order of the float32 additions of the blue noise energies is part of it.
 
     python -m vulkan_renderer_amd.noise_tables --type owen [--resolution W H D] [--seed n] --data-root DIR
+    python -m vulkan_renderer_amd.noise_tables --type blue_noise_dithered [--rounds N] [--verify] --data-root DIR
 
 generates the table on the device and writes DIR/data/noise/<the reference's file name for that type and resolution>,
-where load_noise_table() - and the reference itself - look for it."""
+where load_noise_table() - and the reference itself - look for it.  --verify compares the device's table with the
+restatement in every byte first (numpy needs about 0.4 ms per round and array of a dithered table)."""
 import argparse
 import os
 import sys
@@ -13,11 +16,19 @@ import sys
 import numpy as np
 
 TYPES = {"white": 0, "blue": 1, "ahmed": 2, "sobol": 4, "owen": 5, "burley_owen": 6, "blue_noise_dithered": 7}
-GENERATED_TYPES = ("blue", "sobol", "owen", "burley_owen")
+GENERATED_TYPES = ("blue", "sobol", "owen", "burley_owen", "blue_noise_dithered")
 FILE_STEMS = {"blue": "blue_noise_rgba", "sobol": "sobol_2d_rgba", "owen": "owen_2d_rgba", "burley_owen": "burley_owen_2d_rgba",
               "ahmed": "ahmed_2d_rgba", "blue_noise_dithered": "dithered_2d_rgba"}
 RANDOM_SEED = 3124705  # noise_table_t.random_seed of a fresh table
 BLUE_SIGMA = 1.5
+# blue-noise dithered sampling: the window is (2 * 6 + 1)^2 pixels, exp(-d^2 / 2.1^2) in space and exp(-d / 1^2) in value
+DITHERED_RADIUS = 6
+DITHERED_SPATIAL_SIGMA = 2.1
+DITHERED_VALUE_SIGMA = 1.0
+DITHERED_VALUE_WEIGHTS = 1449
+DITHERED_MAX_ROUNDS = 1 << 22
+# VKR_DITHERED_ROUNDS_PER_LAUNCH of the header: a call is split into kernel launches of at most so many rounds
+DITHERED_ROUNDS_PER_LAUNCH = 4096
 # Joe-Kuo direction numbers of dimensions 1 ... 3 as (s, a, m); dimension 0 is van der Corput
 JOE_KUO = ((1, 0, (1,)), (2, 1, (1, 3)), (3, 1, (1, 3, 1)))
 
@@ -30,6 +41,8 @@ def file_name(noise_type, resolution):
 
 
 def default_resolution(noise_type):
+    if noise_type == "blue_noise_dithered":
+        return (128, 128, 1)
     return (64, 64, 64) if noise_type == "blue" else (256, 256, 64)
 
 
@@ -275,9 +288,194 @@ def blue_table(width, height, depth, seed=0):
     return table
 
 
-def table(noise_type, resolution=None, seed=0):
-    """Any generated table as uint16 (D, H, W, 4)"""
+# ---- blue-noise dithered sampling ------------------------------------------------------------------------------------
+
+def dithered_weights():
+    """(Kq, Gq) of the header as uint32: the 13 x 13 spatial weights (centre 0) and the 1449 value weights, rounded from
+    double to 16 fractional bits"""
+    d = np.arange(-DITHERED_RADIUS, DITHERED_RADIUS + 1, dtype=np.float64)
+    spatial = np.rint(65536.0 * np.exp(-(d[None, :] ** 2 + d[:, None] ** 2) / (DITHERED_SPATIAL_SIGMA * DITHERED_SPATIAL_SIGMA)))
+    spatial[DITHERED_RADIUS, DITHERED_RADIUS] = 0.0
+    value = np.rint(65536.0 * np.exp(-((np.arange(DITHERED_VALUE_WEIGHTS, dtype=np.float64) + 0.5) / 2048.0) / (DITHERED_VALUE_SIGMA * DITHERED_VALUE_SIGMA)))
+    return spatial.astype(U32), value.astype(U32)
+
+
+def check_dithered_resolution(width, height, depth, rounds=0):
+    for extent in (width, height):
+        if extent & (extent - 1) or not 16 <= extent <= 256:
+            raise ValueError("dithered sampling needs W and H powers of two in 16 ... 256")
+    if not 512 <= width * height <= 32768:
+        raise ValueError("dithered sampling needs 512 <= W H <= 32768")
+    if depth < 1 or depth & (depth - 1) or depth > 1 << 24:
+        raise ValueError("dithered sampling needs D a power of two, at most 2^24")
+    if not 0 <= rounds <= DITHERED_MAX_ROUNDS:
+        raise ValueError("dithered sampling takes at most 2^22 rounds")
+
+
+def dithered_array_seed(seed, a):
+    """s of the header: wang(wang(generator_seed) + a)"""
+    return _wang_int(_wang_int(seed) + a)
+
+
+def dithered_values(width, height, seed, a):
+    """The value set of array a = 2 * layer + pair in point order, uint32 (N,) packed x | y << 16: the top 16 bits of
+    dimensions 0 and 1 of the first N Sobol points, Owen-scrambled with the seeds of s"""
+    check_dithered_resolution(width, height, 1)
+    s = dithered_array_seed(seed, a)
+    c = sobol_points(0, width * height)
+    x = owen_scramble(c[0], dimension_seed(s, 0), 16) >> U32(16)
+    y = owen_scramble(c[1], dimension_seed(s, 1), 16) >> U32(16)
+    return x | (y << U32(16))
+
+
+def dithered_initial(width, height, seed, a):
+    """The assignment before the first round, uint32 (N,) packed by pixel: the pixel with the j-th smallest
+    (wang(s + pixel), pixel) holds point j"""
+    n = width * height
+    s = dithered_array_seed(seed, a)
+    keys = wang(np.arange(n, dtype=U32) + U32(s))
+    order = np.lexsort((np.arange(n), keys))
+    packed = np.empty(n, U32)
+    packed[order] = dithered_values(width, height, seed, a)
+    return packed
+
+
+def dithered_round_pixels(width, height, seed, a, k):
+    """(pixels, mask) of round k: the pixel index y W + x that every 16 x 16 tile offers, int64 (T,) in tile order, and the
+    mask that pairs tile t with tile t ^ mask"""
+    s = dithered_array_seed(seed, a)
+    tiles_x, tiles_y = width // 16, height // 16
+    tile_count = tiles_x * tiles_y
+    g = _wang_int(_wang_int(s ^ 0x9E3779B9) + k)
+    shift_x, shift_y = g & 15, (g >> 4) & 15
+    mask = 1 + ((((g >> 8) & 0xFFFF) * (tile_count - 1)) >> 16)
+    t = np.arange(tile_count, dtype=U32)
+    h = wang(t + U32(_wang_int(s + k)))
+    core_x = (((h & U32(0xFFFF)) * U32(10)) >> U32(16)).astype(np.int64)
+    core_y = (((h >> U32(16)) * U32(10)) >> U32(16)).astype(np.int64)
+    t = t.astype(np.int64)
+    x = (16 * (t % tiles_x) + shift_x + core_x) % width
+    y = (16 * (t // tiles_x) + shift_y + core_y) % height
+    return y * width + x, mask
+
+
+def _dithered_value_index(a, b):
+    """i of the header for packed values: floor(sqrt(ax^2 + ay^2)) >> 5 over toroidal differences, exact"""
+    a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    ax = np.abs((a & 0xFFFF) - (b & 0xFFFF))
+    ay = np.abs((a >> 16) - (b >> 16))
+    ax, ay = np.minimum(ax, 65536 - ax), np.minimum(ay, 65536 - ay)
+    squared = ax * ax + ay * ay
+    r = np.floor(np.sqrt(squared.astype(np.float64))).astype(np.int64)
+    r -= r * r > squared
+    r += (r + 1) * (r + 1) <= squared
+    return r >> 5
+
+
+def _dithered_windows(width, height, pixels):
+    """Pixel indices (len(pixels), 169) of the toroidal 13 x 13 windows around `pixels`, row-major like Kq"""
+    d = np.arange(-DITHERED_RADIUS, DITHERED_RADIUS + 1)
+    x = (pixels[:, None, None] % width + d[None, None, :]) % width
+    y = (pixels[:, None, None] // width + d[None, :, None]) % height
+    return (y * width + x).reshape(len(pixels), -1)
+
+
+def dithered_rounds(packed, width, height, seed, a, first, count, deltas=None):
+    """Rounds first ... first + count - 1 on the assignment `packed` (uint32 (N,), changed in place).  `deltas`, a list,
+    receives the sum of the accepted deltas of every round."""
+    spatial, value = dithered_weights()
+    spatial, value = spatial.ravel().astype(np.int64), value.astype(np.int64)
+    tile_count = (width // 16) * (height // 16)
+    t = np.arange(tile_count)
+    for k in range(first, first + count):
+        pixels, mask = dithered_round_pixels(width, height, seed, a, k)
+        lower = t[t < (t ^ mask)]
+        p, q = pixels[lower], pixels[lower ^ mask]
+        around_p, around_q = packed[_dithered_windows(width, height, p)], packed[_dithered_windows(width, height, q)]
+        vp, vq = packed[p], packed[q]
+
+        def local(neighbours, v):
+            return (spatial[None, :] * value[_dithered_value_index(v[:, None], neighbours)]).sum(axis=1)
+        delta = local(around_p, vq) + local(around_q, vp) - local(around_p, vp) - local(around_q, vq)
+        accepted = delta < 0
+        packed[p[accepted]], packed[q[accepted]] = vq[accepted], vp[accepted]
+        if deltas is not None:
+            deltas.append(int(delta[accepted].sum()))
+    return packed
+
+
+def _dithered_unpack(packed, width, height):
+    return np.stack([packed & U32(0xFFFF), packed >> U32(16)], -1).astype(np.uint16).reshape(height, width, 2)
+
+
+def dithered_array(width, height, seed, a, rounds):
+    """Array a = 2 * layer + pair after `rounds` rounds as uint16 (H, W, 2): x and y of every pixel's value"""
+    check_dithered_resolution(width, height, 1, rounds)
+    packed = dithered_rounds(dithered_initial(width, height, seed, a), width, height, seed, a, 0, rounds)
+    return _dithered_unpack(packed, width, height)
+
+
+def dithered_table(width, height, depth, seed=0, rounds=0):
+    check_dithered_resolution(width, height, depth, rounds)
+    table = np.zeros((depth, height, width, 4), np.uint16)
+    for layer in range(depth):
+        for pair in range(2):
+            table[layer, :, :, 2 * pair:2 * pair + 2] = dithered_array(width, height, seed, 2 * layer + pair, rounds)
+    return table
+
+
+def _dithered_pack(array):
+    array = np.asarray(array)
+    return (array[..., 0].astype(U32) | (array[..., 1].astype(U32) << U32(16))).ravel()
+
+
+def dithered_energy(array):
+    """Total energy of one array (H, W, 2) as a Python int: the local energies L(p, v_p) of the header summed over all
+    pixels and halved - every unordered pair of pixels once, so that a swap changes it by its delta"""
+    height, width, _ = np.shape(array)
+    packed = _dithered_pack(array)
+    spatial, value = dithered_weights()
+    spatial, value = spatial.ravel().astype(np.int64), value.astype(np.int64)
+    total = 0
+    # (in slices: the windows of 32768 pixels at once are 44 MB of indices)
+    for first in range(0, packed.size, 4096):
+        pixels = np.arange(first, min(first + 4096, packed.size))
+        neighbours = packed[_dithered_windows(width, height, pixels)]
+        total += int((spatial[None, :] * value[_dithered_value_index(packed[pixels][:, None], neighbours)]).sum())
+    assert total % 2 == 0
+    return total // 2
+
+
+def dithered_low_frequency_share(array):
+    """Mean power of fft2(exp(2 pi i v / 65536)), both coordinates of v added, over the frequencies 0 < |f| <= 1 / 8 cycles
+    per pixel, divided by the mean over all f != 0: 1 for white noise, small where neighbours hold distant values"""
+    array = np.asarray(array, np.float64)
+    height, width, _ = array.shape
+    power = sum(np.abs(np.fft.fft2(np.exp(2.0j * np.pi * array[..., c] / 65536.0))) ** 2 for c in range(2))
+    k, l = np.arange(width), np.arange(height)
+    radius = np.hypot(np.minimum(k, width - k)[None, :] / width, np.minimum(l, height - l)[:, None] / height)
+    return float(power[(radius > 0) & (radius <= 0.125)].mean() / power[radius > 0].mean())
+
+
+def dithered_neighbour_distance(array):
+    """Mean toroidal distance between the values of 4-neighbours (the pixels wrap around too), in units of the value
+    range: 0.3826 for independent uniform values, at most 0.7071"""
+    packed = _dithered_pack(array).reshape(np.shape(array)[:2]).astype(np.int64)
+    total = 0.0
+    for axis in (0, 1):
+        other = np.roll(packed, 1, axis)
+        ax = np.abs((packed & 0xFFFF) - (other & 0xFFFF))
+        ay = np.abs((packed >> 16) - (other >> 16))
+        ax, ay = np.minimum(ax, 65536 - ax), np.minimum(ay, 65536 - ay)
+        total += float(np.hypot(ax, ay).mean()) / 65536.0
+    return total / 2.0
+
+
+def table(noise_type, resolution=None, seed=0, rounds=0):
+    """Any generated table as uint16 (D, H, W, 4); rounds: of the dithered table only"""
     width, height, depth = resolution or default_resolution(noise_type)
+    if noise_type == "blue_noise_dithered":
+        return dithered_table(width, height, depth, seed, rounds)
     if noise_type == "blue":
         return blue_table(width, height, depth, seed)
     check_sobol_resolution(width, height, depth)
@@ -300,11 +498,28 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--data-root", required=True, help="directory that receives data/noise/<file>")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--rounds", type=int, default=None, help="annealing rounds of blue_noise_dithered (default: get_default_dithered_round_count)")
+    ap.add_argument("--verify", action="store_true", help="compare the device's table with the numpy restatement before it is written")
     args = ap.parse_args(argv)
+    if args.rounds is not None and args.type != "blue_noise_dithered":
+        ap.error("--rounds belongs to --type blue_noise_dithered")
     from . import renderer
     r = renderer.Renderer(hip_device=args.device)
     try:
-        milliseconds = r.generate_noise_table(args.type, args.resolution, args.seed)
+        milliseconds = r.generate_noise_table(args.type, args.resolution, args.seed, args.rounds)
+        if args.verify:
+            n = r.app.noise_table.resolution
+            resolution = (n.width, n.height, n.depth)
+            got = np.ctypeslib.as_array(r.app.noise_table.host_data, (n.depth, n.height, n.width, 4))
+            if args.type == "blue_noise_dithered":
+                rounds = r.lib.get_default_dithered_round_count(n) if args.rounds is None else args.rounds
+                expected = table(args.type, resolution, args.seed, rounds)
+            else:
+                expected = table(args.type, resolution, args.seed)
+            differing = int((got != expected).sum())
+            print("verify: %d of %d channels differ from the restatement" % (differing, got.size))
+            if differing:
+                return 1
         path = r.write_noise_table(args.type, args.data_root)
     finally:
         r.close()

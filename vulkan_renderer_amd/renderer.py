@@ -295,19 +295,29 @@ class Renderer(HostScene):
         t = self.app.tile_schedule
         t.tile_size, t.rank, t.rank_count, t.slab_layout = tile_size, rank, rank_count, int(slab_layout)
 
-    def generate_noise_table(self, noise_type, resolution=None, seed=0):
+    def generate_noise_table(self, noise_type, resolution=None, seed=0, rounds=None):
         """Replaces the noise table by one generated on the device (include/vkr_noise_table.h generate_noise_table):
-        "blue", "sobol", "owen" or "burley_owen"; resolution None: the default of the type.  Returns the milliseconds
-        the call took (allocation, kernels and read-back).  Frames in flight are finished first: they read the old table."""
+        "blue", "sobol", "owen", "burley_owen" or "blue_noise_dithered" (generate_dithered_noise_table, annealed for
+        `rounds` rounds; None: get_default_dithered_round_count); resolution None: the default of the type.  Returns the
+        milliseconds the call took (allocation, kernels and read-back).  Frames in flight are finished first: they read
+        the old table."""
         import time
         t = _enum(NOISE, noise_type)
+        dithered = t == NOISE["blue_noise_dithered"]
+        if rounds is not None and not dithered:
+            raise ValueError("only the blue_noise_dithered table is generated in rounds")
         if self.app.shading_pass.constants_device:
             self.finish_frames()
             self.sync()
         res = self.lib.get_default_noise_resolution(t) if resolution is None else capi.Extent3D(*resolution)
+        if dithered and rounds is None:
+            rounds = self.lib.get_default_dithered_round_count(res)
         self.lib.destroy_noise_table(C.byref(self.app.noise_table), self._dev())
         start = time.perf_counter()
-        if self.lib.generate_noise_table(C.byref(self.app.noise_table), self._dev(), res, t, int(seed) & 0xFFFFFFFF):
+        if dithered:
+            if not 0 <= int(rounds) <= 0xFFFFFFFF or self.lib.generate_dithered_noise_table(C.byref(self.app.noise_table), self._dev(), res, int(seed) & 0xFFFFFFFF, int(rounds)):
+                raise RuntimeError("generate_dithered_noise_table failed")
+        elif self.lib.generate_noise_table(C.byref(self.app.noise_table), self._dev(), res, t, int(seed) & 0xFFFFFFFF):
             raise RuntimeError("generate_noise_table failed")
         return (time.perf_counter() - start) * 1.0e3
 
