@@ -379,7 +379,7 @@ int render_and_exchange_frame(application_t* app, slab_exchange_t* exchange, voi
 	   on the ray mode, the scene, the pipeline depth, and differs for the first frame of a fresh pass), so
 	   the pass itself waits for the event, on the stream it picks, before its first kernel.
 	   Round 6: not the whole frame waits but the kernel that writes what the collective of the set's previous frame reads -
-	   this rank's slot of gathered[b] (vkr_note_target_reader, shading_pass.hip). */
+	   this rank's slot of gathered[b] (vkr_note_target_reader, frame_transfers.hip). */
 	if (reused) vkr_note_target_reader(app, exchange->assembled[b], exchange->send[b], (size_t) exchange->send_bytes);
 	/* (an untimed frame leaves the set's timing events alone: they keep the last timed frame; the
 	   start mark goes to the stream the frame is expected on, which only the very first frame may miss) */

@@ -93,14 +93,14 @@ void vkr_free_refit_state(acceleration_structure_t* structure, const device_t* d
 /*! slab_assembly.hip: scatters all-gathered slabs (format: slab_format_t of vkr_slab_exchange.h)
 	into a frame on the given hipStream_t */
 int vkr_assemble_slabs_on_stream(application_t* app, const void* gathered_slabs, void* out_frame, int format, void* stream);
-/* (shading_pass.hip) `event`, a hipEvent_t, marks the end of a reader of [target, target + bytes): the next frame that
+/* (frame_transfers.hip) `event`, a hipEvent_t, marks the end of a reader of [target, target + bytes): the next frame that
    writes that range waits for it in front of the kernel that writes */
 void vkr_note_target_reader(application_t* app, void* event, const void* target, size_t bytes);
 void vkr_forget_target_reader(application_t* app, void* event);
-/* (shading_pass.hip) makes hipStream_t `stream` wait for the frames in flight, the most recent one of every frame stream
+/* (frame_transfers.hip) makes hipStream_t `stream` wait for the frames in flight, the most recent one of every frame stream
    (nothing to wait for without the frame pipeline: such frames ran on device->stream) */
 int vkr_order_behind_frames_in_flight(application_t* app, void* stream);
-/* (shading_pass.hip) for a writer of [target, target + bytes) outside the pass: makes `stream` wait for the read-backs and
+/* (frame_transfers.hip) for a writer of [target, target + bytes) outside the pass: makes `stream` wait for the read-backs and
    noted readers of that range, as a frame that writes it does */
 void vkr_order_target_write(application_t* app, const void* target, size_t bytes, void* stream);
 /* (device.c) creates the frame streams 0 ... count - 1 of the device that do not exist yet */

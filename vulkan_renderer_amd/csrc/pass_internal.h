@@ -1,7 +1,7 @@
-// What the units of the shading pass's host side share (shading_pass.hip - the frame pipeline -, render_targets.hip,
-// output_encoding.hip, slab_assembly.hip, device_probes.hip): two small helpers and the functions that one unit calls in
-// another.  Functions only: the pipeline's structs stay private to shading_pass.hip.  The library is built with
-// -fvisibility=hidden, so none of these is exported.
+// What the units of the shading pass's host side share (the frame pipeline - shading_pass.hip and the units beside it -,
+// render_targets.hip, output_encoding.hip, slab_assembly.hip, device_probes.hip): two small helpers and the functions that
+// one unit calls in another.  Functions only: the pipeline's structs stay private to its own units (frame_pipeline.h).
+// The library is built with -fvisibility=hidden, so none of these is exported.
 #pragma once
 #include "shading_kernel.h"
 #include "host/vkr_internal.h"
@@ -16,7 +16,7 @@ inline vkr::bvh_view make_bvh_view(const acceleration_structure_t* structure) {
 	return view;
 }
 
-// ---- shading_pass.hip ----
+// ---- the frame pipeline: frame_transfers.hip, shading_pass.hip (slab_tiling) ----
 // Call behind a kernel on device->stream that reads a buffer frames in flight write (the radiance
 // target, a caller's slab): the next frames wait for it before they resolve.
 void note_target_reader(application_t* app);

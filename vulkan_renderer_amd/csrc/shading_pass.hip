@@ -1,11 +1,10 @@
 // The frame pipeline behind the reference's entry points (create_shading_pass src/main.c:598, write_constants :2114,
-// the vkCmdDraw of record_render_frame_commands :1428-1434): variant selection, constant upload, frame plan, band
-// steps, read-back ordering, timing, and the diagnostics that read the pipeline's private buffers (wavefront_kernels.h and
-// light_shafts.h define non-template kernels: one unit alone may include them).  The rest of the pass: pass_internal.h.
+// the vkCmdDraw of record_render_frame_commands :1428-1434): variant selection, the wavefront buffers, frame plan, band
+// steps, and the diagnostics that replay the queued rays (wavefront_kernels.h defines non-template kernels: one unit
+// alone may include it).  The band steps with a unit of their own, and what all of them share: frame_pipeline.h.
 #include "wavefront_kernels.h"
-#include "light_shafts.h"
 #include "shade_launchers.h"
-#include "pass_internal.h"
+#include "frame_pipeline.h"
 
 using namespace vkr;
 
@@ -15,17 +14,8 @@ static const launch_function_t g_launchers[6][5] = {
 	VKR_LAUNCHER_ROW(libm), VKR_LAUNCHER_ROW(fast), VKR_LAUNCHER_ROW(exact),
 	VKR_LAUNCHER_ROW(textured_libm), VKR_LAUNCHER_ROW(textured_fast), VKR_LAUNCHER_ROW(textured_exact),
 };
-// [arithmetic_mode_t][strategy - kStrategySeparately]: the kernels with kept prepared polygons; none in the fast mode
-#define VKR_PREPARED_ROW(mode) {vkr_launch_shade_prepared_##mode##_2, vkr_launch_shade_prepared_##mode##_3, vkr_launch_shade_prepared_##mode##_4}
-static const prepared_launch_function_t g_prepared_launchers[3][3] = {VKR_PREPARED_ROW(libm), {NULL, NULL, NULL}, VKR_PREPARED_ROW(exact)};
-static const sector_terms_launch_function_t g_sector_terms_launchers[3] = {vkr_launch_sector_terms_libm, NULL, vkr_launch_sector_terms_exact};
 static const error_launch_function_t g_error_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_error_display);
 static const resolve_launch_function_t g_resolve_launchers[3] = VKR_MODE_LAUNCHERS(vkr_launch_resolve_materials);
-
-// Events that order streams of one device: a device-scope release is all they need.  The default
-// (system-scope fence: L2 write-back and invalidation at every record) is paid by whatever runs
-// next on the device, and a frame records several.
-constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
 
 // The strategies that prepare a specular technique besides the diffuse one (the combined diffuse + specular path), and the
 // out-of-range strategies, which select the same preparation (validate_settings)
@@ -57,164 +47,15 @@ static int technique_index(const render_settings_t* settings) {
 // the projected solid angle techniques: the only ones with an error display and with LTC importance sampling beside them
 static bool is_projected_solid_angle(int technique) { return technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniquePsaArvo; }
 
-// the techniques whose samples aim at the light polygon itself: every shadow ray lies inside the light's shaft
-static bool aims_at_light_polygon(int technique) {
-	return technique == kTechniquePsa || technique == kTechniquePsaBiased || technique == kTechniqueSolidAngle || technique == kTechniqueClippedSolidAngle;
-}
-
 // ---- shading pass ----------------------------------------------------------------
-
-// events of a timed frame: its start, the start and the end of the (last band's) shading kernel, its end
-constexpr uint32_t kTimingFrameStart = 0, kTimingShadingStart = 1, kTimingShadingEnd = 2, kTimingFrameEnd = 3, kTimingEvents = 4;
-
-static hipEvent_t timing_event(const shading_pass_t* pass, uint32_t slot, uint32_t which) { return ((hipEvent_t*) pass->timing_ring)[kTimingEvents * slot + which]; }
-
-// Buffers of the wavefront ray path, sized for the worst case (every sample of every
-// light on every pixel produces a term and a ray) and owned by the pass.
-struct wavefront_buffers {
-	uint8_t* codes;
-	float* terms_visible;
-	float* terms_hidden;
-	float4* base_color;
-	float4* ray_directions;
-	uint32_t* ray_records;
-	float4* ray_origins;
-	uint32_t* ray_queue_size;  // kRayCounterCount live counters (queue sizes, per-XCD work cursors), then last frame's copy
-	uint32_t thread_count, max_terms, max_codes, queue_capacity, thread_bits;
-	// the streams that only some settings need are allocated when they first do: values of blocked
-	// terms (only the plain optimal MIS heuristic has non-zero ones), colour before the sampled terms
-	// (only the light display has one); their element counts, 0 while they do not exist
-	size_t hidden_term_count, base_color_count;
-	// stack entries beyond the LDS part of trace_shadow_rays_wide, [entry][thread of the trace grid];
-	// allocated only for trees that can need them
-	uint32_t* spill;
-	size_t spill_entries;
-	// light shafts (light_shafts.h): one word per shading workgroup and light, 1 = no ray of that patch toward that
-	// light can be blocked; allocated when the feature first runs
-	uint32_t* shaft_clear;
-	// what the verdicts in shaft_clear (and the lists in shaft_lists) were derived from: a byte image of the inputs of the
-	// most recent launch with these buffers (shaft_arrangement below), shaft_seen_size bytes of it; 0: the tables hold nothing
-	// to lean on.  The shaft kernel keeps a verdict only while these bytes are the next launch's, too.
-	uint8_t* shaft_seen;
-	size_t shaft_seen_size, shaft_seen_capacity;
-	size_t shaft_words;
-	// ... and per light the plane-space rectangle that the shading kernel tests its rays against
-	float4* shaft_rectangles;
-	size_t shaft_rectangle_count;
-	// ... and per pair kShaftListMax triangle slots: the occluder lists (VKR_SHAFT_LISTS)
-	float* shaft_lists;
-	size_t shaft_list_words;
-	// the second polygon table of every shading workgroup, for the kernel variants that keep one table in LDS only
-	// (shading_kernel.h psa_table_in_memory); allocated when such a variant first runs
-	float2* psa_table_memory;
-	size_t psa_table_bytes;
-};
 
 static void free_wavefront_buffers(wavefront_buffers* w) {
 	(void) hipFree(w->codes); (void) hipFree(w->terms_visible); (void) hipFree(w->terms_hidden);
 	(void) hipFree(w->base_color); (void) hipFree(w->ray_directions); (void) hipFree(w->ray_records); (void) hipFree(w->ray_origins); (void) hipFree(w->ray_queue_size);
 	(void) hipFree(w->spill);
-	(void) hipFree(w->shaft_clear);
-	(void) hipFree(w->shaft_rectangles);
-	(void) hipFree(w->shaft_lists);
-	free(w->shaft_seen);
+	destroy_light_shafts(w);
 	(void) hipFree(w->psa_table_memory);
 	memset(w, 0, sizeof(*w));
-}
-
-// The prepared polygons of the most recent launches (shading_kernel.h "Prepared polygons that are still true")
-enum { kCacheEmpty = 0, kCachePending = 1, kCacheValid = 2 };
-struct prepared_cache {
-	uint4* buffer;  // the second argument of the storing and the loading kernel, allocated when a launch first stores
-	size_t buffer_quads;
-	// the sector terms of the polygons in `buffer` (shading_kernel.h "Sector terms that are still true"): the third argument of
-	// the kernel that loads with terms, allocated, retained and released by the rules of `buffer`, and filled behind the storing
-	// launch, in front of `stored`.  terms_quads: its size, 0: the launches of this arrangement load without terms
-	float4* terms;
-	size_t terms_quads;
-	// a byte image of everything the preparation reads (prepared_arrangement below), of the most recent launch that the
-	// cache could serve: seen_size bytes, 0: none
-	uint8_t* seen;
-	size_t seen_size, seen_capacity;
-	uint8_t* scratch;
-	size_t scratch_capacity;
-	// kCachePending: a storing launch with the inputs in `seen` has been submitted and `stored` recorded behind it;
-	// kCacheValid: that event has been seen complete - launches with these inputs load
-	uint32_t state;
-	hipEvent_t stored;
-	hipStream_t stored_stream;  // the stream of that storing launch
-	// VKR_PREPARED_POLYGONS_MIB: the largest buffer that is allocated (0: no launch stores or loads)
-	uint32_t budget_mib;
-	// for get_prepared_polygon_statistics(): the mode of the last launch, launches per mode, launches that ran plain because
-	// the storing launch had not completed yet
-	uint32_t last_mode;
-	uint64_t launches[3], waited;
-	// VKR_SECTOR_TERMS=0: no terms are kept; for get_sector_terms_statistics(): loading launches with and without terms
-	uint32_t terms_enabled;
-	uint64_t loaded_with_terms, loaded_without_terms;
-};
-
-// What a frame in flight owns.  With frames_in_flight = n >= 2 consecutive frames take turns
-// on n contexts (and n of the device's frame streams); otherwise only context 0 is used, on
-// device->stream.
-struct frame_context {
-	wavefront_buffers buffers;
-	hipEvent_t done;  // recorded behind the last kernel of the frame
-	bool recorded;    // `done` has been recorded: the next frame's resolve is ordered behind it
-	// what the context's most recent launches wrote their output to (a ring of the last eight): a launch only has to be ordered
-	// behind another one when they write the same buffer (frames of a slab exchange take turns on several slabs, round 6); the
-	// context's `done` event lies behind all of them
-	const void* targets[8];
-	uint32_t target_cursor;
-	bool pending;     // device->stream has not been made to wait for `done` yet
-	uint32_t readers_seen;  // frame_pipeline::readers_generation this context's stream has waited for
-};
-struct frame_pipeline {
-	frame_context contexts[VKR_MAX_FRAMES_IN_FLIGHT];
-	hipEvent_t inputs_ready;  // marks what device->stream had submitted when a frame started
-	// Recorded on device->stream behind every kernel there that reads a target of the frames
-	// (output encoding of the frame or of a slab): a later frame in flight must not resolve into
-	// that target before the reader is done.  (finish_frames() orders device->stream behind the
-	// frames; this is the opposite direction.)
-	hipEvent_t readers_done;
-	uint32_t readers_generation;
-	// bumped whenever an input that the frames read from device memory has been rewritten (visibility buffer, scene):
-	// part of what the light shafts' verdicts are derived from (shaft_arrangement)
-	uint32_t inputs_generation;
-	// where run_light_shafts() puts the inputs of a launch together before it compares them with the context's copy
-	uint8_t* shaft_scratch;
-	size_t shaft_scratch_capacity;
-	// the polygon tables in device memory (wavefront_buffers::psa_table_memory) of the frames without wavefront rays, which
-	// own no context
-	wavefront_buffers device_stream_buffers;
-	// the prepared polygons that the shading kernel keeps while its inputs stand still ("prepared polygon cache" below): one
-	// per pass, not per frame context - it is read-only while it is valid
-	prepared_cache prepared;
-	uint32_t next;            // context of the next pipelined frame
-	uint32_t last;            // context of the most recent frame
-	uint32_t depth;           // frames in flight of the most recent pipelined frame
-	// tuning / test knobs, read from the environment once when the pipeline is created:
-	// VKR_WIDE_STACK_LDS (stack entries per lane that trace_shadow_rays_wide keeps in LDS: tests shrink
-	// it to drive rays through the spill path)
-	// VKR_WAVEFRONT_BUDGET_MIB: most device memory that all sets of wavefront buffers in flight may take
-	// (default 36864 - config 4 then runs as three bands of 12 GB, the fastest of 1 ... 12 bands, profiles/r04c/: a
-	// frame whose worst case needs more is rendered in bands); VKR_BAND_COUNT forces
-	// the number of bands per frame (0: automatic)
-	// VKR_LIGHT_SHAFTS: 0 turns the shaft test off (every shadow ray is traced, as until round 3), 1 on; default 2:
-	// on when a pixel may queue 8 rays or more (samples x techniques x lights) - the walk of a patch costs about as
-	// much as tracing 2.5 rays per pixel and light, and it is the patches with many rays per light and several lights
-	// that repay it (measured, profiles/r05m: config 3, 32 rays per pixel, 1.553 -> 1.443 ms; config 4, 128, 25.9 -> 23.0;
-	// the target shape, 8, 0.488 -> 0.500 before the occluder lists and 0.501 -> 0.443 with them, which is what moved
-	// the rule from 16 to 8; config 2, 2 rays per pixel, 0.127 -> 0.192)
-	// VKR_SHAFT_REST, VKR_SHAFT_MAX_STEPS, VKR_WIDE_REFILL, VKR_WIDE_REFILL_BELOW (round 5): ensure_frames()
-	uint32_t wide_stack_lds, wide_refill, wide_refill_below, wavefront_budget_mib, band_count, light_shafts, shaft_lists, shaft_rest, shaft_max_steps;
-};
-
-static uint32_t environment_knob(const char* name, uint32_t fallback, uint32_t low, uint32_t high) {
-	const char* text = getenv(name);
-	if (!text || !text[0]) return fallback;
-	long value = strtol(text, NULL, 10);
-	return (uint32_t) (value < (long) low ? (long) low : (value > (long) high ? (long) high : value));
 }
 
 static void destroy_wavefront(shading_pass_t* pass) {
@@ -227,12 +68,8 @@ static void destroy_wavefront(shading_pass_t* pass) {
 	free_wavefront_buffers(&frames->device_stream_buffers);
 	if (frames->inputs_ready) (void) hipEventDestroy(frames->inputs_ready);
 	if (frames->readers_done) (void) hipEventDestroy(frames->readers_done);
-	free(frames->shaft_scratch);
-	(void) hipFree(frames->prepared.buffer);
-	(void) hipFree(frames->prepared.terms);
-	if (frames->prepared.stored) (void) hipEventDestroy(frames->prepared.stored);
-	free(frames->prepared.seen);
-	free(frames->prepared.scratch);
+	free(frames->scratch.bytes);
+	destroy_prepared_polygons(frames);
 	free(frames);
 	pass->wavefront = NULL;
 }
@@ -244,7 +81,7 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 	pass->wavefront = frames;
 	bool failed = !frames || hipEventCreateWithFlags(&frames->inputs_ready, kSyncEventFlags) != hipSuccess
 		|| hipEventCreateWithFlags(&frames->readers_done, kSyncEventFlags) != hipSuccess
-		|| hipEventCreateWithFlags(&frames->prepared.stored, kSyncEventFlags) != hipSuccess;
+		|| create_prepared_polygons(frames);
 	for (int i = 0; i != VKR_MAX_FRAMES_IN_FLIGHT && !failed; ++i) failed = hipEventCreateWithFlags(&frames->contexts[i].done, kSyncEventFlags) != hipSuccess;
 	if (failed) {
 		printf("Failed to create the events of the frame pipeline.\n");
@@ -252,16 +89,7 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 		return NULL;
 	}
 	frames->wide_stack_lds = environment_knob("VKR_WIDE_STACK_LDS", kWideStackLds, 4u, kWideStackLds);
-	frames->light_shafts = environment_knob("VKR_LIGHT_SHAFTS", 2u, 0u, 2u);
-	// VKR_SHAFT_LISTS=0: a shaft walk ends at the first triangle in the way (no occluder lists, light_shafts.h)
-	frames->shaft_lists = environment_knob("VKR_SHAFT_LISTS", 1u, 0u, 1u);
-	// VKR_SHAFT_REST: frames (of a frame context) for which a pair is not walked again after a walk that met more triangles
-	// than a list holds; 0: every pair is walked in every frame (light_shafts.h, kShaftResting)
-	frames->shaft_rest = environment_knob("VKR_SHAFT_REST", kShaftRestFrames, 0u, 200u);
-	// VKR_SHAFT_MAX_STEPS: steps after which a walk gives up (plus a fifth of it per light that is walked along).  The shaft
-	// kernel of a small launch - a rank's slab at N = 8 - lasts as long as its longest walk.
-	// (0: by the size of the launch - kShaftMaxSteps, or kShaftSmallLaunchSteps below 12 288 shading waves)
-	frames->shaft_max_steps = environment_knob("VKR_SHAFT_MAX_STEPS", 0u, 0u, 1000u);
+	create_light_shafts(frames);
 	// VKR_WIDE_REFILL: lanes of a tracing wave (four-wide tree) that have to be idle before they are handed the next rays,
 	// once the wave has found its batches less than VKR_WIDE_REFILL_BELOW / 256 busy (wavefront_kernels.h; 256: from the
 	// first batch on); 0: a batch of 64 rays is always walked to its end first (until round 4)
@@ -269,12 +97,6 @@ static frame_pipeline* ensure_frames(shading_pass_t* pass) {
 	frames->wide_refill_below = environment_knob("VKR_WIDE_REFILL_BELOW", kWideRefillBelow, 0u, 256u);
 	frames->wavefront_budget_mib = environment_knob("VKR_WAVEFRONT_BUDGET_MIB", 36864u, 64u, 262144u);
 	frames->band_count = environment_knob("VKR_BAND_COUNT", 0u, 0u, 4096u);
-	// VKR_PREPARED_POLYGONS_MIB: most device memory that the kept prepared polygons of a launch may take; 0: nothing is kept,
-	// every launch prepares its polygons itself.  (Config 3 at 1920x1080 keeps 2 040 MiB: 2.09 M threads x 4 lights x 256 B.)
-	// (with the sector terms of those polygons - as much again at V = 5 - where both fit: 4 080 MiB)
-	frames->prepared.budget_mib = environment_knob("VKR_PREPARED_POLYGONS_MIB", 4096u, 0u, 262144u);
-	// VKR_SECTOR_TERMS=0: the loading launches compute the terms of their sectors themselves
-	frames->prepared.terms_enabled = environment_knob("VKR_SECTOR_TERMS", 1u, 0u, 1u);
 	return frames;
 }
 
@@ -287,49 +109,6 @@ static uint32_t ray_block_size(uint32_t max_terms) { return max_terms >= 8 ? 256
 // (trace_shadow_rays_wide), and the refill threshold of the binary walk (trace_shadow_rays)
 constexpr uint32_t kLeafBatch = 16;
 constexpr uint32_t kRefillThreshold = 0;
-
-// host memory that grows on demand and keeps its content
-static int grow_bytes(uint8_t** buffer, size_t* capacity, size_t size) {
-	if (*capacity >= size) return 0;
-	uint8_t* grown = (uint8_t*) realloc(*buffer, size);
-	if (!grown) return 1;
-	*buffer = grown;
-	*capacity = size;
-	return 0;
-}
-
-// The same for a device buffer of `count` elements, whose content is not kept: a buffer that is too small is freed
-// (while other frames may be in flight: hipFree waits for the device) and allocated anew.  On failure pointer and count
-// are zero and `message` is printed, a format for the MiB that were asked for.
-template <typename T>
-static int grow_device_buffer(T** buffer, size_t* count, size_t wanted, size_t element_bytes, const char* message) {
-	if (wanted <= *count) return 0;
-	(void) hipFree(*buffer);
-	*buffer = NULL; *count = 0;
-	if (hipMalloc(buffer, wanted * element_bytes) != hipSuccess) {
-		printf(message, wanted * element_bytes / 1048576.0);
-		return 1;
-	}
-	*count = wanted;
-	return 0;
-}
-
-static int ensure_shaft_words(wavefront_buffers* w, size_t words, uint32_t light_count, bool lists, hipStream_t stream) {
-	size_t list_words = lists ? words * kShaftListMax * kShaftListEntry : 0;
-	const bool fresh_words = words > w->shaft_words;
-	// (the tables carry state from frame to frame: whichever of them is allocated anew, the copy of the inputs is forgotten)
-	if (list_words > w->shaft_list_words || light_count > w->shaft_rectangle_count || fresh_words) w->shaft_seen_size = 0;
-	if (grow_device_buffer(&w->shaft_lists, &w->shaft_list_words, list_words, sizeof(float), "Failed to allocate %.1f MiB for the occluder lists of the light shafts.\n")
-		|| grow_device_buffer(&w->shaft_rectangles, &w->shaft_rectangle_count, light_count, sizeof(float4), "Failed to allocate the rectangles of the light shafts.\n")
-		|| grow_device_buffer(&w->shaft_clear, &w->shaft_words, words, sizeof(uint32_t), "Failed to allocate %.1f MiB for the light shafts.\n"))
-		return 1;
-	// (the shaft kernel reads the verdicts of the frame before: none yet)
-	if (fresh_words && hipMemsetAsync(w->shaft_clear, 0, words * sizeof(uint32_t), stream) != hipSuccess) {
-		w->shaft_words = 0;
-		return 1;
-	}
-	return 0;
-}
 
 static int ensure_spill(wavefront_buffers* w, uint32_t stack_need, uint32_t in_lds, uint32_t trace_threads) {
 	size_t entries = stack_need > in_lds ? (size_t) (stack_need - in_lds) * trace_threads : 0;
@@ -423,289 +202,6 @@ extern "C" int finish_frames(application_t* app) {
 			c.pending = false;
 		}
 	return failed;
-}
-
-void note_target_reader(application_t* app) {
-	frame_pipeline* frames = (frame_pipeline*) app->shading_pass.wavefront;
-	if (!frames || !app->shading_pass.last_frame_in_flight) return;
-	if (hipEventRecord(frames->readers_done, (hipStream_t) app->device.stream) == hipSuccess) ++frames->readers_generation;
-}
-
-// The constant buffer is a small ring: the host may record several frames ahead, so
-// every set of constants in flight needs its own staging and device copy (the reference
-// keeps one uniform buffer per swapchain image for the same reason, main.c:330-360).
-// A frame whose constants are byte-identical to the previous frame's reuses the slot
-// that is already on the device (static camera and lights: no upload at all, like the
-// reference's host-coherent uniform buffer, which costs no GPU time either).
-constexpr uint32_t kConstantSlots = VKR_MAX_FRAMES_IN_FLIGHT + 2;
-// (device->stream and the frame streams)
-constexpr int kConstantReaders = 1 + VKR_MAX_FRAMES_IN_FLIGHT;
-struct constants_ring {
-	void* host[kConstantSlots];
-	void* device[kConstantSlots];
-	// a slot may be read from device->stream and from the frame streams
-	hipEvent_t consumed[kConstantSlots][kConstantReaders];
-	hipEvent_t uploaded[kConstantSlots];
-	// bit i: readers[i] (device->stream, then the frame streams) is ordered behind the upload
-	uint32_t ordered[kConstantSlots];
-	bool in_flight[kConstantSlots];
-	void* scratch;    // write_constants target before it is known whether anything changed
-	uint32_t current; // slot whose device copy the next launch reads
-	bool valid;       // false until the first upload
-};
-
-static void destroy_constants_ring(shading_pass_t* pass, const device_t* device) {
-	constants_ring* ring = (constants_ring*) pass->constants_ring;
-	if (!ring) return;
-	for (uint32_t i = 0; i != kConstantSlots; ++i) {
-		vkr_device_free(ring->device[i], device);
-		vkr_host_free_pinned(ring->host[i]);
-		for (hipEvent_t event : ring->consumed[i]) if (event) (void) hipEventDestroy(event);
-		if (ring->uploaded[i]) (void) hipEventDestroy(ring->uploaded[i]);
-	}
-	free(ring->scratch);
-	free(ring);
-	pass->constants_ring = NULL;
-	pass->constants_device = pass->constants_host = NULL;
-}
-
-static int create_constants_ring(shading_pass_t* pass, const device_t* device) {
-	constants_ring* ring = (constants_ring*) calloc(1, sizeof(constants_ring));
-	pass->constants_ring = ring;
-	if (!ring) return 1;
-	ring->scratch = calloc(1, pass->constants_size);
-	if (!ring->scratch) return 1;
-	for (uint32_t i = 0; i != kConstantSlots; ++i) {
-		if (vkr_device_alloc(&ring->device[i], device, pass->constants_size, "the constant buffer")
-			|| vkr_host_alloc_pinned(&ring->host[i], pass->constants_size)
-			|| hip_failed(hipEventCreateWithFlags(&ring->uploaded[i], kSyncEventFlags), "creating upload events"))
-			return 1;
-		for (hipEvent_t& event : ring->consumed[i])
-			if (hip_failed(hipEventCreateWithFlags(&event, kSyncEventFlags), "creating upload events")) return 1;
-		memset(ring->host[i], 0, pass->constants_size);
-	}
-	pass->constants_device = ring->device[0];
-	pass->constants_host = ring->host[0];
-	return 0;
-}
-
-int upload_constants(application_t* app, hipStream_t stream) {
-	shading_pass_t* pass = &app->shading_pass;
-	constants_ring* ring = (constants_ring*) pass->constants_ring;
-	// a frame stream that does not exist yet is marked by `present`: a NULL stream is a stream too
-	hipStream_t readers[kConstantReaders] = {(hipStream_t) app->device.stream};
-	bool present[kConstantReaders] = {true};
-	for (int i = 0; i != VKR_MAX_FRAMES_IN_FLIGHT; ++i) {
-		readers[1 + i] = (hipStream_t) app->device.frame_streams[i];
-		present[1 + i] = app->device.frame_streams[i] != NULL;
-	}
-	write_constants(ring->scratch, app);
-	if (!ring->valid || memcmp(ring->scratch, ring->host[ring->current], pass->constants_size) != 0) {
-		uint32_t slot = ring->valid ? (ring->current + 1) % kConstantSlots : 0;
-		// everything launched so far may read the old slot: it is free again once all
-		// streams have passed this point
-		if (ring->valid) {
-			// (an absent reader's event stays unrecorded, which completes at once)
-			for (int i = 0; i != kConstantReaders; ++i) if (present[i]) (void) hipEventRecord(ring->consumed[ring->current][i], readers[i]);
-			ring->in_flight[ring->current] = true;
-		}
-		if (ring->in_flight[slot])
-			for (int i = 0; i != kConstantReaders; ++i)
-				if (hip_failed(hipEventSynchronize(ring->consumed[slot][i]), "waiting for a free constant buffer")) return 1;
-		ring->in_flight[slot] = false;
-		memcpy(ring->host[slot], ring->scratch, pass->constants_size);
-		if (hip_failed(hipMemcpyAsync(ring->device[slot], ring->host[slot], pass->constants_size, hipMemcpyHostToDevice, stream), "uploading the constants")
-			|| hip_failed(hipEventRecord(ring->uploaded[slot], stream), "recording the upload"))
-			return 1;
-		ring->ordered[slot] = 0;
-		for (int i = 0; i != kConstantReaders; ++i) if (present[i] && readers[i] == stream) ring->ordered[slot] |= 1u << i;
-		ring->current = slot;
-		ring->valid = true;
-		pass->constants_device = ring->device[slot];
-		pass->constants_host = ring->host[slot];
-		return 0;
-	}
-	// unchanged constants that another stream uploaded: order this stream behind that upload
-	for (int i = 0; i != kConstantReaders; ++i)
-		if (present[i] && readers[i] == stream) {
-			if (ring->ordered[ring->current] & (1u << i)) return 0;
-			ring->ordered[ring->current] |= 1u << i;
-		}
-	return hip_failed(hipStreamWaitEvent(stream, ring->uploaded[ring->current], 0), "waiting for the constants");
-}
-
-// ---- asynchronous read-back through pinned staging (include/vkr_shading_pass.h begin_read_back) ----------------
-// One staging buffer, one event and the device address it was filled from per slot; all copies run on one stream of their
-// own (device-to-host copies into pinned memory are served by a DMA engine: they take no compute unit from the frames).
-constexpr uint32_t kReadBackSlots = VKR_MAX_FRAMES_IN_FLIGHT + 1;
-struct read_back_state {
-	hipStream_t stream;
-	hipEvent_t source_ready;               // marks device->stream when a copy is queued
-	void* staging[kReadBackSlots];
-	size_t staging_size[kReadBackSlots];
-	hipEvent_t copied[kReadBackSlots];
-	const void* source[kReadBackSlots];    // device range [source, source + bytes) of the slot's most recent copy
-	size_t bytes[kReadBackSlots];
-	bool pending[kReadBackSlots];          // the copy may still be running: a writer of its source waits for `copied`
-	// readers outside the pass (vkr_note_target_reader: the slab exchange's collectives): an event of the caller and the
-	// device range that is read until it completes
-	hipEvent_t reader_event[kReadBackSlots];
-	const void* reader_source[kReadBackSlots];
-	size_t reader_bytes[kReadBackSlots];
-};
-
-// ... and before the caller destroys such an event
-extern "C" void vkr_forget_target_reader(application_t* app, void* event) {
-	read_back_state* rb = (read_back_state*) app->shading_pass.readback;
-	if (!rb || !event) return;
-	for (uint32_t i = 0; i != kReadBackSlots; ++i)
-		if (rb->reader_event[i] == (hipEvent_t) event) rb->reader_event[i] = NULL;
-	if (app->shading_pass.wait_before_next_frame == event) app->shading_pass.wait_before_next_frame = NULL;
-}
-
-static read_back_state* ensure_read_back_state(shading_pass_t* pass) {
-	if (!pass->readback) pass->readback = calloc(1, sizeof(read_back_state));
-	return (read_back_state*) pass->readback;
-}
-
-// For host/slab_exchange.c: `event` (a hipEvent_t of the caller, recorded behind a reader of [target, target + bytes)) must
-// have completed before a later frame writes that range.  The frame that writes it waits on the device, in front of the
-// kernel that does the writing - the resolve kernel of a frame with wavefront rays, the shading kernel otherwise, the
-// encoding kernel for an encoded slab - and not in front of its first kernel, as shading_pass_t.wait_before_next_frame
-// makes it: shaft walks, shading and tracing of frame k + n overlap the collective of frame k (round 6: a rank's slab at
-// N = 8 took 0.220 instead of 0.176 ms through the exchange with a collective that did nothing,
-// profiles/r10c/exchange_overhead_before.jsonl).  One entry per range; a new event for a known range replaces the old one.
-extern "C" void vkr_note_target_reader(application_t* app, void* event, const void* target, size_t bytes) {
-	read_back_state* rb = ensure_read_back_state(&app->shading_pass);
-	if (!rb) return;
-	uint32_t slot = kReadBackSlots;
-	for (uint32_t i = 0; i != kReadBackSlots; ++i) {
-		if (rb->reader_event[i] && rb->reader_source[i] == target) { slot = i; break; }
-		if (!rb->reader_event[i] && slot == kReadBackSlots) slot = i;
-	}
-	if (slot == kReadBackSlots) {
-		// (more ranges than buffer sets can exist: fall back to the oldest rule - the whole next frame waits)
-		app->shading_pass.wait_before_next_frame = event;
-		return;
-	}
-	rb->reader_event[slot] = (hipEvent_t) event;
-	rb->reader_source[slot] = target;
-	rb->reader_bytes[slot] = bytes;
-}
-
-static void destroy_read_back(shading_pass_t* pass) {
-	read_back_state* rb = (read_back_state*) pass->readback;
-	if (!rb) return;
-	if (rb->stream) { (void) hipStreamSynchronize(rb->stream); (void) hipStreamDestroy(rb->stream); }
-	if (rb->source_ready) (void) hipEventDestroy(rb->source_ready);
-	for (uint32_t i = 0; i != kReadBackSlots; ++i) {
-		if (rb->copied[i]) (void) hipEventDestroy(rb->copied[i]);
-		vkr_host_free_pinned(rb->staging[i]);
-	}
-	free(rb);
-	pass->readback = NULL;
-}
-
-// Makes `stream` wait for every pending copy that reads from [target, target + bytes): called in front of the kernel
-// of a frame that writes its output (the resolve kernel with wavefront rays, the shading kernel otherwise)
-static void wait_for_read_backs_of(shading_pass_t* pass, const void* target, size_t bytes, hipStream_t stream) {
-	read_back_state* rb = (read_back_state*) pass->readback;
-	if (!rb) return;
-	for (uint32_t i = 0; i != kReadBackSlots; ++i) {
-		if (!rb->reader_event[i]) continue;
-		const uint8_t* a = (const uint8_t*) rb->reader_source[i];
-		const uint8_t* b = (const uint8_t*) target;
-		if (!(a < b + bytes && b < a + rb->reader_bytes[i])) continue;
-		if (hipEventQuery(rb->reader_event[i]) == hipSuccess) { rb->reader_event[i] = NULL; continue; }
-		(void) hipStreamWaitEvent(stream, rb->reader_event[i], 0);
-	}
-	for (uint32_t i = 0; i != kReadBackSlots; ++i) {
-		if (!rb->pending[i]) continue;
-		if (hipEventQuery(rb->copied[i]) == hipSuccess) { rb->pending[i] = false; continue; }
-		const uint8_t* a = (const uint8_t*) rb->source[i];
-		const uint8_t* b = (const uint8_t*) target;
-		if (a < b + bytes && b < a + rb->bytes[i]) (void) hipStreamWaitEvent(stream, rb->copied[i], 0);
-	}
-}
-
-// For csrc/frame_statistics.hip, whose kernels read and write targets on streams of their own
-extern "C" void vkr_order_target_write(application_t* app, const void* target, size_t bytes, void* stream) {
-	wait_for_read_backs_of(&app->shading_pass, target, bytes, (hipStream_t) stream);
-}
-
-// Makes `stream` wait for the frames in flight: the most recent frame of every context (earlier frames of a context precede
-// it on the context's stream).  begin_read_back() waits for the most recent frame only, which covers the one buffer that
-// frame wrote; a reader of several frames' targets - an accumulation of a ring - needs them all, and frames that wrote
-// different targets do not wait for each other.
-extern "C" int vkr_order_behind_frames_in_flight(application_t* app, void* stream) {
-	frame_pipeline* frames = (frame_pipeline*) app->shading_pass.wavefront;
-	if (!frames || !app->shading_pass.last_frame_in_flight) return 0;
-	for (frame_context& c : frames->contexts)
-		if (c.recorded && hip_failed(hipStreamWaitEvent((hipStream_t) stream, c.done, 0), "ordering a reader behind the frames in flight")) return 1;
-	return 0;
-}
-
-extern "C" int begin_read_back(application_t* app, uint32_t slot, const void* device_source, uint64_t bytes) {
-	shading_pass_t* pass = &app->shading_pass;
-	if (slot >= kReadBackSlots) {
-		printf("begin_read_back(): slot %u does not exist (0 ... %u).\n", slot, kReadBackSlots - 1u);
-		return 1;
-	}
-	if (!device_source) {
-		device_source = app->render_targets.radiance;
-		bytes = sizeof(float) * 4 * (uint64_t) app->swapchain.extent.width * app->swapchain.extent.height;
-	}
-	if (!device_source || !bytes) {
-		printf("begin_read_back() needs a device buffer (or render targets) to read from.\n");
-		return 1;
-	}
-	read_back_state* rb = ensure_read_back_state(pass);
-	if (!rb) return 1;
-	if (!rb->stream && (hip_failed(hipStreamCreateWithFlags(&rb->stream, hipStreamNonBlocking), "creating the read-back stream")
-		|| hip_failed(hipEventCreateWithFlags(&rb->source_ready, kSyncEventFlags), "creating read-back events")))
-		return 1;
-	// (the host waits for this one: no device-scope-only release)
-	if (!rb->copied[slot] && hip_failed(hipEventCreateWithFlags(&rb->copied[slot], hipEventDisableTiming), "creating read-back events")) return 1;
-	// (the slot's previous copy has to have landed before its staging memory is reused or freed)
-	if (rb->pending[slot] && hip_failed(hipEventSynchronize(rb->copied[slot]), "waiting for the slot's previous read-back")) return 1;
-	rb->pending[slot] = false;
-	if (rb->staging_size[slot] < bytes) {
-		vkr_host_free_pinned(rb->staging[slot]);
-		rb->staging[slot] = NULL; rb->staging_size[slot] = 0;
-		if (vkr_host_alloc_pinned(&rb->staging[slot], (size_t) bytes)) {
-			printf("Failed to allocate %.1f MiB of pinned host memory for read-backs.\n", bytes / 1048576.0);
-			return 1;
-		}
-		rb->staging_size[slot] = (size_t) bytes;
-	}
-	// behind the most recent frame in flight (only that one: its resolves wait for earlier frames that wrote the same target,
-	// not for those that wrote another one, which may still be running) ...
-	frame_pipeline* frames = (frame_pipeline*) pass->wavefront;
-	if (frames && pass->last_frame_in_flight) {
-		frame_context* last = &frames->contexts[frames->last];
-		if (last->recorded && hip_failed(hipStreamWaitEvent(rb->stream, last->done, 0), "ordering the read-back behind the frame")) return 1;
-	}
-	// ... and behind what device->stream has queued (frames without the pipeline, output encoding, an assembled frame)
-	if (hip_failed(hipEventRecord(rb->source_ready, (hipStream_t) app->device.stream), "marking the source")
-		|| hip_failed(hipStreamWaitEvent(rb->stream, rb->source_ready, 0), "ordering the read-back behind the device stream")
-		|| hip_failed(hipMemcpyAsync(rb->staging[slot], device_source, (size_t) bytes, hipMemcpyDeviceToHost, rb->stream), "queueing the read-back")
-		|| hip_failed(hipEventRecord(rb->copied[slot], rb->stream), "marking the read-back"))
-		return 1;
-	rb->source[slot] = device_source;
-	rb->bytes[slot] = (size_t) bytes;
-	rb->pending[slot] = true;
-	return 0;
-}
-
-extern "C" const void* end_read_back(application_t* app, uint32_t slot) {
-	read_back_state* rb = (read_back_state*) app->shading_pass.readback;
-	if (!rb || slot >= kReadBackSlots || !rb->staging[slot] || !rb->copied[slot]) {
-		printf("end_read_back(): slot %u has no read-back in flight.\n", slot);
-		return NULL;
-	}
-	if (hip_failed(hipEventSynchronize(rb->copied[slot]), "waiting for the read-back")) return NULL;
-	rb->pending[slot] = false;
-	return rb->staging[slot];
 }
 
 extern "C" void destroy_shading_pass(shading_pass_t* pass, const device_t* device) {
@@ -870,31 +366,6 @@ uint64_t slab_tiling(const application_t* app, uint32_t rank, shade_params& p) {
 	return (uint64_t) grid_blocks * 256;
 }
 
-// What render_pass() decides about a frame before its first band (plan_frame, plan_bands); the band steps read it
-struct frame_plan {
-	shade_params p;          // the parameters of every launch of the frame; a band step adds the band's blocks and buffers
-	frame_pipeline* frames;  // NULL for a frame without wavefront rays, unless its polygon tables live in device memory
-	int strategy, technique, capacity, error_mode, ray_mode;
-	// how the launch gets its prepared polygons (kPreparedPlain / kPreparedStoring / kPreparedLoading, choose_prepared_mode()) and
-	// the buffer of the other two than plain
-	int prepared_mode;
-	uint4* prepared;
-	// quads (16 B) of the buffer that the prepared polygons of the frame's one launch may take: plan_bands() has found room for
-	// them in the budgets; 0: this frame keeps none
-	size_t prepared_quads;
-	// ... and the sector terms of those polygons: the buffer of the kernel that loads with terms, and its quads - 0: the budgets
-	// hold the polygons alone (or VKR_SECTOR_TERMS=0), and the launches load without terms
-	const float4* terms;
-	size_t terms_quads;
-	// (table_in_memory: the kernel variants that keep one of their two polygon tables in device memory, shading_kernel.h psa_table_in_memory)
-	bool table_in_memory, hidden_terms, base_color, use_wide_tree, textured, pipelined;
-	uint32_t grid_blocks, table_bytes_per_workgroup, max_terms;
-	// frames in flight (1: not pipelined), the bands of the frame, workgroups of the tracing kernels (wavefront rays only)
-	uint32_t depth, band_count, blocks_per_band, trace_blocks;
-	// bytes of the output this call writes (a slab in slab layout, else the frame): what pending read-backs are checked against
-	size_t frame_output_bytes;
-};
-
 // the parameters of a frame that come straight from the application
 static void fill_frame_inputs(const application_t* app, void* out_radiance, shade_params& p) {
 	memset(&p, 0, sizeof(p));
@@ -1006,15 +477,6 @@ static int plan_frame(application_t* app, void* out_radiance, frame_plan* f) {
 	return 0;
 }
 
-// Which launches can keep prepared polygons at all ("prepared polygon cache" below): the kernel variants of
-// prepared_polygons_apply() (shading_kernel.h), untextured.  plan_bands() adds: one launch per frame, and room in the budgets.
-static bool prepared_polygons_possible(const application_t* app, const frame_plan* f) {
-	return f->ray_mode == kRaysDeferredBlocks && f->error_mode == kErrorNone && !f->table_in_memory && !f->textured
-		&& !f->p.light_texture_descriptors && app->shading_pass.arithmetic_mode != arithmetic_mode_fast && f->p.light_count != 0
-		&& (f->technique == kTechniquePsa || f->technique == kTechniquePsaBiased) && f->strategy >= kStrategySeparately && f->strategy <= kStrategyRandom
-		&& f->capacity >= 4 && f->capacity <= 5;
-}
-
 // Launches with wavefront rays may run n at a time: launch k on frame stream k mod n with
 // its own buffers, so that the (latency-bound) tracing of one launch overlaps the
 // (VALU-bound) shading of the next ones.  Everything else runs on device->stream, behind
@@ -1069,25 +531,8 @@ static int plan_bands(application_t* app, frame_plan* f) {
 	f->trace_blocks = (f->trace_blocks + 7u) & ~7u;
 	f->p.ray_block = f->ray_mode == kRaysDeferredBlocks ? ray_block_size(f->max_terms) : 0u;
 	f->p.refill_threshold = kRefillThreshold;
-	// The prepared polygons of a frame that is one launch (a frame in bands meets a context's buffers with another band each
-	// time, and config 4, the frame that is rendered in bands, has no such kernel variant): one buffer per pass, counted against
-	// the budget of the wavefront buffers like the shafts' tables, and against VKR_PREPARED_POLYGONS_MIB.  (bind_textures() runs
-	// after this: a frame with light textures is turned away by choose_prepared_mode().)
-	f->prepared_quads = f->terms_quads = 0;
-	if (f->band_count == 1 && frames->prepared.budget_mib != 0u && prepared_polygons_possible(app, f)) {
-		const uint32_t thread_count = f->blocks_per_band * 256u;
-		const size_t quads = (size_t) thread_count * f->p.light_count * (prepared_bytes_per_pair(f->capacity) / 16u);
-		const double bytes = 16.0 * (double) quads;
-		if (bytes <= (double) frames->prepared.budget_mib * 1048576.0
-			&& f->depth * wavefront_bytes(thread_count, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, 0u) + bytes <= budget)
-			f->prepared_quads = quads;
-		// the terms count against both budgets together with the polygons; where only the polygons fit, the launch loads without
-		const size_t terms_quads = (size_t) thread_count * f->p.light_count * (sector_terms_bytes_per_pair(f->capacity) / 16u);
-		const double both = bytes + 16.0 * (double) terms_quads;
-		if (f->prepared_quads != 0 && frames->prepared.terms_enabled && both <= (double) frames->prepared.budget_mib * 1048576.0
-			&& f->depth * wavefront_bytes(thread_count, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, 0u) + both <= budget)
-			f->terms_quads = terms_quads;
-	}
+	// (the kept prepared polygons count against the budget beside the wavefront buffers of the frame's one launch)
+	plan_prepared_polygons(app, f, f->depth * wavefront_bytes(f->blocks_per_band * 256u, f->max_terms, f->p.light_count, f->hidden_terms, f->base_color, 0u), budget);
 	return 0;
 }
 
@@ -1206,316 +651,13 @@ static int resolve_materials(application_t* app, shade_params& p, hipStream_t st
 	return 0;
 }
 
-// light shafts: which patches need no shadow rays toward which lights (light_shafts.h).  For the techniques
-// whose samples aim at the light polygon itself (every ray then lies inside the shaft); the walk uses the
-// four-wide tree whatever tree the rays walk.
-static bool light_shafts_apply(const application_t* app, const frame_plan* f, const frame_context* frame) {
-	const frame_pipeline* frames = f->frames;
-	const uint32_t rays_per_pixel = app->render_settings.sample_count * f->p.light_count * (f->strategy == (int) sampling_strategies_diffuse_only ? 1u : 2u);
-	return frame && (frames->light_shafts == 1u || (frames->light_shafts == 2u && rays_per_pixel >= 8u)) && is_deferred(f->ray_mode) && f->error_mode == kErrorNone
-		&& app->scene.acceleration_structure.wide_nodes && f->p.light_count
-		&& app->scene.acceleration_structure.node_count < (1u << kShaftLightShift)  // (a queue entry of the walk is a node or triangle index and a light)
-		&& aims_at_light_polygon(f->technique);
-}
-
-// What the verdicts of a launch are derived from, as bytes (light_shafts.h "Verdicts that are still true"): a frame context
-// keeps the image of its most recent launch (wavefront_buffers::shaft_seen) and the next launch is compared with it by
-// memcmp - exactly, not through a hash: "the same" now keeps a "clear" or a list, and a collision would keep a wrong one.
-// The image has two parts.  The ARRANGEMENT is this struct and, behind it, the ranges of the constants that the shading
-// positions are computed from (the camera's, the mesh's de-quantisation); then comes one record per LIGHT, its bytes in
-// the constants.
-// Who changes an input and how that shows here: a BVH build (scene load) gives the tree a new build_serial; whoever
-// rewrites the visibility buffer or another input in device memory - render_visibility_pass, upload_visibility, a caller
-// on its own through mark_inputs_changed() (INTEGRATION.md obliges it to) - bumps inputs_generation; camera, lights and
-// the de-quantisation reach the kernels through write_constants() alone, whose bytes are compared themselves.
-struct shaft_arrangement {
-	uint32_t first_block, block_count, width, height, tile_size, rank, rank_count, tiles_x, tile_count, slab_layout;
-	uint32_t light_count, max_light_vertex_count, lists, groups, max_steps;
-	uint32_t inputs_generation, build_serial, build_bits, node_count, wide_node_count;
-	float extent;
-	uint32_t light_stride;
-	const void *visibility, *positions, *nodes, *triangles, *wide_nodes;
-	float grid_origin[3], grid_inverse_cell[3];
-};
-static_assert(sizeof(shaft_arrangement) == 22 * 4 + 5 * sizeof(void*) + 6 * 4, "no padding: the struct is compared as bytes");
-
-// Puts the image of this launch's inputs together, compares it with the context's copy and keeps it as the new copy.
-// -> arrangement_same, same_lights (bit i: arrangement and light i < 32 are byte-equal to the previous launch's)
-static int compare_shaft_inputs(frame_pipeline* frames, wavefront_buffers* w, const shading_pass_t* pass, const shaft_arrangement& arrangement, bool& arrangement_same, uint32_t& same_lights) {
-	arrangement_same = false;
-	same_lights = 0u;
-	const uint8_t* constants = (const uint8_t*) pass->constants_host;
-	const size_t ranges[2][2] = {{offsetof(per_frame_constants_t, world_to_projection_space), offsetof(per_frame_constants_t, mis_visibility_estimate)},
-		{offsetof(per_frame_constants_t, mesh_dequantization_factor), offsetof(per_frame_constants_t, error_factor)}};
-	const size_t light_bytes = (size_t) arrangement.light_stride * arrangement.light_count;
-	size_t arrangement_bytes = sizeof(shaft_arrangement);
-	for (const size_t* range : ranges) arrangement_bytes += range[1] - range[0];
-	const size_t size = arrangement_bytes + light_bytes;
-	if (grow_bytes(&frames->shaft_scratch, &frames->shaft_scratch_capacity, size) || grow_bytes(&w->shaft_seen, &w->shaft_seen_capacity, size)) {
-		printf("Failed to allocate %zu bytes for the inputs of the light shafts.\n", size);
-		w->shaft_seen_size = 0;
-		return 1;
-	}
-	uint8_t* now = frames->shaft_scratch;
-	memcpy(now, &arrangement, sizeof(arrangement));
-	size_t cursor = sizeof(arrangement);
-	for (const size_t* range : ranges) {
-		memcpy(now + cursor, constants + range[0], range[1] - range[0]);
-		cursor += range[1] - range[0];
-	}
-	memcpy(now + cursor, constants + sizeof(per_frame_constants_t), light_bytes);
-	if (w->shaft_seen_size == size && memcmp(now, w->shaft_seen, arrangement_bytes) == 0) {
-		arrangement_same = true;
-		for (uint32_t i = 0; i != arrangement.light_count && i != 32u; ++i) {
-			const size_t at = arrangement_bytes + (size_t) arrangement.light_stride * i;
-			if (memcmp(now + at, w->shaft_seen + at, arrangement.light_stride) == 0) same_lights |= 1u << i;
-		}
-	}
-	memcpy(w->shaft_seen, now, size);
-	w->shaft_seen_size = size;
-	return 0;
-}
-
-// Band step 4: the shaft kernel of the band where light_shafts_apply(), its tables in p
-static int run_light_shafts(application_t* app, frame_plan* f, frame_context* frame, hipStream_t stream) {
-	shading_pass_t* pass = &app->shading_pass;
-	shade_params& p = f->p;
-	p.shaft_clear = NULL;
-	p.shaft_rectangles = NULL;
-	p.shaft_lists = NULL;
-	if (!light_shafts_apply(app, f, frame)) {
-		pass->last_shaft_groups = 0;
-		return 0;
-	}
-	frame_pipeline* frames = f->frames;
-	const acceleration_structure_t* structure = &app->scene.acceleration_structure;
-	uint32_t shaft_groups = shade_grid_size(p.block_count);
-	const bool lists = frames->shaft_lists != 0u && kShaftListMax != 0u;
-	if (ensure_shaft_words(&frame->buffers, (size_t) shaft_groups * p.light_count + 8, p.light_count, lists, stream)) return 1;
-	float extent = 0.0f;
-	for (int j = 0; j != 3; ++j) extent = fmaxf(extent, kGridMax / structure->grid_inverse_cell[j]);
-	// (VKR_SHAFT_COUNTERS=1: the walks count their steps into three words behind the table, for get_light_shaft_work())
-	static const bool count_work = getenv("VKR_SHAFT_COUNTERS") != NULL;
-	unsigned long long* work = NULL;
-	if (count_work) {
-		work = (unsigned long long*) (frame->buffers.shaft_clear + (((size_t) shaft_groups * p.light_count + 1u) & ~(size_t) 1u));
-		(void) hipMemsetAsync(work, 0, 3 * sizeof(unsigned long long), stream);
-	}
-	// (a small launch lasts as long as its longest walk: plan_bands(), at trace_blocks)
-	const uint32_t max_steps = frames->shaft_max_steps ? frames->shaft_max_steps : (shaft_groups < 12288u ? kShaftSmallLaunchSteps : kShaftMaxSteps);
-	shaft_arrangement arrangement;
-	memset(&arrangement, 0, sizeof(arrangement));
-	arrangement.first_block = p.first_block; arrangement.block_count = p.block_count;
-	arrangement.width = p.width; arrangement.height = p.height;
-	arrangement.tile_size = p.tile_size; arrangement.rank = p.rank; arrangement.rank_count = p.rank_count;
-	arrangement.tiles_x = p.tiles_x; arrangement.tile_count = p.tile_count; arrangement.slab_layout = p.slab_layout;
-	arrangement.light_count = p.light_count; arrangement.max_light_vertex_count = p.max_light_vertex_count;
-	arrangement.lists = lists ? 1u : 0u; arrangement.groups = shaft_groups; arrangement.max_steps = max_steps;
-	arrangement.inputs_generation = frames->inputs_generation;
-	arrangement.build_serial = structure->build_serial;
-	memcpy(&arrangement.build_bits, &structure->build_milliseconds, sizeof(arrangement.build_bits));
-	arrangement.node_count = structure->node_count; arrangement.wide_node_count = structure->wide_node_count;
-	arrangement.extent = extent;
-	arrangement.light_stride = (uint32_t) ((pass->constants_size - sizeof(per_frame_constants_t)) / p.light_count);
-	arrangement.visibility = p.visibility; arrangement.positions = p.positions;
-	arrangement.nodes = p.bvh.nodes; arrangement.triangles = p.bvh.triangles; arrangement.wide_nodes = structure->wide_nodes;
-	for (int j = 0; j != 3; ++j) {
-		arrangement.grid_origin[j] = structure->grid_origin[j];
-		arrangement.grid_inverse_cell[j] = structure->grid_inverse_cell[j];
-	}
-	bool arrangement_same;
-	uint32_t same_lights;
-	if (compare_shaft_inputs(frames, &frame->buffers, pass, arrangement, arrangement_same, same_lights)) return 1;
-	// VKR_SHAFT_REST=0, "every pair is walked in every frame": nothing rests and nothing is kept
-	if (frames->shaft_rest == 0u) { arrangement_same = false; same_lights = 0u; }
-	// (The kernel is launched even when the host expects every verdict to be kept: which pairs still rest, and which walks are
-	// due again, only the table on the device knows.  A launch whose waves read their words and leave: DESIGN.md 4.3.)
-	k_light_shafts<<<shaft_groups, 64, 0, stream>>>(p, (const uint4*) structure->wide_nodes, frame->buffers.shaft_clear, frame->buffers.shaft_rectangles, lists ? frame->buffers.shaft_lists : NULL, extent, work,
-		arrangement_same ? 1u : 0u, same_lights, frames->shaft_rest, max_steps);
-	if (hip_failed(hipGetLastError(), "launching the light shaft kernel")) {
-		// (what the tables hold now is anybody's guess)
-		frame->buffers.shaft_seen_size = 0;
-		return 1;
-	}
-	p.shaft_clear = frame->buffers.shaft_clear;
-	p.shaft_rectangles = frame->buffers.shaft_rectangles;
-	p.shaft_lists = lists ? frame->buffers.shaft_lists : NULL;
-	pass->last_shaft_groups = shaft_groups;
-	return 0;
-}
-
-// ---- prepared polygon cache ------------------------------------------------------------------
-// Everything the preparation of a launch reads, as bytes: this struct and behind it the constants of the launch - camera,
-// de-quantisation, roughness factor, the LTC table's lookup constants and every light's record - with the four noise
-// words blanked, which only the samples read.  (The constants hold more than the preparation reads - exposure, the MIS
-// visibility estimate: a change of those costs one plain and one storing launch and nothing else.)
-// What lies behind the pointers is named by inputs_generation (visibility buffer, mark_inputs_changed()), the tree's
-// build_serial (mesh and materials are uploaded with it, load_scene()) and the LTC table's upload_serial.
-struct prepared_arrangement {
-	uint32_t first_block, block_count, thread_count, width, height, tile_size, rank, rank_count, tiles_x, tile_count, slab_layout;
-	uint32_t light_count, max_light_vertex_count, strategy, technique, capacity, arithmetic_mode;
-	uint32_t inputs_generation, build_serial, ltc_serial, ltc_resolution, ltc_layer_count;
-	const void *visibility, *positions, *normals_and_tex_coords, *material_indices, *material_constants, *ltc_rgba, *ltc_rg;
-};
-static_assert(sizeof(prepared_arrangement) == 22 * 4 + 7 * sizeof(void*), "no padding: the struct is compared as bytes");
-
-static void forget_prepared_polygons(frame_pipeline* frames) {
-	if (!frames) return;
-	frames->prepared.state = kCacheEmpty;
-	frames->prepared.seen_size = 0;
-}
-
-// ... and gives the buffer back: for a launch that cannot keep prepared polygons at all (another kernel variant, a frame in
-// bands, no room in the budgets).  A launch whose inputs merely differ from the last one's keeps the buffer - a camera that
-// moves and stops would free and allocate 2 GB each time.  (hipFree waits for the device: no launch still loads from it.)
-static void release_prepared_polygons(frame_pipeline* frames) {
-	forget_prepared_polygons(frames);
-	if (!frames || (!frames->prepared.buffer && !frames->prepared.terms)) return;
-	(void) hipFree(frames->prepared.buffer);
-	(void) hipFree(frames->prepared.terms);
-	frames->prepared.buffer = NULL;
-	frames->prepared.terms = NULL;
-	frames->prepared.buffer_quads = frames->prepared.terms_quads = 0;
-}
-
-// Band step 4b: decides how this launch gets its prepared polygons -> f->prepared_mode, f->prepared
-//   loading  when the cache holds the polygons of exactly these inputs and the launch that stored them has completed (the
-//            event is queried, never waited for: until it completes, launches run plain) or runs on this launch's stream
-//   storing  when the inputs are those of the launch before and nothing is stored or being stored
-//   plain    otherwise - a moving frame pays a memcmp that fails early
-static int choose_prepared_mode(application_t* app, frame_plan* f, frame_context* frame, hipStream_t stream) {
-	const shade_params& p = f->p;
-	f->prepared_mode = kPreparedPlain;
-	f->prepared = NULL;
-	f->terms = NULL;
-	frame_pipeline* frames = f->frames;
-	if (!frames) return 0;
-	prepared_cache* cache = &frames->prepared;
-	cache->last_mode = kPreparedPlain;
-	if (!frame || f->prepared_quads == 0 || !prepared_polygons_possible(app, f)) {
-		release_prepared_polygons(frames);
-		++cache->launches[kPreparedPlain];
-		return 0;
-	}
-	const shading_pass_t* pass = &app->shading_pass;
-	prepared_arrangement arrangement;
-	memset(&arrangement, 0, sizeof(arrangement));
-	arrangement.first_block = p.first_block; arrangement.block_count = p.block_count; arrangement.thread_count = p.thread_count;
-	arrangement.width = p.width; arrangement.height = p.height;
-	arrangement.tile_size = p.tile_size; arrangement.rank = p.rank; arrangement.rank_count = p.rank_count;
-	arrangement.tiles_x = p.tiles_x; arrangement.tile_count = p.tile_count; arrangement.slab_layout = p.slab_layout;
-	arrangement.light_count = p.light_count; arrangement.max_light_vertex_count = p.max_light_vertex_count;
-	arrangement.strategy = (uint32_t) f->strategy; arrangement.technique = (uint32_t) f->technique; arrangement.capacity = (uint32_t) f->capacity;
-	arrangement.arithmetic_mode = (uint32_t) pass->arithmetic_mode;
-	arrangement.inputs_generation = frames->inputs_generation;
-	arrangement.build_serial = app->scene.acceleration_structure.build_serial;
-	arrangement.ltc_serial = app->ltc_table.upload_serial;
-	arrangement.ltc_resolution = p.ltc_resolution; arrangement.ltc_layer_count = p.ltc_layer_count;
-	arrangement.visibility = p.visibility; arrangement.positions = p.positions; arrangement.normals_and_tex_coords = p.normals_and_tex_coords;
-	arrangement.material_indices = p.material_indices; arrangement.material_constants = p.material_constants;
-	arrangement.ltc_rgba = p.ltc_rgba; arrangement.ltc_rg = p.ltc_rg;
-	const size_t size = sizeof(arrangement) + pass->constants_size;
-	if (grow_bytes(&cache->scratch, &cache->scratch_capacity, size) || grow_bytes(&cache->seen, &cache->seen_capacity, size)) {
-		printf("Failed to allocate %zu bytes for the inputs of the prepared polygons.\n", size);
-		forget_prepared_polygons(frames);
-		return 1;
-	}
-	uint8_t* now = cache->scratch;
-	memcpy(now, &arrangement, sizeof(arrangement));
-	memcpy(now + sizeof(arrangement), pass->constants_host, pass->constants_size);
-	memset(now + sizeof(arrangement) + offsetof(per_frame_constants_t, noise_random_numbers), 0, sizeof(((per_frame_constants_t*) NULL)->noise_random_numbers));
-	if (cache->seen_size != size || memcmp(now, cache->seen, size) != 0) {
-		// other inputs: whatever is stored, or being stored, is of no use to anybody any more
-		memcpy(cache->seen, now, size);
-		cache->seen_size = size;
-		cache->state = kCacheEmpty;
-		++cache->launches[kPreparedPlain];
-		return 0;
-	}
-	if (cache->state == kCachePending) {
-		hipError_t stored = hipEventQuery(cache->stored);
-		if (stored == hipSuccess) cache->state = kCacheValid;
-		else {
-			// (hipErrorNotReady is an answer, not an error: it must not meet the launch checks below)
-			(void) hipGetLastError();
-			// A launch on the stream of the storing launch runs behind it whatever the event says - the stream is in order -,
-			// so it loads: frames that are submitted in a burst on ONE stream (frames_in_flight <= 1) load from the third on
-			// instead of running plain until somebody waits.  Other streams are never made to wait for the storing launch.
-			if (stream != cache->stored_stream) ++cache->waited;
-		}
-	}
-	if (cache->state == kCacheValid || (cache->state == kCachePending && stream == cache->stored_stream)) {
-		// (the terms were filled behind the storing launch, in front of the event: they are as complete as the polygons)
-		const bool with_terms = cache->terms != NULL && cache->terms_quads != 0;
-		f->prepared_mode = with_terms ? kPreparedLoadingTerms : kPreparedLoading;
-		cache->last_mode = kPreparedLoading;
-		f->prepared = cache->buffer;
-		f->terms = with_terms ? cache->terms : NULL;
-		++(with_terms ? cache->loaded_with_terms : cache->loaded_without_terms);
-	}
-	else if (cache->state == kCacheEmpty) {
-		// (plan_bands() has found room for the buffer.  One of another size goes first: freeing waits for the device, so no launch
-		// still loads from it, and the bytes that the statistics report are those of this arrangement.)
-		if (cache->buffer && cache->buffer_quads != f->prepared_quads) {
-			(void) hipFree(cache->buffer);
-			cache->buffer = NULL;
-			cache->buffer_quads = 0;
-		}
-		if (grow_device_buffer(&cache->buffer, &cache->buffer_quads, f->prepared_quads, sizeof(uint4), "Failed to allocate %.1f MiB for the prepared polygons.\n")) return 1;
-		// the terms by the same rules; an arrangement without room for them keeps none
-		if (cache->terms && cache->terms_quads != f->terms_quads) {
-			(void) hipFree(cache->terms);
-			cache->terms = NULL;
-			cache->terms_quads = 0;
-		}
-		if (f->terms_quads != 0 && grow_device_buffer(&cache->terms, &cache->terms_quads, f->terms_quads, sizeof(float4), "Failed to allocate %.1f MiB for the sector terms.\n")) return 1;
-		// launches in flight on other streams may still load what an earlier arrangement stored here.  (A launch outside the
-		// pipeline runs behind finish_frames(), join_frame_pipeline(): it waits for events that it is behind already.)
-		for (uint32_t c = 0; c != VKR_MAX_FRAMES_IN_FLIGHT; ++c) {
-			frame_context* other = &frames->contexts[c];
-			if (other != frame && other->recorded) (void) hipStreamWaitEvent(stream, other->done, 0);
-		}
-		f->prepared_mode = cache->last_mode = kPreparedStoring;
-		f->prepared = cache->buffer;
-	}
-	// (mode 2 covers both loading kinds)
-	++cache->launches[f->prepared_mode == kPreparedLoadingTerms ? kPreparedLoading : f->prepared_mode];
-	return 0;
-}
-
-// ... and behind the launch: the terms kernel and the event of a storing launch, or nothing kept after a launch that failed
-static void note_prepared_launch(const application_t* app, frame_plan* f, int status, hipStream_t stream) {
-	frame_pipeline* frames = f->frames;
-	if (!frames) return;
-	if (status != 0) forget_prepared_polygons(frames);
-	else if (f->prepared_mode == kPreparedStoring) {
-		frames->prepared.stored_stream = stream;
-		// the sector terms of what the launch has stored, on its stream: the event that lets other streams load lies behind both
-		if (frames->prepared.terms) {
-			const sector_terms_launch_function_t fill = g_sector_terms_launchers[app->shading_pass.arithmetic_mode];
-			// (a kernel that the library lacks is an error, not a reason to load without terms)
-			if (!fill || fill(f->capacity, frames->prepared.buffer, frames->prepared.terms, f->p.thread_count, f->p.light_count, stream) != 0) {
-				printf("Failed to launch the kernel that fills the sector terms.\n");
-				forget_prepared_polygons(frames);
-				return;
-			}
-		}
-		if (hipEventRecord(frames->prepared.stored, stream) == hipSuccess) frames->prepared.state = kCachePending;
-		else forget_prepared_polygons(frames);
-	}
-}
-
 // Band step 5: the shading kernel, or the error display's; < 0: no such kernel variant was built
 static int launch_shading(const application_t* app, const frame_plan* f, hipStream_t stream) {
 	const int mode = app->shading_pass.arithmetic_mode;
 	const shade_params* p = &f->p;
 	if (f->error_mode != kErrorNone)
 		return g_error_launchers[mode](has_specular_technique(&app->render_settings), f->technique, f->capacity, f->error_mode, p, p->block_count, stream);
-	if (f->prepared_mode != kPreparedPlain) {
-		// (a variant that prepared_polygons_possible() promises and the library lacks is an error, not a reason to run plain)
-		const prepared_launch_function_t launch = g_prepared_launchers[mode][f->strategy - kStrategySeparately];
-		return launch ? launch(f->technique, f->capacity, f->prepared_mode, f->prepared, f->terms, p, p->block_count, stream) : -1;
-	}
+	if (f->prepared_mode != kPreparedPlain) return launch_prepared_shading(app, f, stream);
 	return g_launchers[mode + (p->light_texture_descriptors ? 3 : 0)][f->strategy](f->technique, f->capacity, f->ray_mode, p, p->block_count, stream);
 }
 
@@ -1670,65 +812,6 @@ extern "C" int render_shading_pass_encoded(application_t* app, void* out_radianc
 	return render_pass(app, out_radiance, out_rgb8);
 }
 
-// timed frames whose events are still in the ring
-static uint32_t timed_frames(const shading_pass_t* pass) { return pass->timing_cursor < pass->timing_ring_size ? pass->timing_cursor : pass->timing_ring_size; }
-
-// slot of the i-th of the most recent `count` timed frames
-static uint32_t timing_slot(const shading_pass_t* pass, uint32_t count, uint32_t i) { return (pass->timing_cursor - count + i) % pass->timing_ring_size; }
-
-// milliseconds from `from` to `to` once `to` has completed (0 if either cannot be read)
-static float elapsed_milliseconds(hipEvent_t from, hipEvent_t to) {
-	float ms = 0.0f;
-	if (hipEventSynchronize(to) != hipSuccess || hipEventElapsedTime(&ms, from, to) != hipSuccess) ms = 0.0f;
-	return ms;
-}
-
-// the time from event `from` to event `to` of each of the most recent `count` timed frames
-static uint32_t get_timed_intervals(application_t* app, uint32_t from, uint32_t to, float* out, uint32_t count) {
-	const shading_pass_t* pass = &app->shading_pass;
-	if (!pass->timing_ring) return 0;
-	if (count > timed_frames(pass)) count = timed_frames(pass);
-	for (uint32_t i = 0; i != count; ++i) {
-		uint32_t slot = timing_slot(pass, count, i);
-		out[i] = elapsed_milliseconds(timing_event(pass, slot, from), timing_event(pass, slot, to));
-	}
-	return count;
-}
-
-extern "C" uint32_t get_dispatch_milliseconds(application_t* app, float* out, uint32_t count) {
-	return get_timed_intervals(app, kTimingFrameStart, kTimingFrameEnd, out, count);
-}
-
-// what a timed frame spends before its shading kernel starts: the shaft kernel (and, for textured scenes, the material resolve)
-extern "C" uint32_t get_light_shaft_milliseconds(application_t* app, float* out, uint32_t count) {
-	return get_timed_intervals(app, kTimingFrameStart, kTimingShadingStart, out, count);
-}
-
-extern "C" uint32_t get_shading_kernel_milliseconds(application_t* app, float* out, uint32_t count) {
-	return get_timed_intervals(app, kTimingShadingStart, kTimingShadingEnd, out, count);
-}
-
-extern "C" uint32_t get_frame_period_milliseconds(application_t* app, float* out, uint32_t count) {
-	shading_pass_t* pass = &app->shading_pass;
-	if (!pass->timing_ring || pass->timing_cursor < 2) return 0;
-	uint32_t stride = pass->timing_stride > 1 ? pass->timing_stride : 1;
-	uint32_t available = timed_frames(pass) - 1;
-	if (count > available) count = available;
-	for (uint32_t i = 0; i != count; ++i) {
-		uint32_t later = timing_slot(pass, count, i);
-		uint32_t earlier = (later + pass->timing_ring_size - 1) % pass->timing_ring_size;
-		out[i] = elapsed_milliseconds(timing_event(pass, earlier, kTimingFrameEnd), timing_event(pass, later, kTimingFrameEnd)) / (float) stride;
-	}
-	return count;
-}
-
-extern "C" float get_last_dispatch_milliseconds(application_t* app) {
-	float ms = 0.0f;
-	if (get_dispatch_milliseconds(app, &ms, 1) != 1) return 0.0f;
-	app->shading_pass.last_dispatch_ms = ms;
-	return ms;
-}
-
 // Diagnostics: replays the rays that the last frame queued and counts the work of the
 // traversal (profiles/ cites these numbers; not part of the frame).
 __global__ void __launch_bounds__(256) k_traversal_statistics(bvh_view bvh, ray_stream stream, unsigned long long* out) {
@@ -1840,12 +923,6 @@ __global__ void __launch_bounds__(256) k_traversal_statistics_wide(bvh_view bvh,
 	if (blocked_visits) atomicAdd(out + 9, blocked_visits);
 }
 
-// the wavefront buffers of the most recent launch with wavefront rays (the last band of the last frame), or NULL
-static const wavefront_buffers* last_launch_buffers(const application_t* app) {
-	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
-	return frames ? &frames->contexts[frames->last].buffers : NULL;
-}
-
 extern "C" int get_traversal_statistics(application_t* app, uint64_t out_statistics[6]) {
 	const wavefront_buffers* w = last_launch_buffers(app);
 	if (!w || !w->ray_directions || !app->shading_pass.use_ray_tracing || app->shading_pass.inline_rays) {
@@ -1879,101 +956,4 @@ extern "C" int get_traversal_statistics_of_tree(application_t* app, VkBool32 wid
 	int failed = vkr_copy_to_host(out_statistics, counters, sizeof(uint64_t) * 12, &app->device);
 	(void) hipFree(counters);
 	return failed;
-}
-
-// sums the words of the most recent launch's shaft table
-// out[0]: clear pairs, out[1 ... 5]: pairs that are traced, by reason (kShaftNoPixels ... kShaftTriangle, light_shafts.h),
-// out[6]: anything else, out[7]: pairs with an occluder list, out[8]: triangles on those lists
-__global__ void __launch_bounds__(256) k_count_clear_shafts(const uint32_t* words, size_t count, unsigned long long* out) {
-	for (size_t i = (size_t) blockIdx.x * 256u + threadIdx.x; i < count; i += (size_t) gridDim.x * 256u) {
-		uint32_t verdict = words[i] & 0xFFu;
-		uint32_t slot = verdict == kShaftClear ? 0u : (verdict == kShaftList ? 7u : (verdict >= kShaftNoPixels && verdict <= kShaftTriangle ? 1u + (verdict - kShaftNoPixels) : 6u));
-		atomicAdd(out + slot, 1ull);
-		if (verdict == kShaftList) atomicAdd(out + 8, (unsigned long long) ((words[i] >> 8) & 0x1Fu));
-	}
-}
-
-extern "C" int get_light_shaft_statistics(application_t* app, uint64_t out_statistics[12]) {
-	memset(out_statistics, 0, sizeof(uint64_t) * 12);
-	const shading_pass_t* pass = &app->shading_pass;
-	const wavefront_buffers* w = last_launch_buffers(app);
-	if (!w || !pass->last_shaft_groups || !w->shaft_clear) return 0;  // the last frame ran without the shaft test: all zero
-	if (finish_frames(app)) return 1;
-	size_t words = (size_t) pass->last_shaft_groups * app->scene_specification.polygonal_light_count;
-	unsigned long long* counter = NULL;
-	if (hip_failed(hipMalloc(&counter, sizeof(unsigned long long) * 16), "allocating counters")) return 1;
-	hipStream_t stream = (hipStream_t) app->device.stream;
-	(void) hipMemsetAsync(counter, 0, sizeof(unsigned long long) * 16, stream);
-	k_count_clear_shafts<<<256, 256, 0, stream>>>(w->shaft_clear, words, counter);
-	unsigned long long counts[16] = {0};
-	int failed = vkr_copy_to_host(counts, counter, sizeof(counts), &app->device);
-	(void) hipFree(counter);
-	out_statistics[0] = words;
-	out_statistics[1] = counts[0];
-	out_statistics[2] = pass->last_shaft_groups;
-	out_statistics[3] = app->scene_specification.polygonal_light_count;
-	for (int i = 0; i != 6; ++i) out_statistics[4 + i] = counts[1 + i];
-	out_statistics[10] = counts[7];
-	out_statistics[11] = counts[8];
-	return failed;
-}
-
-// {mode of the last launch, bytes of the buffer, launches plain / storing / loading, launches that found the storing one
-// incomplete, state, budget in MiB} of the prepared polygon cache (include/vkr_shading_pass.h)
-extern "C" int get_prepared_polygon_statistics(application_t* app, uint64_t out_statistics[8]) {
-	memset(out_statistics, 0, 8 * sizeof(uint64_t));
-	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
-	if (!frames) return 1;
-	const prepared_cache* cache = &frames->prepared;
-	out_statistics[0] = cache->last_mode;
-	out_statistics[1] = (uint64_t) cache->buffer_quads * sizeof(uint4);
-	for (int i = 0; i != 3; ++i) out_statistics[2 + i] = cache->launches[i];
-	out_statistics[5] = cache->waited;
-	out_statistics[6] = cache->state;
-	out_statistics[7] = cache->budget_mib;
-	return 0;
-}
-
-// {bytes of the buffer of the sector terms, loading launches with terms, loading launches without} (include/vkr_shading_pass.h)
-extern "C" int get_sector_terms_statistics(application_t* app, uint64_t out_statistics[3]) {
-	memset(out_statistics, 0, 3 * sizeof(uint64_t));
-	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
-	if (!frames) return 1;
-	const prepared_cache* cache = &frames->prepared;
-	out_statistics[0] = (uint64_t) cache->terms_quads * sizeof(float4);
-	out_statistics[1] = cache->loaded_with_terms;
-	out_statistics[2] = cache->loaded_without_terms;
-	return 0;
-}
-
-// (diagnostics, VKR_SHAFT_COUNTERS=1) {steps, triangle batches, walks} of the most recent launch's shaft kernel
-extern "C" int get_light_shaft_work(application_t* app, uint64_t out_work[3]) {
-	out_work[0] = out_work[1] = out_work[2] = 0;
-	const shading_pass_t* pass = &app->shading_pass;
-	const wavefront_buffers* w = last_launch_buffers(app);
-	if (!w || !pass->last_shaft_groups || !w->shaft_clear || !getenv("VKR_SHAFT_COUNTERS") || finish_frames(app)) return 0;
-	size_t words = ((size_t) pass->last_shaft_groups * app->scene_specification.polygonal_light_count + 1u) & ~(size_t) 1u;
-	return vkr_copy_to_host(out_work, w->shaft_clear + words, 3 * sizeof(uint64_t), &app->device);
-}
-
-// (diagnostics) the verdict words of the most recent launch, [patch][light]; returns how many were written
-extern "C" uint64_t read_back_light_shafts(application_t* app, uint32_t* out_words, uint64_t capacity) {
-	const shading_pass_t* pass = &app->shading_pass;
-	const wavefront_buffers* w = last_launch_buffers(app);
-	if (!w || !pass->last_shaft_groups || !w->shaft_clear || finish_frames(app)) return 0;
-	uint64_t words = (uint64_t) pass->last_shaft_groups * app->scene_specification.polygonal_light_count;
-	if (words > capacity) words = capacity;
-	if (vkr_copy_to_host(out_words, w->shaft_clear, sizeof(uint32_t) * words, &app->device)) return 0;
-	return words;
-}
-
-extern "C" uint64_t get_last_ray_count(const application_t* app) {
-	unsigned long long rays = 0;
-	const shading_pass_t* pass = &app->shading_pass;
-	if (!pass->ray_counter || !pass->use_ray_tracing || !pass->last_frame_traced_rays || !pass->frame_counter) return 0;
-	// (the kernels of the frame - the shading kernel with inline rays, else the resolve kernel of every
-	// band - added their rays to the frame's counter)
-	if (finish_frames((application_t*) app)) return 0;
-	if (vkr_copy_to_host(&rays, (const unsigned long long*) pass->ray_counter + (pass->frame_counter - 1u) % 16u, sizeof(rays), &app->device)) return 0;
-	return rays;
 }
