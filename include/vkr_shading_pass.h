@@ -461,7 +461,7 @@ VKR_API int get_traversal_statistics_of_tree(application_t* app, VkBool32 wide_t
 	12 inversesqrt as 1 / sqrt (inverse_square_root_ieee).  a, b (may be NULL for unary operations) and out are host arrays of
 	`count` floats.  0 on success. */
 VKR_API int evaluate_device_arithmetic(const device_t* device, uint32_t operation, const float* a, const float* b, float* out, uint32_t count);
-/*! Diagnostics for the material texture sampler (sample_texture() of csrc/shading_kernel.h, mirrored by
+/*! Diagnostics for the material texture sampler (sample_texture() of csrc/shading_inputs.h, mirrored by
 	oracle_sample_texture): samples one RGBA8 texture on the device, with the kernel of the arithmetic mode
 	`arithmetic_mode` (an arithmetic_mode_t) and the sRGB table of the pass.  texels_rgba8: `mip_count` levels, finest first,
 	each half as wide and as high as the one before (rounded down, at least 1), row-major, tightly packed.  inputs: six floats

@@ -2,7 +2,7 @@
 against the restatement) and tests/test_gpu_texture_sampler.py (the device sampler against the oracle).  Not collected by
 pytest.
 
-The restatement is written from the rule in the sampler's comment (oracle/oracle.h, csrc/shading_kernel.h), not from its
+The restatement is written from the rule in the sampler's comment (oracle/oracle.h, csrc/shading_inputs.h), not from its
 code: N = min(ceil(P_max / P_min), 16, ceil(P_max)) trilinear taps at level log2(P_max / N), clamped to the chain, at
 uv + (i / (N + 1) - 1 / 2) d(uv), i = 1 ... N, averaged; repeat addressing; sRGB texels decoded before filtering; a texel
 coordinate that no int holds addresses texel 0.  It takes the float32 inputs as they are and computes in binary64."""

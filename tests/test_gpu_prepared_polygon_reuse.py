@@ -1,4 +1,4 @@
-"""Prepared polygons that are kept while the inputs of the launches stand still (csrc/shading_kernel.h "Prepared polygons
+"""Prepared polygons that are kept while the inputs of the launches stand still (csrc/kept_polygons.h "Prepared polygons
 that are still true", csrc/prepared_polygons.hip): the first launch of an arrangement
 prepares its polygons itself (plain), the second one also writes them to device memory (storing), and the launches after
 it read them from there instead of preparing them (loading) - until any input of the preparation changes.  A loaded

@@ -1,4 +1,4 @@
-"""Sector terms that are kept with the prepared polygons (csrc/shading_kernel.h "Sector terms that are still true",
+"""Sector terms that are kept with the prepared polygons (csrc/kept_polygons.h "Sector terms that are still true",
 csrc/prepared_polygons.hip): behind the storing launch a kernel derives, for every
 sector that a sample of a decentral polygon can fall into, the eight inverse square roots that depend on the sector alone,
 and the launches after it load them instead of computing them.  A loaded term is the term, so every frame must be the

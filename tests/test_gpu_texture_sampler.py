@@ -1,4 +1,4 @@
-"""The device's material texture sampler (sample_texture() of csrc/shading_kernel.h) on its own, through
+"""The device's material texture sampler (sample_texture() of csrc/shading_inputs.h) on its own, through
 evaluate_device_texture_sampler: every tap count at every level of textures that are square or not, powers of two or not, with
 whole or truncated chains, at coordinates from texel centres to NaN.  In the libm and the exact arithmetic mode the device must
 equal the CPU oracle bit for bit; the fast mode is held to the binary64 restatement of tests/sampler_cases.py.  That the inputs

@@ -1,0 +1,85 @@
+"""The headers that csrc/shading_kernel.h was split into, checked with the compiler's front end and with make, no kernel
+is compiled or run: every header is self-contained; the host units of the pass see the launch contract
+(csrc/shade_params.h) and neither the samplers nor the shading program; an edit of the shading program rebuilds the kernel
+variant units and none of the host units.
+
+The last one asks make itself, in a copy of csrc/ and include/ whose objects are empty files that are newer than every
+source: what `make -n` rebuilds there after a touch of shading_kernel.h does not depend on whether, or when, the tree
+that the tests run in was built, and no file of that tree is touched."""
+import os
+import re
+import shutil
+import subprocess
+import time
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "vulkan_renderer_amd", "csrc")
+# the launch contract and what it includes, then the parts of the shading program
+NEW_HEADERS = ("device_types.h", "bvh_view.h", "psa_table_layout.h", "shade_params.h", "shading_inputs.h", "ltc_brdf.h", "light_records.h",
+               "shadow_terms.h", "kept_polygons.h")
+PROGRAM_HEADER = "shading_kernel.h"  # the one that holds evaluate_light
+HOST_UNITS = ("frame_transfers", "pass_diagnostics", "render_targets", "slab_assembly", "output_encoding", "prepared_polygons")
+
+
+def make_variable(name):
+    return subprocess.run(["make", "-s", "-C", CSRC, "--no-print-directory", "--eval", "print-variable: ; @echo $(%s)" % name, "print-variable"],
+                          capture_output=True, text=True, timeout=120, check=True).stdout.strip()
+
+
+@pytest.fixture(scope="module")
+def hipcc():
+    compiler = make_variable("HIPCC")
+    if not (compiler and (os.path.isfile(compiler) or shutil.which(compiler))):
+        pytest.skip("no hipcc (csrc/Makefile: HIPCC = %r)" % compiler)
+    return [compiler, "--offload-arch=" + make_variable("ARCH"), "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC]
+
+
+def test_every_new_header_compiles_alone(hipcc, tmp_path):
+    running = []
+    for header in NEW_HEADERS:
+        assert os.path.isfile(os.path.join(CSRC, header)), header
+        unit = tmp_path / (header[:-2] + "_alone.hip")
+        unit.write_text('#include "%s"\n' % header)
+        running.append((header, subprocess.Popen(hipcc + ["-fsyntax-only", str(unit)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+    for header, process in running:
+        output = process.communicate(timeout=300)[0]
+        assert process.returncode == 0, "%s is not self-contained:\n%s" % (header, output)
+
+
+@pytest.mark.parametrize("unit", ["frame_transfers", "pass_diagnostics"])
+def test_host_units_see_the_contract_only(hipcc, unit):
+    listed = subprocess.run(hipcc + ["-M", os.path.join(CSRC, unit + ".hip")], capture_output=True, text=True, timeout=300)
+    assert listed.returncode == 0, listed.stderr
+    names = {os.path.basename(path) for path in listed.stdout.replace("\\\n", " ").split()}
+    assert "shade_params.h" in names, sorted(names)
+    for header in ("polygon_sampling.h", "related_work.h", "glibc_math.h", PROGRAM_HEADER):
+        assert header not in names, "%s.hip includes %s" % (unit, header)
+
+
+def test_an_edit_of_the_shading_program_rebuilds_no_host_unit(hipcc, tmp_path):
+    csrc = tmp_path / "vulkan_renderer_amd" / "csrc"
+    shutil.copytree(CSRC, csrc, ignore=shutil.ignore_patterns("build"))
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+
+    def recipes(*arguments):
+        done = subprocess.run(["make", "-n", "-C", str(csrc), "--no-print-directory"] + list(arguments) + ["all", "ieee"], capture_output=True, text=True, timeout=300)
+        assert done.returncode == 0, done.stderr
+        return set(re.findall(r" -o build/(\w+)\.o\b", done.stdout))
+
+    objects = recipes("-B")
+    assert set(HOST_UNITS) <= objects and "shade_libm_3" in objects, sorted(objects)
+    now = time.time()
+    # (the generated clip cases are newer than their generator, whatever order a checkout wrote the two in)
+    os.utime(csrc / "clip_cases.inc", (now + 30, now + 30))
+    (csrc / "build").mkdir()
+    for name in objects:
+        path = csrc / "build" / (name + ".o")
+        path.write_bytes(b"")
+        os.utime(path, (now + 60, now + 60))
+    assert recipes() == set(), "objects that are newer than every source are rebuilt"
+    os.utime(csrc / PROGRAM_HEADER, (now + 120, now + 120))
+    rebuilt = recipes()
+    assert "shade_libm_3" in rebuilt, sorted(rebuilt)
+    assert not rebuilt & set(HOST_UNITS), sorted(rebuilt & set(HOST_UNITS))

@@ -20,27 +20,13 @@
 // The reference leaves these precisions to the GLSL driver
 // (src/shaders/polygon_sampling.glsl:79-82).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#ifndef VKR_MATH_MODE
-#define VKR_MATH_MODE 0
-#endif
-#define VKR_FAST_MATH (VKR_MATH_MODE == 1)
-// glibc's functions in both IEEE modes (mode 0 keeps the polynomial arctangent: VKR_MATH_MODE == 2 below)
-#define VKR_LIBM_MATH (VKR_MATH_MODE != 1)
-
-#define VKR_DEV __device__ __forceinline__
+#include "device_types.h"  // VKR_MATH_MODE and what follows from it, VKR_DEV, f2 / f3 / f4
 
 namespace vkr {
 
 constexpr float kPi = 3.1415926535897932384626433832795f;
 constexpr float kInvPi = 0.31830988618379067153776752674503f;
 constexpr float kHalfPi = 1.5707963267948966192313216916398f;
-
-struct f2 { float x, y; };
-struct f3 { float x, y, z; };
-struct f4 { float x, y, z, w; };
 
 VKR_DEV f2 mk2(float x, float y) { f2 r; r.x = x; r.y = y; return r; }
 VKR_DEV f3 mk3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
@@ -119,6 +105,8 @@ VKR_DEV float divide(float a, float b) {
 	return __builtin_amdgcn_div_fixupf(q, b, a);
 #endif
 }
+// every component over one divisor, each quotient on its own
+VKR_DEV f3 divide3(f3 v, float d) { return mk3(divide(v.x, d), divide(v.y, d), divide(v.z, d)); }
 VKR_DEV float rcp(float x) {
 #if VKR_FAST_MATH
 	return __builtin_amdgcn_rcpf(x);

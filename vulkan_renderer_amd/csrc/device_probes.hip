@@ -4,6 +4,7 @@
 // the tests of device_math.h see here is the arithmetic those kernels use.
 #include "shade_launchers.h"
 #include "pass_internal.h"
+#include "device_math.h"
 
 using namespace vkr;
 

@@ -50,17 +50,17 @@ struct wavefront_buffers {
 	float* shaft_lists;
 	size_t shaft_list_words;
 	// the second polygon table of every shading workgroup, for the kernel variants that keep one table in LDS only
-	// (shading_kernel.h psa_table_in_memory); allocated when such a variant first runs
+	// (shade_params.h psa_table_in_memory); allocated when such a variant first runs
 	float2* psa_table_memory;
 	size_t psa_table_bytes;
 };
 
-// The prepared polygons of the most recent launches (shading_kernel.h "Prepared polygons that are still true")
+// The prepared polygons of the most recent launches (kept_polygons.h "Prepared polygons that are still true")
 enum { kCacheEmpty = 0, kCachePending = 1, kCacheValid = 2 };
 struct prepared_cache {
 	uint4* buffer;  // the second argument of the storing and the loading kernel, allocated when a launch first stores
 	size_t buffer_quads;
-	// the sector terms of the polygons in `buffer` (shading_kernel.h "Sector terms that are still true"): the third argument of
+	// the sector terms of the polygons in `buffer` (kept_polygons.h "Sector terms that are still true"): the third argument of
 	// the kernel that loads with terms, allocated, retained and released by the rules of `buffer`, and filled behind the storing
 	// launch, in front of `stored`.  terms_quads: its size, 0: the launches of this arrangement load without terms
 	float4* terms;
@@ -157,7 +157,7 @@ struct frame_plan {
 	// hold the polygons alone (or VKR_SECTOR_TERMS=0), and the launches load without terms
 	const float4* terms;
 	size_t terms_quads;
-	// (table_in_memory: the kernel variants that keep one of their two polygon tables in device memory, shading_kernel.h psa_table_in_memory)
+	// (table_in_memory: the kernel variants that keep one of their two polygon tables in device memory, shade_params.h psa_table_in_memory)
 	bool table_in_memory, hidden_terms, base_color, use_wide_tree, textured, pipelined;
 	uint32_t grid_blocks, table_bytes_per_workgroup, max_terms;
 	// frames in flight (1: not pipelined), the bands of the frame, workgroups of the tracing kernels (wavefront rays only)

@@ -303,7 +303,7 @@ VKR_API uint32_t get_abi_struct_sizes(uint64_t* sizes, uint32_t capacity) {
 /* Host-side description of the slab layout that render_shading_pass() writes for
    app->tile_schedule with the given rank: pixel (x, y) of every slab slot, or
    0xFFFFFFFF twice for padding slots.  Same arithmetic as locate_pixel() in
-   csrc/shading_kernel.h; lets hosts (and the CPU tests of the multi-process path)
+   csrc/shading_inputs.h; lets hosts (and the CPU tests of the multi-process path)
    scatter gathered slabs without touching a GPU. */
 VKR_API uint64_t get_slab_pixel_coordinates(const application_t* app, uint32_t rank, uint32_t* out_xy, uint64_t capacity) {
 	uint32_t width = app->swapchain.extent.width, height = app->swapchain.extent.height;

@@ -26,6 +26,7 @@
 // leaf order, w of vertex 0 carries the original primitive index.
 #pragma once
 #include "device_math.h"
+#include "bvh_view.h"
 
 namespace vkr {
 
@@ -43,13 +44,6 @@ constexpr uint32_t kNoLeaf = 0xFFFFFFFFu;
 // outward rounding margin of the quantised boxes in cells: covers the rounding of the
 // grid transform of the ray and of the slab arithmetic (a few 1e-3 cells each)
 constexpr float kGridMargin = 0.05f;
-
-struct bvh_view {
-	const uint4* nodes;       // 16 bytes per node, depth-first order
-	const float4* triangles;  // 3 float4 per leaf slot
-	uint32_t node_count;      // 2 * triangle_count - 1
-	f3 grid_origin, grid_inverse_cell;
-};
 
 #if VKR_FAST_MATH
 // the triangle test below with every product rounded before it is added (see ray_triangle_edges)

@@ -7,7 +7,7 @@
 // those rays arrives, whatever its direction.  k_light_shafts decides that per patch and light with ONE
 // conservative walk of the four-wide BVH by the whole wave (64 boxes or 64 triangles per step, one per lane,
 // the shaft's planes wave-uniform); the shading kernel then writes the terms of such a light as final ones
-// instead of queueing their rays (accumulate(), shading_kernel.h).  The result of every ray query is unchanged:
+// instead of queueing their rays (accumulate(), shadow_terms.h).  The result of every ray query is unchanged:
 // "clear" is only ever claimed when no triangle can be hit, with margins that cover the rounding of the kernels
 // that would have traced the rays, so frames stay bit-identical (tests/test_gpu_light_shafts.py renders them
 // with and without).  What it buys depends on the scene: at config 3 the benchmark scene is left with 1.6 M of its
@@ -18,7 +18,7 @@
 // seen edge-on) the reference's directions leave it, and the ray query toward the light's PLANE still decides the term.
 // So the shaft is built around a rectangle R in the light's plane space that contains the polygon with a margin of
 // 1/32 of its size, and the shading kernel lets a ray skip the tracing only if it meets the light's plane inside a
-// slightly smaller rectangle (shaft_holds_ray, shading_kernel.h; out_rectangles carries it); every other ray is traced.
+// slightly smaller rectangle (shaft_holds_ray, shadow_terms.h; out_rectangles carries it); every other ray is traced.
 //
 // Conservative by construction.  With B the bounding box of the patch's shading positions (plus margin), c its
 // centre, support(n) = |n.x| h.x + |n.y| h.y + |n.z| h.z the reach of B along n, L'_i the four corners of R in world
@@ -46,7 +46,8 @@
 // that its own triangle test accepts - its boxes are rounded outwards, lbvh.h kGridMargin.)  Around occluders most pairs
 // end this way: config 3 of the benchmark scene 85 % of the pairs that are not clear, 4.3 triangles on average.
 #pragma once
-#include "shading_kernel.h"
+#include "light_records.h"
+#include "lbvh.h"
 
 namespace vkr {
 
@@ -74,7 +75,7 @@ constexpr float kShaftDilation = 1.0f / 32.0f;
 // Occluder lists (above).  Measured (profiles/r05zg, frame period of config 3 / config 4 with kShaftListMax = 4, 6, 8, 12,
 // 16; none: 1.400 / 22.6 ms): 1.304 / 21.06, 1.240 / 20.15, 1.217 / 19.41, 1.187 / 19.01, 1.192 / 18.87 ms - a triangle
 // test costs a twelfth of what tracing the ray costs, and the walks that give up do so a little later.
-// (kShaftListMax: shading_kernel.h)
+// (kShaftListMax: shade_params.h)
 
 // what the walk needs to know about one (patch, light), wave-uniform, in LDS
 struct shaft_state {

@@ -3,6 +3,7 @@
 // device code, so the table, the kernel that fills it and every kernel that reads it live in this one unit.
 // Compiled in exact mode (-ffp-contract=off): srgb_code_by_powf restates the oracle operation for operation.
 #include "pass_internal.h"
+#include "device_math.h"  // gclamp, gm_powf
 #include <hip/hip_fp16.h>
 
 using namespace vkr;

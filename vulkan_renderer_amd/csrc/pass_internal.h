@@ -3,7 +3,7 @@
 // one unit calls in another.  Functions only: the pipeline's structs stay private to its own units (frame_pipeline.h).
 // The library is built with -fvisibility=hidden, so none of these is exported.
 #pragma once
-#include "shading_kernel.h"
+#include "shade_params.h"
 #include "host/vkr_internal.h"
 
 inline vkr::bvh_view make_bvh_view(const acceleration_structure_t* structure) {

@@ -1,4 +1,4 @@
-// The prepared polygon cache (shading_kernel.h "Prepared polygons that are still true", "Sector terms that are still
+// The prepared polygon cache (kept_polygons.h "Prepared polygons that are still true", "Sector terms that are still
 // true"): which launches keep prepared polygons, the room for them in the budgets, the state machine that
 // decides whether a launch stores, loads or runs plain, and the launch of those kernel variants.  No kernel of its own.
 #include "shade_launchers.h"
@@ -28,7 +28,7 @@ void destroy_prepared_polygons(frame_pipeline* frames) {
 	free_inputs(&frames->prepared.seen);
 }
 
-// Which launches can keep prepared polygons at all: the kernel variants of prepared_polygons_apply() (shading_kernel.h),
+// Which launches can keep prepared polygons at all: the kernel variants of prepared_polygons_apply() (shade_params.h),
 // untextured.  plan_prepared_polygons() adds: one launch per frame, and room in the budgets.
 static bool prepared_polygons_possible(const application_t* app, const frame_plan* f) {
 	return f->ray_mode == kRaysDeferredBlocks && f->error_mode == kErrorNone && !f->table_in_memory && !f->textured

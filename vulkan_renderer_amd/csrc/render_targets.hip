@@ -1,6 +1,8 @@
 // The render targets, the primary visibility pass that fills the visibility buffer, and the blocking transfers
 // of the targets (reading a frame back as the reference's implement_screenshot does, src/main.c:1719).
 #include "pass_internal.h"
+#include "lbvh.h"            // the visibility pass: closest_front_hit
+#include "shading_inputs.h"  // ... and the constant loads
 
 using namespace vkr;
 

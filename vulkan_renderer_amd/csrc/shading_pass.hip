@@ -146,7 +146,7 @@ static int ensure_wavefront(wavefront_buffers* w, uint32_t thread_count, uint32_
 	}
 	free_wavefront_buffers(w);
 	w->thread_count = thread_count; w->max_terms = max_terms; w->max_codes = max_codes;
-	// the record word of a ray: thread and code cursor (shading_kernel.h ray_record)
+	// the record word of a ray: thread and code cursor (shade_params.h ray_record)
 	uint32_t thread_bits = 1;
 	while (thread_bits < 32 && (1ull << thread_bits) < thread_count) ++thread_bits;
 	if (terms >= 0xFFFFFFFFull || (size_t) (max_codes + 3u) * thread_count >= 0xFFFFFFFFull || thread_bits >= 32 || ((uint64_t) max_codes << thread_bits) > 0xFFFFFFFFull) {
@@ -156,7 +156,7 @@ static int ensure_wavefront(wavefront_buffers* w, uint32_t thread_count, uint32_
 	w->thread_bits = thread_bits;
 	w->queue_capacity = queue_capacity_for(thread_count, max_terms);
 	size_t ray_slots = (size_t) w->queue_capacity * kRayQueueCount;
-	// (codes are stored four to a word per thread: code_slot() in shading_kernel.h)
+	// (codes are stored four to a word per thread: code_slot() in shade_params.h)
 	if (hipMalloc(&w->codes, (size_t) ((max_codes + 3u) & ~3u) * thread_count) != hipSuccess
 		|| hipMalloc(&w->terms_visible, terms * 12) != hipSuccess
 		|| (hidden_terms && hipMalloc(&w->terms_hidden, terms * 12) != hipSuccess)
@@ -618,7 +618,7 @@ static int take_frame_context(application_t* app, frame_plan* f, frame_context**
 	}
 	*out_frame = frame;
 	if (f->table_in_memory) {
-		// a region per workgroup of the launch, in the launch's own buffers (shading_kernel.h psa_table_in_memory)
+		// a region per workgroup of the launch, in the launch's own buffers (shade_params.h psa_table_in_memory)
 		wavefront_buffers* owner = frame ? &frame->buffers : &frames->device_stream_buffers;
 		const size_t bytes = (size_t) shade_grid_size(f->blocks_per_band) * f->table_bytes_per_workgroup;
 		if (grow_device_buffer(&owner->psa_table_memory, &owner->psa_table_bytes, bytes, 1, "Failed to allocate %.1f MiB for the polygon tables that do not fit into LDS.\n")) return 1;

@@ -101,7 +101,7 @@ extern "C" int VKR_LAUNCH_NAME(int technique, int capacity, int rays, const shad
 	}
 }
 
-// The same kernels with kept prepared polygons (shading_kernel.h "Prepared polygons that are still true"): the storing or
+// The same kernels with kept prepared polygons (kept_polygons.h "Prepared polygons that are still true"): the storing or
 // the loading instantiation, which exist where prepared_polygons_apply().  Same return values.
 #if VKR_STRATEGY >= 2 && !VKR_LIGHT_TEXTURES && !VKR_FAST_MATH
 #if VKR_MATH_MODE == 2

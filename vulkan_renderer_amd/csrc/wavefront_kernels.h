@@ -3,7 +3,8 @@
 // Instantiated once, in shading_pass.hip.  Ray-query contract: reference
 // src/shaders/shading_pass.frag.glsl:120-138 (opaque, any hit terminates, t in [1e-3, t_max]).
 #pragma once
-#include "shading_kernel.h"
+#include "shading_inputs.h"
+#include "lbvh.h"
 
 namespace vkr {
 
