@@ -71,6 +71,32 @@ def test_rays_whose_stack_leaves_lds_give_the_same_frame(dataset, monkeypatch):
     assert np.array_equal(spilled.view(np.uint32), image.view(np.uint32))
 
 
+@pytest.mark.parametrize("lds_entries", [16, 4], ids=["default_lds_stack", "four_lds_entries"])
+def test_traversal_statistics_of_both_trees_are_consistent(dataset, lds_entries, monkeypatch):
+    """get_traversal_statistics_of_tree() replays the queued rays with one outer loop for both trees (csrc/traversal_statistics.hip:
+    queue stride, null rays, the longest ray of each 64, the final atomics) and a walk per tree.  What that loop must keep,
+    whatever the walk counts: every queued ray once; a blocked ray had a triangle test; a wave step is the longest of 64 rays.
+    And of the wide walk: a fetched node has one to four children, and the rays beyond the LDS stack are those whose
+    stack - with the next item, which trace_shadow_rays_wide keeps on it, one entry more - outgrows the entries in use
+    (16 = kWideStackLds, or VKR_WIDE_STACK_LDS).  The host builder: the tree is the same in every run."""
+    if lds_entries != 16:
+        monkeypatch.setenv("VKR_WIDE_STACK_LDS", str(lds_entries))
+    r, _ = render_config(dataset, 3, 256, 144, "sah_host")
+    rays = r.last_ray_count()
+    trees = {"wide": r.traversal_statistics(True), "binary": r.traversal_statistics(False)}
+    r.close()
+    print(lds_entries, trees)
+    assert rays > 0
+    for name, s in trees.items():
+        assert s["rays"] == rays, name
+        assert s["blocked_rays"] <= s["triangle_tests"], (name, s)
+        assert s["longest_ray_visits"] <= s["wave_steps"] <= s["node_visits"] <= 64 * s["wave_steps"], (name, s)
+    wide = trees["wide"]
+    assert wide["node_visits"] <= wide["boxes_tested"] <= 4 * wide["node_visits"], wide
+    assert wide["node_visits_of_blocked_rays"] <= wide["node_visits"], wide
+    assert (wide["rays_beyond_lds_stack"] == 0) == (wide["deepest_stack"] + 1 <= lds_entries), wide
+
+
 @pytest.mark.parametrize("builder", BUILDERS)
 def test_primary_visibility_does_not_depend_on_the_builder(dataset, builder):
     import oracle

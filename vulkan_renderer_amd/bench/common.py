@@ -24,7 +24,7 @@ def kernel_source_hash():
     # shading_pass.hip around the kernels it instantiates - and the BVH builder do not change what they execute)
     for name in ("shading_kernel.h", "shade_params.h", "bvh_view.h", "psa_table_layout.h", "device_types.h", "shading_inputs.h", "ltc_brdf.h",
                  "light_records.h", "shadow_terms.h", "kept_polygons.h", "polygon_sampling.h", "related_work.h", "device_math.h", "glibc_math.h", "lbvh.h", "clip_cases.inc",
-                 "wavefront_kernels.h", "light_shafts.h", "shading_variants.hip", "Makefile"):
+                 "wavefront_kernels.h", "ray_stream.h", "light_shafts.h", "shading_variants.hip", "Makefile"):
         h.update(name.encode())
         h.update(open(os.path.join(base, name), "rb").read())
     return h.hexdigest()[:16]

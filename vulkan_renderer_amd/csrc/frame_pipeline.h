@@ -1,5 +1,5 @@
 // What the units of the frame pipeline share and nobody else includes (shading_pass.hip, frame_transfers.hip,
-// light_shaft_step.hip, prepared_polygons.hip, pass_diagnostics.hip): the pipeline's structs and the functions that one of
+// light_shaft_step.hip, prepared_polygons.hip, pass_diagnostics.hip, traversal_statistics.hip): the pipeline's structs and the functions that one of
 // these units calls in another.  The narrow header of the rest of the pass is pass_internal.h.
 #pragma once
 #include "pass_internal.h"

@@ -133,6 +133,13 @@ VKR_DEV bool ray_box(uint4 n, const grid_ray& r, float t_min, float t_max) {
 	return near <= far * 1.0000004f;
 }
 
+// What every walk shares, loop aside (a loop template changed the schedule of the shading kernels, profiles/r28_summary.md).
+// The next node: an inner node that was hit is entered (its left child follows it), a leaf is followed by the next node as
+// well; otherwise the link leaves the subtree.
+VKR_DEV uint32_t threaded_next(uint32_t node, uint4 n, bool hit) { return (hit || (n.w & kLeafBit) != 0) ? node + 1 : n.w; }
+// the three vertices behind the link of a leaf (kLeafBit | triangle slot, of either layout; a bare slot is one too)
+VKR_DEV const float4* leaf_triangle(const bvh_view& bvh, uint32_t link) { return bvh.triangles + 3 * (size_t) (link & ~kLeafBit); }
+
 // Any-hit query (shadow rays).  Returns true iff some triangle intersects the
 // ray within [t_min, t_max].
 VKR_DEV bool any_hit(const bvh_view& bvh, f3 o, f3 d, float t_min, float t_max) {
@@ -146,12 +153,10 @@ VKR_DEV bool any_hit(const bvh_view& bvh, f3 o, f3 d, float t_min, float t_max) 
 		bool is_leaf = (n.w & kLeafBit) != 0;
 		bool hit = ray_box(n, r, t_min, t_max);
 		if (hit && is_leaf) {
-			const float4* t = bvh.triangles + 3 * (size_t) (n.w & ~kLeafBit);
+			const float4* t = leaf_triangle(bvh, n.w);
 			if (ray_triangle<false>(t[0], t[1], t[2], o, d, t_min, t_max, dist)) return true;
 		}
-		// inner node that was hit: descend (the left child is the next node); a leaf is
-		// followed by the next node as well; otherwise leave the subtree
-		node = (hit || is_leaf) ? node + 1 : n.w;
+		node = threaded_next(node, n, hit);
 	}
 	return false;
 }
@@ -207,19 +212,42 @@ VKR_DEV wide_ray make_wide_ray(const grid_ray& r) {
 	return w;
 }
 
-// Conservative slab test of one child box of a wide node.  A NaN (0 * inf for a ray inside a slab
-// it runs parallel to) is ignored by min / max, which is conservative.
-VKR_DEV bool wide_ray_box(uint32_t qx, uint32_t qy, uint32_t qz, const wide_ray& r, float t_min, float t_max) {
+// Conservative slab test of one child box of a wide node, which also gives the parameter at which the ray enters the box.
+// A NaN (0 * inf for a ray inside a slab it runs parallel to) is ignored by min / max, which is conservative.
+VKR_DEV bool wide_ray_box_entry(uint32_t qx, uint32_t qy, uint32_t qz, const wide_ray& r, float t_min, float t_max, float& near) {
 	float nx = fmaf(__uint_as_float(__builtin_amdgcn_perm(qx, kPermMagic, r.near_x)), r.inv.x, r.shift.x);
 	float fx = fmaf(__uint_as_float(__builtin_amdgcn_perm(qx, kPermMagic, r.near_x ^ kPermFlip)), r.inv.x, r.shift.x);
 	float ny = fmaf(__uint_as_float(__builtin_amdgcn_perm(qy, kPermMagic, r.near_y)), r.inv.y, r.shift.y);
 	float fy = fmaf(__uint_as_float(__builtin_amdgcn_perm(qy, kPermMagic, r.near_y ^ kPermFlip)), r.inv.y, r.shift.y);
 	float nz = fmaf(__uint_as_float(__builtin_amdgcn_perm(qz, kPermMagic, r.near_z)), r.inv.z, r.shift.z);
 	float fz = fmaf(__uint_as_float(__builtin_amdgcn_perm(qz, kPermMagic, r.near_z ^ kPermFlip)), r.inv.z, r.shift.z);
-	float near = fmaxf(fmaxf(nx, ny), fmaxf(nz, t_min));
+	near = fmaxf(fmaxf(nx, ny), fmaxf(nz, t_min));
 	float far = fminf(fminf(fx, fy), fminf(fz, t_max));
 	return near <= far;
 }
+
+// One visit of a wide node, the fetch of its 64 bytes and the four slab tests: how the tracing kernel, the ray queries and
+// the replay that counts the tracing kernel's work visit; what a walk does with the children that were hit is its own.
+struct wide_visit {
+	uint4 link;      // the four links of the node (an absent child: kWideEmpty, and a box that only NaNs let through)
+	bool hit[4];
+	float entry[4];  // the parameter at which the ray enters each box
+};
+VKR_DEV wide_visit visit_wide_node(const uint4* wide_nodes, uint32_t item, const wide_ray& ray, float t_min, float t_max) {
+	const uint4* n = (const uint4*) ((const uint8_t*) wide_nodes + ((size_t) item << 6));
+	uint4 qx = n[0], qy = n[1], qz = n[2];
+	wide_visit v;
+	v.link = n[3];
+	v.hit[0] = wide_ray_box_entry(qx.x, qy.x, qz.x, ray, t_min, t_max, v.entry[0]);
+	v.hit[1] = wide_ray_box_entry(qx.y, qy.y, qz.y, ray, t_min, t_max, v.entry[1]);
+	v.hit[2] = wide_ray_box_entry(qx.z, qy.z, qz.z, ray, t_min, t_max, v.entry[2]);
+	v.hit[3] = wide_ray_box_entry(qx.w, qy.w, qz.w, ray, t_min, t_max, v.entry[3]);
+	return v;
+}
+
+// The per-lane stacks of the wide walks live in LDS and are addressed by 32-bit byte addresses in its own address space:
+// generic pointers make the compiler do the arithmetic in 64 bits and merge an entry's two homes into one flat access
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 // Closest hit with back-face culling (primary visibility).  Returns the original
 // primitive index or 0xFFFFFFFF.
@@ -234,7 +262,7 @@ VKR_DEV uint32_t closest_front_hit(const bvh_view& bvh, f3 o, f3 d, float t_min,
 		bool is_leaf = (n.w & kLeafBit) != 0;
 		bool hit = ray_box(n, r, t_min, t_max);
 		if (hit && is_leaf) {
-			const float4* t = bvh.triangles + 3 * (size_t) (n.w & ~kLeafBit);
+			const float4* t = leaf_triangle(bvh, n.w);
 			float4 p0 = t[0];
 			if (ray_triangle<true>(p0, t[1], t[2], o, d, t_min, t_max, dist)) {
 				uint32_t primitive = __float_as_uint(p0.w);
@@ -242,7 +270,7 @@ VKR_DEV uint32_t closest_front_hit(const bvh_view& bvh, f3 o, f3 d, float t_min,
 				if (dist < t_max || primitive < best) { t_max = dist; best = primitive; }
 			}
 		}
-		node = (hit || is_leaf) ? node + 1 : n.w;
+		node = threaded_next(node, n, hit);
 	}
 	return best;
 }

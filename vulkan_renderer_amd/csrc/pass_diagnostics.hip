@@ -1,6 +1,6 @@
 // What a caller reads about the frames it has rendered: the times between the events of the timed frames, the count of
-// their rays.  (The replay kernels of get_traversal_statistics() take the ray_stream of wavefront_kernels.h and live with
-// it, in shading_pass.hip; the shaft tables' diagnostics: light_shaft_step.hip.)
+// their rays.  (The replay kernels of get_traversal_statistics() walk with lbvh.h and have a unit of their own,
+// traversal_statistics.hip; the shaft tables' diagnostics: light_shaft_step.hip.)
 #include "frame_pipeline.h"
 
 // timed frames whose events are still in the ring

@@ -1,20 +1,10 @@
 // What the units of the shading pass's host side share (the frame pipeline - shading_pass.hip and the units beside it -,
-// render_targets.hip, output_encoding.hip, slab_assembly.hip, device_probes.hip): two small helpers and the functions that
-// one unit calls in another.  Functions only: the pipeline's structs stay private to its own units (frame_pipeline.h).
+// render_targets.hip, output_encoding.hip, slab_assembly.hip, device_probes.hip): the functions that one unit calls in
+// another.  Functions only: the pipeline's structs stay private to its own units (frame_pipeline.h).
 // The library is built with -fvisibility=hidden, so none of these is exported.
 #pragma once
 #include "shade_params.h"
 #include "host/vkr_internal.h"
-
-inline vkr::bvh_view make_bvh_view(const acceleration_structure_t* structure) {
-	vkr::bvh_view view;
-	view.nodes = (const uint4*) structure->nodes;
-	view.triangles = (const float4*) structure->triangle_vertices;
-	view.node_count = structure->node_count;
-	view.grid_origin = vkr::f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]};
-	view.grid_inverse_cell = vkr::f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]};
-	return view;
-}
 
 // ---- the frame pipeline: frame_transfers.hip, shading_pass.hip (slab_tiling) ----
 // Call behind a kernel on device->stream that reads a buffer frames in flight write (the radiance

@@ -79,8 +79,8 @@ struct closest_hit {
 };
 
 template <bool CULL_BACK>
-__device__ static inline void test_leaf(const bvh_view& bvh, uint32_t slot, const query_ray& r, closest_hit& best) {
-	const float4* t = bvh.triangles + 3 * (size_t) slot;
+__device__ static inline void test_leaf(const bvh_view& bvh, uint32_t link, const query_ray& r, closest_hit& best) {
+	const float4* t = leaf_triangle(bvh, link);
 	float4 p0 = t[0], p1 = t[1], p2 = t[2];
 	float unused;
 	if (!ray_triangle<CULL_BACK>(p0, p1, p2, r.o, r.d, r.t_min, r.t_max, unused)) return;
@@ -128,8 +128,8 @@ __global__ void __launch_bounds__(kBlock) k_closest_hits_binary(bvh_view bvh, co
 			uint4 n = bvh.nodes[node];
 			bool is_leaf = (n.w & kLeafBit) != 0;
 			bool hit = r.no_culling || ray_box(n, g, near, widened_far(r.t_max, best.t));
-			if (hit && is_leaf) test_leaf<CULL_BACK>(bvh, n.w & ~kLeafBit, r, best);
-			node = (hit || is_leaf) ? node + 1 : n.w;
+			if (hit && is_leaf) test_leaf<CULL_BACK>(bvh, n.w, r, best);
+			node = threaded_next(node, n, hit);
 		}
 	}
 	store_hit(out_hits, index, best);
@@ -152,10 +152,10 @@ __global__ void __launch_bounds__(kBlock) k_any_hits_binary(bvh_view bvh, const 
 			bool is_leaf = (n.w & kLeafBit) != 0;
 			bool hit = r.no_culling || ray_box(n, g, near, far);
 			if (hit && is_leaf) {
-				const float4* t = bvh.triangles + 3 * (size_t) (n.w & ~kLeafBit);
+				const float4* t = leaf_triangle(bvh, n.w);
 				if (ray_triangle<false>(t[0], t[1], t[2], r.o, r.d, r.t_min, r.t_max, unused)) { blocked = true; break; }
 			}
-			node = (hit || is_leaf) ? node + 1 : n.w;
+			node = threaded_next(node, n, hit);
 		}
 	}
 	out_blocked[index] = blocked ? 1 : 0;
@@ -163,26 +163,10 @@ __global__ void __launch_bounds__(kBlock) k_any_hits_binary(bvh_view bvh, const 
 
 // ---- the four-wide tree: a stack per lane ---------------------------------------------------------------------------
 
-// wide_ray_box() of lbvh.h, which also gives the parameter at which the ray enters the box
-__device__ static inline bool wide_ray_box_entry(uint32_t qx, uint32_t qy, uint32_t qz, const wide_ray& r, float t_min, float t_max, float& near) {
-	float nx = fmaf(__uint_as_float(__builtin_amdgcn_perm(qx, kPermMagic, r.near_x)), r.inv.x, r.shift.x);
-	float fx = fmaf(__uint_as_float(__builtin_amdgcn_perm(qx, kPermMagic, r.near_x ^ kPermFlip)), r.inv.x, r.shift.x);
-	float ny = fmaf(__uint_as_float(__builtin_amdgcn_perm(qy, kPermMagic, r.near_y)), r.inv.y, r.shift.y);
-	float fy = fmaf(__uint_as_float(__builtin_amdgcn_perm(qy, kPermMagic, r.near_y ^ kPermFlip)), r.inv.y, r.shift.y);
-	float nz = fmaf(__uint_as_float(__builtin_amdgcn_perm(qz, kPermMagic, r.near_z)), r.inv.z, r.shift.z);
-	float fz = fmaf(__uint_as_float(__builtin_amdgcn_perm(qz, kPermMagic, r.near_z ^ kPermFlip)), r.inv.z, r.shift.z);
-	near = fmaxf(fmaxf(nx, ny), fmaxf(nz, t_min));
-	float far = fminf(fminf(fx, fy), fminf(fz, t_max));
-	return near <= far;
-}
-
 // The stack of a lane: `lds_entries` links [entry][thread] in LDS (a per-lane slot never conflicts on banks), deeper ones
 // [entry][thread of the grid] in `spill`, which the host sizes from the worst case of the build
 // (acceleration_structure_t.wide_stack_need): a stack cannot outgrow it.  A link is that of a wide node: an inner
-// node's index or kLeafBit | triangle slot.
-// (LDS is addressed by 32-bit byte addresses in its own address space: through generic pointers the compiler merges the two
-// homes of an entry into one flat access)
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
+// node's index or kLeafBit | triangle slot.  (LDS through lds_u32 of lbvh.h.)
 struct lane_stack {
 	uint32_t lds_links;
 	uint32_t* spill_links;
@@ -243,18 +227,13 @@ __global__ void __launch_bounds__(kBlock) k_closest_hits_wide(bvh_view bvh, cons
 		// the root
 		uint32_t item = 0;
 		while (true) {
-			if (item & kLeafBit) test_leaf<CULL_BACK>(bvh, item & ~kLeafBit, r, best);
+			if (item & kLeafBit) test_leaf<CULL_BACK>(bvh, item, r, best);
 			else {
-				const uint4* n = (const uint4*) ((const uint8_t*) wide_nodes + ((size_t) item << 6));
-				uint4 qx = n[0], qy = n[1], qz = n[2], link = n[3];
-				const float far = widened_far(r.t_max, best.t);
-				float d0, d1, d2, d3;
-				bool h0 = wide_ray_box_entry(qx.x, qy.x, qz.x, ray, near, far, d0) || r.no_culling;
-				bool h1 = wide_ray_box_entry(qx.y, qy.y, qz.y, ray, near, far, d1) || r.no_culling;
-				bool h2 = wide_ray_box_entry(qx.z, qy.z, qz.z, ray, near, far, d2) || r.no_culling;
-				bool h3 = wide_ray_box_entry(qx.w, qy.w, qz.w, ray, near, far, d3) || r.no_culling;
+				const wide_visit v = visit_wide_node(wide_nodes, item, ray, near, widened_far(r.t_max, best.t));
+				float d0 = v.entry[0], d1 = v.entry[1], d2 = v.entry[2], d3 = v.entry[3];
 				// (an absent child cannot be hit unless NaNs let it through: its link is never pushed)
-				uint32_t l0 = h0 ? link.x : kWideEmpty, l1 = h1 ? link.y : kWideEmpty, l2 = h2 ? link.z : kWideEmpty, l3 = h3 ? link.w : kWideEmpty;
+				const bool h0 = v.hit[0] || r.no_culling, h1 = v.hit[1] || r.no_culling, h2 = v.hit[2] || r.no_culling, h3 = v.hit[3] || r.no_culling;
+				uint32_t l0 = h0 ? v.link.x : kWideEmpty, l1 = h1 ? v.link.y : kWideEmpty, l2 = h2 ? v.link.z : kWideEmpty, l3 = h3 ? v.link.w : kWideEmpty;
 				// (NaN distances of rays that are not culled order nothing, which is as good as any order)
 				const float inf = __builtin_inff();
 				d0 = (l0 != kWideEmpty) ? d0 : inf; d1 = (l1 != kWideEmpty) ? d1 : inf; d2 = (l2 != kWideEmpty) ? d2 : inf; d3 = (l3 != kWideEmpty) ? d3 : inf;
@@ -291,20 +270,15 @@ __global__ void __launch_bounds__(kBlock) k_any_hits_wide(bvh_view bvh, const ui
 		float unused;
 		while (true) {
 			if (item & kLeafBit) {
-				const float4* t = bvh.triangles + 3 * (size_t) (item & ~kLeafBit);
+				const float4* t = leaf_triangle(bvh, item);
 				if (ray_triangle<false>(t[0], t[1], t[2], r.o, r.d, r.t_min, r.t_max, unused)) { blocked = true; break; }
 			}
 			else {
-				const uint4* n = (const uint4*) ((const uint8_t*) wide_nodes + ((size_t) item << 6));
-				uint4 qx = n[0], qy = n[1], qz = n[2], link = n[3];
-				bool h0 = wide_ray_box(qx.x, qy.x, qz.x, ray, near, far) || r.no_culling;
-				bool h1 = wide_ray_box(qx.y, qy.y, qz.y, ray, near, far) || r.no_culling;
-				bool h2 = wide_ray_box(qx.z, qy.z, qz.z, ray, near, far) || r.no_culling;
-				bool h3 = wide_ray_box(qx.w, qy.w, qz.w, ray, near, far) || r.no_culling;
-				if (h3 && link.w != kWideEmpty) stack.push(link.w);
-				if (h2 && link.z != kWideEmpty) stack.push(link.z);
-				if (h1 && link.y != kWideEmpty) stack.push(link.y);
-				if (h0 && link.x != kWideEmpty) stack.push(link.x);
+				const wide_visit v = visit_wide_node(wide_nodes, item, ray, near, far);
+				if ((v.hit[3] || r.no_culling) && v.link.w != kWideEmpty) stack.push(v.link.w);
+				if ((v.hit[2] || r.no_culling) && v.link.z != kWideEmpty) stack.push(v.link.z);
+				if ((v.hit[1] || r.no_culling) && v.link.y != kWideEmpty) stack.push(v.link.y);
+				if ((v.hit[0] || r.no_culling) && v.link.x != kWideEmpty) stack.push(v.link.x);
 			}
 			if (stack.top == 0) break;
 			item = stack.pop();
@@ -314,16 +288,6 @@ __global__ void __launch_bounds__(kBlock) k_any_hits_wide(bvh_view bvh, const ui
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-
-static inline bvh_view view_of(const acceleration_structure_t* structure) {
-	bvh_view view;
-	view.nodes = (const uint4*) structure->nodes;
-	view.triangles = (const float4*) structure->triangle_vertices;
-	view.node_count = structure->node_count;
-	view.grid_origin = f3{structure->grid_origin[0], structure->grid_origin[1], structure->grid_origin[2]};
-	view.grid_inverse_cell = f3{structure->grid_inverse_cell[0], structure->grid_inverse_cell[1], structure->grid_inverse_cell[2]};
-	return view;
-}
 
 // What both calls check and decide: 0 and the walk in *walk (a ray_walk_t other than ray_walk_auto), or 1 after one line
 static int plan_query(const char* call, const scene_t* scene, const device_t* device, uint64_t count, const ray_query_options_t* options, uint32_t* walk, uint32_t* lds_entries) {
@@ -424,7 +388,7 @@ static int launch_wide(const char* call, const acceleration_structure_t* structu
 template <bool CULL_BACK>
 static int launch_closest_hits(const scene_t* scene, const device_t* device, uint32_t walk, uint32_t lds_option, const ray_t* rays, uint64_t count, ray_hit_t* out_hits, hipStream_t stream) {
 	const acceleration_structure_t* structure = &scene->acceleration_structure;
-	const bvh_view bvh = view_of(structure);
+	const bvh_view bvh = make_bvh_view(structure);
 	if (walk == ray_walk_binary) {
 		k_closest_hits_binary<CULL_BACK><<<block_count(count, kBlock), kBlock, 0, stream>>>(bvh, rays, (uint32_t) count, out_hits);
 		return hip_failed(hipGetLastError(), "trace_closest_hits");
@@ -450,7 +414,7 @@ extern "C" int trace_any_hits(const scene_t* scene, const device_t* device, cons
 	if (!count) return 0;
 	hipStream_t s = (hipStream_t) (stream ? stream : device->stream);
 	const acceleration_structure_t* structure = &scene->acceleration_structure;
-	const bvh_view bvh = view_of(structure);
+	const bvh_view bvh = make_bvh_view(structure);
 	if (walk == ray_walk_binary) {
 		k_any_hits_binary<<<block_count(count, kBlock), kBlock, 0, s>>>(bvh, rays, (uint32_t) count, out_blocked);
 		return hip_failed(hipGetLastError(), "trace_any_hits");

@@ -1,7 +1,7 @@
 // The frame pipeline behind the reference's entry points (create_shading_pass src/main.c:598, write_constants :2114,
 // the vkCmdDraw of record_render_frame_commands :1428-1434): variant selection, the wavefront buffers, frame plan, band
-// steps, and the diagnostics that replay the queued rays (wavefront_kernels.h defines non-template kernels: one unit
-// alone may include it).  The band steps with a unit of their own, and what all of them share: frame_pipeline.h.
+// steps (wavefront_kernels.h defines non-template kernels: this unit alone includes it, and launches them).  The band steps
+// with a unit of their own, and what all of them share: frame_pipeline.h.
 #include "wavefront_kernels.h"
 #include "shade_launchers.h"
 #include "frame_pipeline.h"
@@ -810,150 +810,4 @@ extern "C" int render_shading_pass_encoded(application_t* app, void* out_radianc
 		return 1;
 	}
 	return render_pass(app, out_radiance, out_rgb8);
-}
-
-// Diagnostics: replays the rays that the last frame queued and counts the work of the
-// traversal (profiles/ cites these numbers; not part of the frame).
-__global__ void __launch_bounds__(256) k_traversal_statistics(bvh_view bvh, ray_stream stream, unsigned long long* out) {
-	uint32_t queue = blockIdx.y;
-	uint32_t size = stream.sizes[queue];
-	unsigned long long visits = 0, tests = 0, blocked_rays = 0, rays = 0, wave_steps = 0;
-	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < ((size + 63u) & ~63u); i += gridDim.x * 256u) {
-		uint32_t my_visits = 0;
-		size_t slot = (size_t) queue * stream.capacity + i;
-		if (i < size && stream.records[slot] != kNullRay) {
-			float4 a = stream.origins[ray_record_thread(stream.thread_bits, stream.records[slot])], b = stream.directions[slot];
-			f3 o = mk3(a.x, a.y, a.z), d = mk3(b.x, b.y, b.z);
-			float t_max = b.w;
-			grid_ray ray = make_grid_ray(bvh, o, d);
-			uint32_t node = 0;
-			bool blocked = false;
-			++rays;
-			while (t_max >= 1.0e-3f && node < bvh.node_count && !blocked) {
-				uint4 n = bvh.nodes[node];
-				bool is_leaf = (n.w & kLeafBit) != 0;
-				bool hit = ray_box(n, ray, 1.0e-3f, t_max);
-				++my_visits;
-				if (hit && is_leaf) {
-					const float4* t = bvh.triangles + 3 * (size_t) (n.w & ~kLeafBit);
-					float dist;
-					++tests;
-					blocked = ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist);
-				}
-				node = (hit || is_leaf) ? node + 1 : n.w;
-			}
-			blocked_rays += blocked ? 1 : 0;
-		}
-		visits += my_visits;
-		// steps the wave needs for these 64 rays = longest ray
-		uint32_t longest = my_visits;
-		for (int offset = 32; offset > 0; offset >>= 1) longest = max(longest, (uint32_t) __shfl_xor((int) longest, offset));
-		if ((threadIdx.x & 63u) == 0) wave_steps += longest;
-		atomicMax(out + 5, (unsigned long long) my_visits);
-	}
-	atomicAdd(out + 0, rays); atomicAdd(out + 1, visits); atomicAdd(out + 2, tests);
-	atomicAdd(out + 3, blocked_rays); atomicAdd(out + 4, wave_steps);
-}
-
-// The same for the four-wide tree: "visits" are fetched nodes (dependent loads), out[5] the longest
-// ray's, wave steps the longest ray of each group of 64; out[6] counts tested boxes, out[7] the
-// deepest stack a ray reached, out[8] the rays whose stack outgrows the `lds_entries` entries that
-// trace_shadow_rays_wide keeps in LDS (it holds the next item on the stack too: one entry more than the
-// scheme here), out[9] the node visits of the rays that end up blocked
-__global__ void __launch_bounds__(256) k_traversal_statistics_wide(bvh_view bvh, const uint4* wide_nodes, ray_stream stream, uint32_t lds_entries, unsigned long long* out) {
-	uint32_t queue = blockIdx.y;
-	uint32_t size = stream.sizes[queue];
-	unsigned long long visits = 0, tests = 0, blocked_rays = 0, rays = 0, wave_steps = 0, boxes = 0, beyond_lds = 0, blocked_visits = 0;
-	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < ((size + 63u) & ~63u); i += gridDim.x * 256u) {
-		uint32_t my_visits = 0;
-		size_t slot = (size_t) queue * stream.capacity + i;
-		if (i < size && stream.records[slot] != kNullRay) {
-			float4 a = stream.origins[ray_record_thread(stream.thread_bits, stream.records[slot])], b = stream.directions[slot];
-			f3 o = mk3(a.x, a.y, a.z), d = mk3(b.x, b.y, b.z);
-			float t_max = b.w;
-			wide_ray ray = make_wide_ray(make_grid_ray(bvh, o, d));
-			uint32_t stack[kWideStackMax];
-			uint32_t depth = 0, deepest = 0, item = 0;
-			bool blocked = false, done = !(t_max >= 1.0e-3f);
-			++rays;
-			while (!done) {
-				if (item & kLeafBit) {
-					const float4* t = bvh.triangles + 3 * (size_t) (item & ~kLeafBit);
-					float dist;
-					++tests;
-					blocked = ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist);
-					if (blocked) break;
-					item = 0xFFFFFFFFu;
-				}
-				else {
-					const uint4* n = wide_nodes + 4 * (size_t) item;
-					uint4 qx = n[0], qy = n[1], qz = n[2], link = n[3];
-					const uint32_t x[4] = {qx.x, qx.y, qx.z, qx.w}, y[4] = {qy.x, qy.y, qy.z, qy.w}, z[4] = {qz.x, qz.y, qz.z, qz.w}, links[4] = {link.x, link.y, link.z, link.w};
-					++my_visits;
-					item = 0xFFFFFFFFu;
-					// the order of trace_shadow_rays_wide: child 0 next, then 1, 2, 3 (pushed last to first)
-					for (int c = 3; c >= 0; --c) {
-						if (links[c] == kWideEmpty) continue;
-						++boxes;
-						if (!wide_ray_box(x[c], y[c], z[c], ray, 1.0e-3f, t_max)) continue;
-						if (item != 0xFFFFFFFFu && depth < kWideStackMax) stack[depth++] = item;
-						item = links[c];
-					}
-					deepest = max(deepest, depth);
-				}
-				if (item == 0xFFFFFFFFu) {
-					if (depth == 0) done = true;
-					else item = stack[--depth];
-				}
-			}
-			blocked_rays += blocked ? 1 : 0;
-			blocked_visits += blocked ? my_visits : 0u;
-			beyond_lds += (deepest + 1u > lds_entries) ? 1 : 0;
-			atomicMax(out + 7, (unsigned long long) deepest);
-		}
-		visits += my_visits;
-		uint32_t longest = my_visits;
-		for (int offset = 32; offset > 0; offset >>= 1) longest = max(longest, (uint32_t) __shfl_xor((int) longest, offset));
-		if ((threadIdx.x & 63u) == 0) wave_steps += longest;
-		atomicMax(out + 5, (unsigned long long) my_visits);
-	}
-	atomicAdd(out + 0, rays); atomicAdd(out + 1, visits); atomicAdd(out + 2, tests);
-	atomicAdd(out + 3, blocked_rays); atomicAdd(out + 4, wave_steps); atomicAdd(out + 6, boxes);
-	if (beyond_lds) atomicAdd(out + 8, beyond_lds);
-	if (blocked_visits) atomicAdd(out + 9, blocked_visits);
-}
-
-extern "C" int get_traversal_statistics(application_t* app, uint64_t out_statistics[6]) {
-	const wavefront_buffers* w = last_launch_buffers(app);
-	if (!w || !w->ray_directions || !app->shading_pass.use_ray_tracing || app->shading_pass.inline_rays) {
-		printf("get_traversal_statistics() needs a frame rendered with wavefront shadow rays.\n");
-		return 1;
-	}
-	uint64_t all[12];
-	int failed = get_traversal_statistics_of_tree(app, app->scene.acceleration_structure.wide_nodes && !app->shading_pass.binary_traversal, all);
-	memcpy(out_statistics, all, sizeof(uint64_t) * 6);
-	return failed;
-}
-
-extern "C" int get_traversal_statistics_of_tree(application_t* app, VkBool32 wide_tree, uint64_t out_statistics[12]) {
-	const frame_pipeline* frames = (const frame_pipeline*) app->shading_pass.wavefront;
-	const wavefront_buffers* w = last_launch_buffers(app);
-	const acceleration_structure_t* structure = &app->scene.acceleration_structure;
-	if (!w || !w->ray_directions || !app->shading_pass.use_ray_tracing || app->shading_pass.inline_rays || (wide_tree && !structure->wide_nodes)) {
-		printf("get_traversal_statistics_of_tree() needs a frame rendered with wavefront shadow rays (and the tree it is asked about).\n");
-		return 1;
-	}
-	unsigned long long* counters = NULL;
-	if (hip_failed(hipMalloc(&counters, sizeof(unsigned long long) * 12), "allocating traversal counters")) return 1;
-	hipStream_t stream = (hipStream_t) app->device.stream;
-	(void) finish_frames(app);
-	(void) hipMemsetAsync(counters, 0, sizeof(unsigned long long) * 12, stream);
-	bvh_view bvh = make_bvh_view(structure);
-	// (the queues of the most recent launch - the last band of the last frame - with the sizes the resolve kernel kept)
-	ray_stream rays = {w->ray_directions, w->ray_records, w->ray_origins, w->ray_queue_size + kRayCounterCount, w->queue_capacity, w->thread_bits, w->thread_count};
-	if (wide_tree) k_traversal_statistics_wide<<<dim3(16, kRayQueueCount), 256, 0, stream>>>(bvh, (const uint4*) structure->wide_nodes, rays, frames->wide_stack_lds, counters);
-	else k_traversal_statistics<<<dim3(16, kRayQueueCount), 256, 0, stream>>>(bvh, rays, counters);
-	int failed = vkr_copy_to_host(out_statistics, counters, sizeof(uint64_t) * 12, &app->device);
-	(void) hipFree(counters);
-	return failed;
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include "shading_inputs.h"
 #include "lbvh.h"
+#include "ray_stream.h"
 
 namespace vkr {
 
@@ -17,16 +18,6 @@ constexpr uint32_t kWideTraceWaves = 8;
 constexpr uint32_t kWideRefillLanes = 16;
 // ... by a wave whose batches kept less than this share (in 1/256) of its lanes busy (VKR_WIDE_REFILL_BELOW)
 constexpr uint32_t kWideRefillBelow = 166;
-
-// What the tracing kernels read: the queues that the shading kernel filled (shade_params has the
-// same pointers, writable)
-struct ray_stream {
-	const float4* directions;   // [queue][slot]: direction, t_max
-	const uint32_t* records;    // [queue][slot]: thread | code cursor << thread_bits, or kNullRay
-	const float4* origins;      // [thread]: where all rays of that pixel start
-	const uint32_t* sizes;      // slots used per queue
-	uint32_t capacity, thread_bits, thread_count;
-};
 
 // Wave-uniform bookkeeping of the persistent tracing waves: which chunk of which queue the wave
 // works on.  Queues 64 x ... 64 x + 63 are served only by workgroups that run on XCD x (workgroup b
@@ -143,11 +134,11 @@ __global__ void __launch_bounds__(256) trace_shadow_rays(bvh_view bvh, ray_strea
 				bool hit = ray_box(n, ray, 1.0e-3f, t_max);
 				bool blocked = false;
 				if (hit && is_leaf) {
-					const float4* t = bvh.triangles + 3 * (size_t) (n.w & ~kLeafBit);
+					const float4* t = leaf_triangle(bvh, n.w);
 					float dist;
 					blocked = ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist);
 				}
-				node = (hit || is_leaf) ? node + 1 : n.w;
+				node = threaded_next(node, n, hit);
 				if (!blocked && node >= end) codes[code_index] = (uint8_t) kCodeVisible;
 				if (blocked || node >= end) node = kIdle;
 			}
@@ -157,7 +148,7 @@ __global__ void __launch_bounds__(256) trace_shadow_rays(bvh_view bvh, ray_strea
 }
 
 // The same persistent scheme on the four-wide tree (lbvh.h "wide BVH"): a visit fetches one
-// 64-byte node and tests its four boxes (wide_ray_box: 6 v_perm_b32, 6 FMAs, 2 x min3 / max3, one
+// 64-byte node and tests its four boxes (visit_wide_node: 6 v_perm_b32, 6 FMAs, 2 x min3 / max3, one
 // compare per box, no branches - an absent child has a box that cannot be hit).  All children that
 // were hit go to the lane's stack and the top one is taken off again: kWideStackLds entries in LDS,
 // [entry][thread], written without a condition (the cursor only advances for a hit), which needs
@@ -216,8 +207,7 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 	// The stack pointer is the lane's LDS address itself (entries are THREADS x 4 bytes apart), so
 	// that a push is a store and a conditional add; entries beyond the LDS part only exist as a
 	// depth (`top` then points behind the LDS part and is never dereferenced)
-	// (as 32-bit LDS byte addresses: generic pointers make the compiler do the arithmetic in 64 bits)
-	typedef __attribute__((address_space(3))) uint32_t lds_u32;
+	// (as 32-bit LDS byte addresses, lds_u32 of lbvh.h)
 	constexpr uint32_t kEntry = THREADS * 4u;
 	const uint32_t my_stack = (uint32_t) (uintptr_t) (lds_u32*) (stack + threadIdx.x);
 	// (lds_entries <= kWideStackLds: tests shrink the LDS part to drive rays through the spill path)
@@ -248,27 +238,21 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 	auto walk_step = [&](bool at_node, bool at_leaf, uint64_t node_lanes, uint64_t leaf_lanes) {
 		bool pop = false;
 		if (at_node) {
-			const uint4* n = (const uint4*) ((const uint8_t*) wide_nodes + ((size_t) item << 6));
-			uint4 qx = n[0], qy = n[1], qz = n[2], link = n[3];
-			bool h0 = wide_ray_box(qx.x, qy.x, qz.x, ray, 1.0e-3f, t_max);
-			bool h1 = wide_ray_box(qx.y, qy.y, qz.y, ray, 1.0e-3f, t_max);
-			bool h2 = wide_ray_box(qx.z, qy.z, qz.z, ray, 1.0e-3f, t_max);
-			bool h3 = wide_ray_box(qx.w, qy.w, qz.w, ray, 1.0e-3f, t_max);
+			const wide_visit v = visit_wide_node(wide_nodes, item, ray, 1.0e-3f, t_max);
 			if (top + 4u * kEntry <= lds_end) {
 				// (the last child first: the first one comes off the stack first, the order of
 				// the scheme with a register for the next item)
-				VKR_STACK_AT(top) = link.w; top += h3 ? kEntry : 0u;
-				VKR_STACK_AT(top) = link.z; top += h2 ? kEntry : 0u;
-				VKR_STACK_AT(top) = link.y; top += h1 ? kEntry : 0u;
-				VKR_STACK_AT(top) = link.x; top += h0 ? kEntry : 0u;
+				VKR_STACK_AT(top) = v.link.w; top += v.hit[3] ? kEntry : 0u;
+				VKR_STACK_AT(top) = v.link.z; top += v.hit[2] ? kEntry : 0u;
+				VKR_STACK_AT(top) = v.link.y; top += v.hit[1] ? kEntry : 0u;
+				VKR_STACK_AT(top) = v.link.x; top += v.hit[0] ? kEntry : 0u;
 			}
 			else {
-				const bool hits[4] = {h3, h2, h1, h0};
-				const uint32_t links[4] = {link.w, link.z, link.y, link.x};
+				const uint32_t links[4] = {v.link.x, v.link.y, v.link.z, v.link.w};
 #pragma unroll
-				for (int c = 0; c != 4; ++c) {
+				for (int c = 3; c >= 0; --c) {
 					// (an absent child cannot be hit - unless a NaN slab let it through: never push its link, which is kIdle)
-					if (!hits[c] || links[c] == kWideEmpty) continue;
+					if (!v.hit[c] || links[c] == kWideEmpty) continue;
 					if (top < lds_end) VKR_STACK_AT(top) = links[c];
 					else my_spill[(size_t) ((top - lds_end) / kEntry) * spill_stride] = links[c];
 					top += kEntry;
@@ -278,7 +262,7 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 		}
 		bool test_leaves = leaf_lanes != 0 && (node_lanes == 0 || (uint32_t) __popcll((unsigned long long) leaf_lanes) >= leaf_batch);
 		if (test_leaves && at_leaf) {
-			const float4* t = bvh.triangles + 3 * (size_t) (item & ~kLeafBit);
+			const float4* t = leaf_triangle(bvh, item);
 			float dist;
 			bool blocked = ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist);
 			// a blocked ray is done: its term keeps the code the shading kernel gave it
@@ -304,7 +288,7 @@ __global__ void __launch_bounds__(THREADS, kWideTraceWaves) trace_shadow_rays_wi
 	// result of the query is the same boolean), a miss costs one triangle test next to the 6 - 22 node fetches of a walk.
 	auto try_last_blocker = [&]() {
 		if (item == 0u && last_blocker != kIdle) {
-			const float4* t = bvh.triangles + 3 * (size_t) last_blocker;
+			const float4* t = leaf_triangle(bvh, last_blocker);
 			float dist;
 			if (ray_triangle<false>(t[0], t[1], t[2], o, d, 1.0e-3f, t_max, dist)) item = kIdle;
 		}
