@@ -1,0 +1,75 @@
+/* Feature buffers: the shading inputs of every pixel as device images - what a deferred renderer calls its G-buffer.
+ *
+ * The pass reconstructs position, shading normal, outgoing direction, diffuse albedo, Fresnel F0 and roughness of the
+ * surface behind each pixel (get_shading_data, reference shading_pass.frag.glsl:721-822) and shades from them.
+ * render_feature_buffers() writes those values out instead: guides for denoisers and temporal accumulation, keys to
+ * split per-pixel statistics by, inputs of diagnostic tools.  No reference counterpart (the reference never leaves its
+ * fragment shader with them).
+ *
+ * Every feature is one 16-byte pixel in the layout of the radiance target (row-major, width * height pixels), so each image
+ * goes as it is to encode_hdr*(), begin_read_back(), the frame statistics and sum_squared_differences().
+ *
+ * Covered pixels.  Position, normal, outgoing, albedo, F0, roughness and lambert_outgoing are the members of the shading
+ * data of (primitive, pixel ray), the pixel ray built as the material resolve of the pass builds it; for a textured scene the
+ * material textures are sampled in the same kernel.  Nothing of this is new arithmetic: in the libm and the polynomial
+ * arithmetic mode the values equal the CPU oracle's (oracle_shading_data(), math mode 0 and 1) in every bit.
+ *
+ * Pixels with nothing visible (primitive 0xFFFFFFFF) get sixteen zero bytes in every float image and
+ * {0xFFFFFFFF, 0xFFFFFFFF, x, y} in the identity image.
+ *
+ * Derived values.  In the libm and the polynomial mode they are binary32 with every operation rounded on its own (nothing
+ * contracted); a / b and sqrt are the correctly rounded ones of the kernels (csrc/device_math.h divide(), square_root()).
+ *     distance = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z), d = camera_position_world_space - position
+ *     material index = material_indices[primitive], widened
+ *     reprojection, with M = reprojection_matrix (row-major, as world_to_projection_space in the constants), P = position:
+ *         c_i = ((M[i][0] * P.x + M[i][1] * P.y) + M[i][2] * P.z) + M[i][3]          for i = 0, 1, 3
+ *         X = (c_0 / c_3 + 1) * (0.5f * width) - 0.5f,  Y = (c_1 / c_3 + 1) * (0.5f * height) - 0.5f
+ *       X, Y are pixel indices: pixel p has its centre at NDC (2 p + 1) / extent - 1, the convention of write_constants().
+ *       The pixel is {X, Y, c_3, inside}; inside = 1.0f if c_3 > 0, X >= -0.5, X < width - 0.5, Y >= -0.5 and
+ *       Y < height - 0.5 (a NaN fails every comparison), else 0.0f.  The reprojection sees the camera only, not moving geometry.
+ *
+ * Previews.  encode_feature_preview() turns a feature image into width * height RGBA8 pixels that encode_png*() and
+ * encode_jpeg*() take as they are; alpha is 255.  u8(x): clamp to [0, 1], x * 255 + 0.5, truncate; a NaN gives 0.
+ *     normal, outgoing            u8(v * 0.5f + 0.5f) per component
+ *     diffuse_albedo, fresnel_0   the sRGB8 code of encode_output() per component, no exposure applied
+ *     position                    u8((distance - range_low) / (range_high - range_low)) as grey
+ *     reprojection                red u8(((X - x) + range_high) / (2 * range_high)), green likewise with Y and y, blue u8(inside)
+ *     identity                    h = primitive * 2654435761u (mod 2^32): bytes h, h >> 8, h >> 16; nothing visible is black
+ * vulkan_renderer_amd/feature_buffers.py restates all of it in numpy, byte for byte. */
+#ifndef VKR_FEATURE_BUFFERS_H
+#define VKR_FEATURE_BUFFERS_H
+#include "vkr_shading_pass.h"
+
+typedef enum pixel_feature_e {
+	pixel_feature_position,        /* RGBA32F: position.xyz, distance */
+	pixel_feature_normal,          /* RGBA32F: shading normal.xyz (unit, after normal map and the 1e-3 offset), lambert_outgoing */
+	pixel_feature_outgoing,        /* RGBA32F: outgoing.xyz (unit), 1 */
+	pixel_feature_diffuse_albedo,  /* RGBA32F: diffuse_albedo.rgb, roughness (after roughness_factor and the clamp) */
+	pixel_feature_fresnel_0,       /* RGBA32F: fresnel_0.rgb, 1 */
+	pixel_feature_identity,        /* RGBA32UI: primitive, material index, x, y */
+	pixel_feature_reprojection,    /* RGBA32F: pixel coordinates under another camera, clip w, inside flag */
+	pixel_feature_count
+} pixel_feature_t;
+
+typedef struct feature_buffers_s {
+	/*! device pointers, NULL = not wanted; width * height * 16 bytes each, row-major, 16-byte aligned */
+	void* images[pixel_feature_count];
+	/*! a world_to_projection_space, e.g. the previous frame's; read only if that image is wanted */
+	float reprojection_matrix[4][4];
+} feature_buffers_t;
+
+/*! Writes the wanted feature images of the frame that render_shading_pass() would shade now: app's camera, settings, scene
+	and render_targets.visibility_buffer.  The kernel is queued on app->device.stream; the call uploads the constants
+	itself, so it needs a created shading pass but no rendered frame, and it reads inputs of the pass only: frames in flight
+	are not waited for.  One rank and the whole frame only.  Returns 0 on success; 1 after printing one line, with nothing
+	written, without a pass or targets, with no image wanted or a misaligned pointer, with tile_schedule.rank_count > 1
+	or a slab layout. */
+VKR_API int render_feature_buffers(application_t* app, const feature_buffers_t* buffers);
+/*! Queues, on app->device.stream, the preview of `image` (device, a feature image of app's extent of kind `feature`, a
+	pixel_feature_t) into out_rgba8 (device, width * height * 4 bytes, 4-byte aligned).  range_low, range_high: used by
+	position and reprojection.  Returns 0 on success; 1 after printing one line, with nothing written, for a missing or
+	misaligned pointer, a feature that is no pixel_feature_t and, for the features that use the range, range_high <=
+	range_low or a NaN in either. */
+VKR_API int encode_feature_preview(application_t* app, uint32_t feature, const void* image, void* out_rgba8, float range_low, float range_high);
+
+#endif

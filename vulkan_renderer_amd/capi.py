@@ -262,6 +262,14 @@ class SceneUpdateReport(C.Structure):
                 ("cost", C.c_double), ("built_cost", C.c_double)]
 
 
+# pixel_feature_t of include/vkr_feature_buffers.h, in its order
+PIXEL_FEATURES = ("position", "normal", "outgoing", "diffuse_albedo", "fresnel_0", "identity", "reprojection")
+
+
+class FeatureBuffers(C.Structure):
+    _fields_ = [("images", C.c_void_p * len(PIXEL_FEATURES)), ("reprojection_matrix", (C.c_float * 4) * 4)]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -428,6 +436,8 @@ SIGNATURES = {
     "write_png_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64]),
     "probe_png_stream": (C.c_int, [P(Device), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
     "take_png_screenshot": (C.c_int, [P(Application), C.c_char_p]),
+    "render_feature_buffers": (C.c_int, [P(Application), P(FeatureBuffers)]),
+    "encode_feature_preview": (C.c_int, [P(Application), C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
     "update_scene_geometry": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_void_p, P(SceneUpdateOptions), P(SceneUpdateReport)]),
 }
 

@@ -3,7 +3,8 @@
 // device code, so the table, the kernel that fills it and every kernel that reads it live in this one unit.
 // Compiled in exact mode (-ffp-contract=off): srgb_code_by_powf restates the oracle operation for operation.
 #include "pass_internal.h"
-#include "device_math.h"  // gclamp, gm_powf
+#include "device_math.h"  // gclamp, gm_powf, divide
+#include "vkr_feature_buffers.h"  // pixel_feature_t of k_feature_preview
 #include <hip/hip_fp16.h>
 
 using namespace vkr;
@@ -127,6 +128,52 @@ static void launch_encode(const void* radiance, void* encoded, uint64_t pixel_co
 
 void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream) {
 	k_encode_output_rgb8<<<(uint32_t) ((pixel_count / 4 + 255) / 256), 256, 0, stream>>>((const float4*) radiance, (uint32_t*) packed, pixel_count / 4, frame_bits, output_linear_rgb);
+}
+
+// The previews of the feature images (include/vkr_feature_buffers.h "Previews"): one lane per pixel, integer and binary32
+// only, nothing contracted; vulkan_renderer_amd/feature_buffers.py restates every line in numpy.
+// u8() of the header: the clamp spelled out so that a NaN gives 0 by a comparison, not by the conversion
+__device__ __forceinline__ uint32_t preview_unorm8(float v) {
+	v = (v > 0.0f) ? gmin(v, 1.0f) : 0.0f;
+	return (uint32_t) (v * 255.0f + 0.5f);
+}
+
+__global__ void __launch_bounds__(256) k_feature_preview(uint32_t feature, const uint4* image, uint32_t* out_rgba8, uint32_t width, uint32_t height, float range_low, float range_high) {
+	uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= (uint64_t) width * height) return;
+	const uint4 bits = image[i];
+	const float x = __uint_as_float(bits.x), y = __uint_as_float(bits.y), z = __uint_as_float(bits.z), w = __uint_as_float(bits.w);
+	uint32_t r, g, b;
+	switch (feature) {
+	case pixel_feature_normal: case pixel_feature_outgoing:
+		r = preview_unorm8(x * 0.5f + 0.5f); g = preview_unorm8(y * 0.5f + 0.5f); b = preview_unorm8(z * 0.5f + 0.5f);
+		break;
+	case pixel_feature_diffuse_albedo: case pixel_feature_fresnel_0:
+		r = srgb_code(x); g = srgb_code(y); b = srgb_code(z);
+		break;
+	case pixel_feature_position:
+		r = g = b = preview_unorm8(divide(w - range_low, range_high - range_low));
+		break;
+	case pixel_feature_reprojection: {
+		float px = (float) (uint32_t) (i % width), py = (float) (uint32_t) (i / width);
+		r = preview_unorm8(divide((x - px) + range_high, 2.0f * range_high));
+		g = preview_unorm8(divide((y - py) + range_high, 2.0f * range_high));
+		b = preview_unorm8(w);
+		break;
+	}
+	default: {  // pixel_feature_identity
+		uint32_t h = bits.x * 2654435761u;
+		if (bits.x == 0xFFFFFFFFu) h = 0u;
+		r = h & 255u; g = (h >> 8) & 255u; b = (h >> 16) & 255u;
+		break;
+	}
+	}
+	out_rgba8[i] = r | (g << 8) | (b << 16) | 0xFF000000u;
+}
+
+void launch_feature_preview(uint32_t feature, const void* image, void* out_rgba8, uint32_t width, uint32_t height, float range_low, float range_high, hipStream_t stream) {
+	uint64_t pixel_count = (uint64_t) width * height;
+	k_feature_preview<<<(uint32_t) ((pixel_count + 255) / 256), 256, 0, stream>>>(feature, (const uint4*) image, (uint32_t*) out_rgba8, width, height, range_low, range_high);
 }
 
 extern "C" int encode_output(application_t* app, VkBool32 output_linear_rgb) {

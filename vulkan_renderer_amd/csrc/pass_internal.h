@@ -20,3 +20,6 @@ uint64_t slab_tiling(const application_t* app, uint32_t rank, vkr::shade_params&
 // ---- output_encoding.hip ----
 // queues the kernel that encodes pixel_count pixels (a multiple of four) as packed RGB8
 void launch_encode_rgb8(const void* radiance, void* packed, uint64_t pixel_count, uint32_t frame_bits, int output_linear_rgb, hipStream_t stream);
+// queues the kernel that turns a feature image (a pixel_feature_t of include/vkr_feature_buffers.h) into RGBA8: it lives
+// beside the sRGB code that two of the previews are
+void launch_feature_preview(uint32_t feature, const void* image, void* out_rgba8, uint32_t width, uint32_t height, float range_low, float range_high, hipStream_t stream);

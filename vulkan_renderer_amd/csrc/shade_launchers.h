@@ -34,5 +34,9 @@ extern "C" int vkr_launch_sector_terms_exact(int capacity, const void* prepared,
 VKR_DECLARE_MODE_LAUNCHES(error_launch_function_t, vkr_launch_error_display, int combined_path, int technique, int capacity, int error_mode, const vkr::shade_params* p, unsigned int grid_x, void* stream)
 VKR_DECLARE_MODE_LAUNCHES(resolve_launch_function_t, vkr_launch_resolve_materials, const vkr::shade_params* p, float* pixel_materials, void* stream)
 VKR_DECLARE_MODE_LAUNCHES(sampler_launch_function_t, vkr_launch_texture_sampler, const vkr::shade_params* p, const uint32_t descriptor[4], const float* inputs, float* out_rgba, uint32_t count, void* stream)
+// k_feature_buffers (feature_buffers_variants.hip; include/vkr_feature_buffers.h): images: pixel_feature_count device
+// pointers, NULL = not wanted; reprojection: the sixteen floats of the caller's matrix, row-major; textured: sample the
+// material textures in the kernel (p->texture_descriptors, texels, srgb_table set)
+VKR_DECLARE_MODE_LAUNCHES(feature_launch_function_t, vkr_launch_feature_buffers, const vkr::shade_params* p, void* const* images, const float* reprojection, int textured, void* stream)
 // [arithmetic_mode_t]
 #define VKR_MODE_LAUNCHERS(name) {name##_libm, name##_fast, name##_exact}

@@ -635,6 +635,92 @@ class Renderer(HostScene):
             raise RuntimeError("read_back_visibility failed")
         return out
 
+    # -- feature buffers (include/vkr_feature_buffers.h) -----------------------------------
+    def render_features(self, names, reprojection_matrix=None, pointers=None):
+        """The feature images of the current frame (render_feature_buffers): names out of capi.PIXEL_FEATURES;
+        reprojection_matrix: a (4, 4) world_to_projection_space for "reprojection" (default: this frame's own).
+        -> {name: array (height, width, 4)}, float32 or, for "identity", uint32.  With pointers, {name: device address}
+        for every name, the images stay on the device, the call returns once the kernel is queued and gives nothing."""
+        from . import feature_buffers
+        names = [names] if isinstance(names, str) else list(names)
+        buffers = capi.FeatureBuffers()
+        if reprojection_matrix is None:
+            reprojection_matrix = feature_buffers.world_to_projection_space(self.constants())
+        matrix = np.ascontiguousarray(reprojection_matrix, np.float32).reshape(4, 4)
+        for i in range(4):
+            buffers.reprojection_matrix[i][:] = [float(v) for v in matrix[i]]
+        e = self.app.swapchain.extent
+        nbytes = e.width * e.height * 16
+        hip, owned = _hip_runtime(), {}
+        try:
+            for name in names:
+                index = capi.PIXEL_FEATURES.index(name)
+                if pointers is not None:
+                    buffers.images[index] = int(pointers[name])
+                    continue
+                address = C.c_void_p()
+                if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
+                    raise RuntimeError("no device memory for the %s image" % name)
+                owned[name] = address
+                buffers.images[index] = address.value
+            if self.lib.render_feature_buffers(C.byref(self.app), C.byref(buffers)):
+                raise RuntimeError("render_feature_buffers failed")
+            if pointers is not None:
+                return None
+            self.sync()
+            images = {}
+            for name, address in owned.items():
+                image = np.zeros((e.height, e.width, 4), np.uint32 if name == "identity" else np.float32)
+                if hip.hipMemcpy(image.ctypes.data, address, nbytes, 2):
+                    raise RuntimeError("reading the %s image back failed" % name)
+                images[name] = image
+            return images
+        finally:
+            if owned:
+                self.sync()
+            for address in owned.values():
+                hip.hipFree(address)
+
+    def feature_preview(self, name, image_or_pointer, range=(0.0, 1.0), out_pointer=None):
+        """The RGBA8 preview of a feature image (encode_feature_preview) - an array as render_features() returns it, which
+        is uploaded, or a device address.  range: (low, high) for "position" (distances) and "reprojection" (high: the
+        motion in pixels that saturates).  -> uint8 array (height, width, 4); with out_pointer, a device address, the
+        preview stays there (for encode_png() / encode_jpeg()) and the call returns once the kernel is queued."""
+        e = self.app.swapchain.extent
+        hip, owned = _hip_runtime(), []
+
+        def allocate(nbytes):
+            address = C.c_void_p()
+            if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
+                raise RuntimeError("no device memory for the preview")
+            owned.append(address)
+            return address.value
+        try:
+            source = image_or_pointer
+            if isinstance(image_or_pointer, np.ndarray):
+                image = np.ascontiguousarray(image_or_pointer)
+                if image.shape != (e.height, e.width, 4) or image.dtype.itemsize != 4:
+                    raise ValueError("a feature image is (height, width, 4) of 32-bit values")
+                source = allocate(image.nbytes)
+                if hip.hipMemcpy(source, image.ctypes.data, image.nbytes, 1):
+                    raise RuntimeError("uploading the feature image failed")
+            target = out_pointer if out_pointer is not None else allocate(e.width * e.height * 4)
+            feature = capi.PIXEL_FEATURES.index(name) if isinstance(name, str) else int(name)
+            if self.lib.encode_feature_preview(C.byref(self.app), feature, source, target, float(range[0]), float(range[1])):
+                raise RuntimeError("encode_feature_preview failed")
+            if out_pointer is not None:
+                return None
+            self.sync()
+            out = np.zeros((e.height, e.width, 4), np.uint8)
+            if hip.hipMemcpy(out.ctypes.data, target, out.nbytes, 2):
+                raise RuntimeError("reading the preview back failed")
+            return out
+        finally:
+            if owned:
+                self.sync()
+            for address in owned:
+                hip.hipFree(address)
+
     # -- ray queries (include/vkr_ray_queries.h) ------------------------------------------
     def _trace(self, closest, origins, directions, t_min, t_max, cull_back_faces, walk, lds_stack_entries, rays_pointer, out_pointer, count, stream):
         """Both ray queries.  Host arrays are uploaded and the answers read back (a blocking call); with rays_pointer and
