@@ -270,6 +270,25 @@ class FeatureBuffers(C.Structure):
     _fields_ = [("images", C.c_void_p * len(PIXEL_FEATURES)), ("reprojection_matrix", (C.c_float * 4) * 4)]
 
 
+# include/vkr_frame_filter.h
+FRAME_FILTER_MAX_ITERATIONS, FRAME_FILTER_MAX_NORMAL_SQUARINGS, FRAME_FILTER_MAX_EXTENT = 5, 8, 32768
+
+
+class FrameFilterSettings(C.Structure):
+    _fields_ = [("iteration_count", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_luminance", C.c_float),
+                ("sigma_depth", C.c_float), ("variance_scale", C.c_float)]
+
+
+class FrameFilterImages(C.Structure):
+    _fields_ = [("colour", C.c_void_p), ("variance", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p),
+                ("modulation", C.c_void_p), ("out_colour", C.c_void_p), ("out_variance", C.c_void_p)]
+
+
+class FrameFilter(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("colour_scratch", C.c_void_p * 2), ("variance_scratch", C.c_void_p * 2),
+                ("filtered", C.c_void_p)]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -438,6 +457,9 @@ SIGNATURES = {
     "take_png_screenshot": (C.c_int, [P(Application), C.c_char_p]),
     "render_feature_buffers": (C.c_int, [P(Application), P(FeatureBuffers)]),
     "encode_feature_preview": (C.c_int, [P(Application), C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
+    "create_frame_filter": (C.c_int, [P(FrameFilter), P(Application), C.c_uint32, C.c_uint32]),
+    "destroy_frame_filter": (None, [P(FrameFilter), P(Application)]),
+    "filter_frame": (C.c_int, [P(FrameFilter), P(Application), P(FrameFilterSettings), P(FrameFilterImages)]),
     "update_scene_geometry": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_void_p, P(SceneUpdateOptions), P(SceneUpdateReport)]),
 }
 

@@ -1,0 +1,271 @@
+"""The frame filter of include/vkr_frame_filter.h restated in numpy, operation for operation in binary32: what
+filter_frame() writes, in every bit.  Vectorised over the frame: an iteration is 25 shifted views of its inputs.  And the
+command line that renders, accumulates and filters a frame of a dataset on the device."""
+import numpy as np
+
+f32 = np.float32
+MAX_ITERATIONS, MAX_NORMAL_SQUARINGS = 5, 8
+KERNEL = (f32(0.375), f32(0.25), f32(0.0625))
+DEFAULT_SETTINGS = dict(iteration_count=5, normal_squarings=7, sigma_luminance=4.0, sigma_depth=0.02, variance_scale=1.0)
+# why a tap adds nothing, in the order in which the rule decides it
+SKIP_REASONS = ("out_of_frame", "uncovered", "normal_weight", "exponent", "weight")
+
+
+def fma32(a, b, c):
+    """fmaf for float32 arrays: the product is exact in float64, the sum is rounded to odd there, so that the rounding to
+    float32 is the only one that matters (scene_update._fma32, vectorised)"""
+    a, b, c = np.asarray(a, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64)
+    with np.errstate(all="ignore"):
+        p = a * b
+        s = p + c
+        t = s - p
+        error = (p - (s - t)) + (c - t)
+        even = (np.ascontiguousarray(s).view(np.uint64) & np.uint64(1)) == 0
+        odd = np.nextafter(s, np.where(error > 0, np.inf, -np.inf))
+        s = np.where((error != 0) & np.isfinite(s) & even, odd, s)
+        return s.astype(f32)
+
+
+def exp2_poly(t):
+    """exp2_poly() of csrc/device_math.h (vkr_exp2f of oracle/oracle_math.h) for float32 t in [-126, 127]"""
+    t = np.asarray(t, f32)
+    n = np.rint(t)
+    r = (t - n) * f32(0.693147182)
+    p = np.full(t.shape, 1.98412698e-04, f32)
+    for coefficient in (1.38888892e-03, 8.33333377e-03, 4.16666679e-02, 1.66666672e-01, 0.5, 1.0, 1.0):
+        p = fma32(p, r, f32(coefficient))
+    scale = ((n.astype(np.int32) + 127).astype(np.uint32) << np.uint32(23)).view(f32)
+    return p * scale
+
+
+def gmax(x, y):
+    """gmax() of csrc/device_math.h: x < y ? y : x"""
+    return np.where(x < y, y, x)
+
+
+def dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def luminance(c):
+    return (f32(0.2126) * c[..., 0] + f32(0.7152) * c[..., 1]) + f32(0.0722) * c[..., 2]
+
+
+def shifted(image, dx, dy):
+    """-> (view, inside): view[y, x] = image[y + dy, x + dx] where that pixel is in the frame (inside), zeros elsewhere"""
+    height, width = image.shape[:2]
+    out = np.zeros_like(image)
+    inside = np.zeros((height, width), bool)
+    x0, x1, y0, y1 = max(0, -dx), min(width, width - dx), max(0, -dy), min(height, height - dy)
+    if x0 < x1 and y0 < y1:
+        out[y0:y1, x0:x1] = image[y0 + dy:y1 + dy, x0 + dx:x1 + dx]
+        inside[y0:y1, x0:x1] = True
+    return out, inside
+
+
+def check_settings(settings):
+    s = dict(DEFAULT_SETTINGS, **settings)
+    if not (1 <= int(s["iteration_count"]) <= MAX_ITERATIONS and 0 <= int(s["normal_squarings"]) <= MAX_NORMAL_SQUARINGS):
+        raise ValueError("1 to %d iterations, 0 to %d squarings" % (MAX_ITERATIONS, MAX_NORMAL_SQUARINGS))
+    for name, low_allowed in (("sigma_luminance", False), ("sigma_depth", False), ("variance_scale", True)):
+        value = f32(s[name])
+        if not (np.isfinite(value) and (value >= 0 if low_allowed else value > 0)):
+            raise ValueError("%s = %r" % (name, s[name]))
+    return s
+
+
+def iteration(c, v, position, normal, covered, step, settings, diagnostics=None):
+    """See _iteration(); the flags that numpy raises at pixels that are not covered are ignored"""
+    with np.errstate(all="ignore"):
+        return _iteration(c, v, position, normal, covered, step, settings, diagnostics)
+
+
+def _iteration(c, v, position, normal, covered, step, settings, diagnostics):
+    """One iteration of the header at step `step`: c, v (height, width, 3) float32 (v None: no variance image) ->
+    (c', v').  Values at pixels that are not covered are meaningless.  diagnostics: a dict that gets, per SKIP_REASONS, the
+    number of taps skipped for it, "denormal_weights" and "centre_only" (covered pixels whose only tap is the centre)."""
+    height, width = covered.shape
+    sigma_luminance, sigma_depth = f32(settings["sigma_luminance"]), f32(settings["sigma_depth"])
+    n_p, P_p = normal[..., :3], position[..., :3]
+    l_p = luminance(c)
+    if v is not None:
+        sum_gv, sum_g = np.zeros((height, width, 3), f32), np.zeros((height, width), f32)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                g = f32((0.5 if dx == 0 else 0.25) * (0.5 if dy == 0 else 0.25))
+                v_q, inside = shifted(v, dx, dy)
+                valid = inside & shifted(covered, dx, dy)[0]
+                sum_gv = np.where(valid[..., None], sum_gv + g * v_q, sum_gv)
+                sum_g = np.where(valid, sum_g + g, sum_g)
+        vbar = sum_gv / sum_g[..., None]
+        d_l = sigma_luminance * luminance(np.sqrt(vbar)) + f32(1.0e-8)
+    d_z = sigma_depth * position[..., 3]
+    sum_c, sum_v, sum_w = np.zeros((height, width, 3), f32), np.zeros((height, width, 3), f32), np.zeros((height, width), f32)
+    tap_count = np.zeros((height, width), np.int32)
+    counts = dict.fromkeys(SKIP_REASONS, 0)
+    denormal_weights = 0
+    for dy in (-2, -1, 0, 1, 2):
+        for dx in (-2, -1, 0, 1, 2):
+            h = KERNEL[abs(dx)] * KERNEL[abs(dy)]
+            c_q, inside = shifted(c, dx * step, dy * step)
+            covered_q = shifted(covered, dx * step, dy * step)[0]
+            valid = inside & covered_q
+            if dx == 0 and dy == 0:
+                w = np.full((height, width), h, f32)
+            else:
+                n_q, P_q = shifted(normal, dx * step, dy * step)[0][..., :3], shifted(position, dx * step, dy * step)[0][..., :3]
+                w_n = gmax(f32(0.0), dot3(n_p, n_q))
+                for _ in range(int(settings["normal_squarings"])):
+                    w_n = w_n * w_n
+                hn = h * w_n
+                e = np.abs(dot3(n_p, P_q - P_p)) / d_z
+                if v is not None:
+                    e = e + np.abs(luminance(c_q) - l_p) / d_l
+                t = -e * f32(1.44269502)
+                in_range = t >= f32(-126.0)
+                w_e = np.where(in_range, exp2_poly(np.where(in_range, t, f32(0.0))), f32(0.0))
+                w = hn * w_e
+                has_normal_weight = hn > 0
+                taken = valid & (w > 0)
+                here = covered
+                counts["out_of_frame"] += int((here & ~inside).sum())
+                counts["uncovered"] += int((here & inside & ~covered_q).sum())
+                counts["normal_weight"] += int((here & valid & ~has_normal_weight).sum())
+                counts["exponent"] += int((here & valid & has_normal_weight & ~in_range).sum())
+                counts["weight"] += int((here & valid & has_normal_weight & in_range & ~(w > 0)).sum())
+                denormal_weights += int((here & taken & (w < f32(2.0 ** -126))).sum())
+                valid = taken
+            tap_count += valid
+            sum_c = np.where(valid[..., None], sum_c + w[..., None] * c_q, sum_c)
+            if v is not None:
+                v_q = shifted(v, dx * step, dy * step)[0]
+                sum_v = np.where(valid[..., None], sum_v + (w * w)[..., None] * v_q, sum_v)
+            sum_w = np.where(valid, sum_w + w, sum_w)
+    if diagnostics is not None:
+        diagnostics.update(counts, denormal_weights=denormal_weights, centre_only=int((covered & (tap_count == 1)).sum()))
+    c_out = sum_c / sum_w[..., None]
+    v_out = None if v is None else sum_v / (sum_w * sum_w)[..., None]
+    return c_out, v_out
+
+
+def filter_frame(colour, variance, position, normal, modulation=None, settings=None, want_variance=True, diagnostics=None):
+    """filter_frame() of include/vkr_frame_filter.h on float32 images (height, width, 4); variance and modulation may be
+    None.  -> (out_colour, out_variance); out_variance is None without a variance image or with want_variance False.
+    diagnostics: a list that gets one dict per iteration (see iteration())."""
+    settings = check_settings(settings or {})
+    colour, position, normal = (np.ascontiguousarray(a, f32) for a in (colour, position, normal))
+    if colour.ndim != 3 or colour.shape[2] != 4 or position.shape != colour.shape or normal.shape != colour.shape:
+        raise ValueError("images are (height, width, 4)")
+    with np.errstate(all="ignore"):
+        covered = position[..., 3] > 0
+        c = colour[..., :3]
+        v = None
+        if variance is not None:
+            variance = np.ascontiguousarray(variance, f32)
+            v = variance[..., :3] * f32(settings["variance_scale"])
+        m = None
+        if modulation is not None:
+            m = gmax(np.ascontiguousarray(modulation, f32)[..., :3], f32(1.0 / 256.0))
+            c = c / m
+            if v is not None:
+                v = v / (m * m)
+        for i in range(int(settings["iteration_count"])):
+            record = {} if diagnostics is not None else None
+            c, v = iteration(c, v, position, normal, covered, 1 << i, settings, record)
+            if diagnostics is not None:
+                diagnostics.append(record)
+        if m is not None:
+            c = c * m
+            if v is not None:
+                v = v * (m * m)
+    out_colour = colour.copy()
+    out_colour[..., :3][covered] = c[covered]
+    out_variance = None
+    if v is not None and want_variance:
+        out_variance = variance.copy()
+        out_variance[covered] = np.concatenate([v, np.ones(v.shape[:2] + (1,), f32)], axis=-1)[covered]
+    return out_colour, out_variance
+
+
+# ---- command line -------------------------------------------------------------------------------------------------
+
+def main(arguments=None):
+    import argparse
+    import ctypes as C
+    import os
+
+    from . import renderer as R
+    parser = argparse.ArgumentParser(prog="python -m vulkan_renderer_amd.frame_filter",
+                                     description="Renders frames of a dataset with animated noise, accumulates them, filters their mean on the device and writes the noisy and the filtered image.")
+    parser.add_argument("dataset", help="directory of a dataset (scene.vks, LTC tables), as bench.py and the tests write it")
+    parser.add_argument("--config", type=int, default=3)
+    parser.add_argument("--width", type=int, default=None)
+    parser.add_argument("--height", type=int, default=None)
+    parser.add_argument("--spp", type=int, default=1, help="samples per pixel of a frame")
+    parser.add_argument("--frames", type=int, default=4, help="frames that are accumulated; their variance guides the filter from two on")
+    parser.add_argument("--iterations", type=int, default=DEFAULT_SETTINGS["iteration_count"])
+    parser.add_argument("--sigma-luminance", type=float, default=DEFAULT_SETTINGS["sigma_luminance"])
+    parser.add_argument("--sigma-depth", type=float, default=DEFAULT_SETTINGS["sigma_depth"])
+    parser.add_argument("--normal-squarings", type=int, default=DEFAULT_SETTINGS["normal_squarings"])
+    parser.add_argument("--out", metavar="DIR", required=True)
+    output = parser.add_mutually_exclusive_group()
+    output.add_argument("--hdr", action="store_true", help="Radiance files through the device's encoder (the default)")
+    output.add_argument("--png", action="store_true", help="PNG files of the sRGB8 encoding through the device's encoder")
+    options = parser.parse_args(arguments)
+    if options.frames < 1 or options.spp < 1:
+        parser.error("at least one frame and one sample")
+    os.makedirs(options.out, exist_ok=True)
+    ltc = os.path.join(options.dataset, "ltc")
+    dataset = {"scene": os.path.join(options.dataset, "scene.vks"), "textures": os.path.join(options.dataset, "textures"), "ltc": ltc,
+               "fresnel_count": len([name for name in os.listdir(ltc) if name.startswith("fit")])}
+    scene = R.Renderer()
+    hip, owned = R._hip_runtime(), []
+    try:
+        R.setup_config(scene, options.config, dataset, width=options.width, height=options.height, sample_count=options.spp, acceleration_structure=True)
+        scene.app.render_settings.animate_noise = 1
+        scene.create_targets()
+        scene.create_pass()
+        scene.render_visibility()
+        extent = scene.app.swapchain.extent
+        pixels = extent.width * extent.height
+
+        def allocate():
+            address = C.c_void_p()
+            if hip.hipMalloc(C.byref(address), max(16 * pixels, 16)):
+                raise RuntimeError("no device memory for an image of the frame")
+            owned.append(address)
+            return address.value
+        mean, variance, filtered, encoded = allocate(), allocate(), allocate(), allocate()
+        features = {name: allocate() for name in ("position", "normal", "diffuse_albedo")}
+        if options.frames < 2:
+            variance = None
+        statistics = scene.create_statistics(pixels)
+        for _ in range(options.frames):
+            scene.render()
+            statistics.accumulate()
+        statistics.resolve(mean, variance)
+        scene.render_features(list(features), pointers=features)
+        settings = dict(iteration_count=options.iterations, normal_squarings=options.normal_squarings, sigma_luminance=options.sigma_luminance,
+                        sigma_depth=options.sigma_depth, variance_scale=1.0 / options.frames)
+        scene.filter_frame(mean, variance, features, settings, out_colour=filtered)
+        for name, image in (("noisy", mean), ("filtered", filtered)):
+            if options.png:
+                scene.encode_slab(image, encoded, pixels)
+                data, suffix = scene.encode_png(encoded, width=extent.width, height=extent.height), ".png"
+            else:
+                data, suffix = scene.encode_hdr(image, width=extent.width, height=extent.height), ".hdr"
+            path = os.path.join(options.out, name + suffix)
+            with open(path, "wb") as file:
+                file.write(data)
+            print("%s -> %s (%d bytes)" % (name, path, len(data)))
+    finally:
+        if owned:
+            scene.sync()
+        for address in owned:
+            hip.hipFree(address)
+        scene.close()
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

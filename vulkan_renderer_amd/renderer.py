@@ -1014,9 +1014,37 @@ class Renderer(HostScene):
             raise RuntimeError("sum_frame failed")
         return np.array(out[:], np.float64)
 
+    # -- frame filter (include/vkr_frame_filter.h) -----------------------------------------
+    def create_frame_filter(self, width=None, height=None):
+        """The scratch images of filter_frame() for frames of an extent; None: the swapchain extent"""
+        return FrameFilter(self, width, height)
+
+    def filter_frame(self, colour, variance, features, settings=None, modulation=None, out_colour=None, out_variance=None, frame_filter=None):
+        """The edge-avoiding a-trous filter of include/vkr_frame_filter.h.  colour, variance (None: no luminance weight) and
+        the values of features - {"position", "normal"} and, unless `modulation` names another image, optionally
+        "diffuse_albedo", which colour is divided by before and multiplied by after - are device addresses or float32
+        arrays (height, width, 4), which are uploaded.  settings: the members of frame_filter_settings_t that differ from
+        frame_filter.DEFAULT_SETTINGS.  frame_filter: a create_frame_filter() of the images' extent; None: one of the
+        swapchain extent that the renderer keeps.  -> (filtered colour, filtered variance or None) as arrays; with
+        out_colour (and out_variance), device addresses, the results stay there, the call returns once the kernels are
+        queued and gives nothing."""
+        if frame_filter is None:
+            e = self.app.swapchain.extent
+            kept = getattr(self, "_kept_frame_filter", None)
+            if kept is None or not kept.filter.filtered or (kept.width, kept.height) != (e.width, e.height):
+                if kept is not None:
+                    kept.close()
+                kept = self._kept_frame_filter = self.create_frame_filter()
+            frame_filter = kept
+        if modulation is None:
+            modulation = features.get("diffuse_albedo")
+        return frame_filter.apply(colour, variance, features["position"], features["normal"], modulation, settings, out_colour, out_variance)
+
     def close(self):
         for statistics in list(getattr(self, "_statistics", ())):
             statistics.close()
+        for frame_filter in list(getattr(self, "_frame_filters", ())):
+            frame_filter.close()
         for encoder in self._file_encoders:
             encoder.close()
         super().close()
@@ -1231,6 +1259,90 @@ class FrameStatistics:
             self._scratch = C.c_void_p()
         if self in getattr(self.owner, "_statistics", ()):
             self.owner._statistics.remove(self)
+
+
+class FrameFilter:
+    """Renderer.create_frame_filter(): the scratch images and the event of filter_frame() for one extent"""
+
+    def __init__(self, owner, width=None, height=None):
+        self.owner = owner
+        self.lib = owner.lib
+        self.filter = capi.FrameFilter()
+        if self.lib.create_frame_filter(C.byref(self.filter), C.byref(owner.app), int(width or 0), int(height or 0)):
+            raise RuntimeError("create_frame_filter failed")
+        if not hasattr(owner, "_frame_filters"):
+            owner._frame_filters = []
+        owner._frame_filters.append(self)
+
+    @property
+    def width(self):
+        return int(self.filter.width)
+
+    @property
+    def height(self):
+        return int(self.filter.height)
+
+    def filter_settings(self, settings=None):
+        from . import frame_filter
+        values = dict(frame_filter.DEFAULT_SETTINGS, **(settings or {}))
+        return capi.FrameFilterSettings(int(values["iteration_count"]), int(values["normal_squarings"]), float(values["sigma_luminance"]),
+                                        float(values["sigma_depth"]), float(values["variance_scale"]))
+
+    def apply(self, colour, variance, position, normal, modulation=None, settings=None, out_colour=None, out_variance=None):
+        """See Renderer.filter_frame()"""
+        shape = (self.height, self.width, 4)
+        nbytes = 16 * self.width * self.height
+        hip, owned = _hip_runtime(), []
+
+        def allocate():
+            address = C.c_void_p()
+            if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
+                raise RuntimeError("no device memory for an image of the filter")
+            owned.append(address)
+            return address.value
+
+        def on_device(image):
+            if image is None or not isinstance(image, np.ndarray):
+                return None if image is None else int(getattr(image, "value", image) or 0)
+            image = np.ascontiguousarray(image, np.float32)
+            if image.shape != shape:
+                raise ValueError("an image of this filter is %r, not %r" % (shape, image.shape))
+            address = allocate()
+            if hip.hipMemcpy(address, image.ctypes.data, nbytes, 1):
+                raise RuntimeError("uploading an image of the filter failed")
+            return address
+        try:
+            images = capi.FrameFilterImages(on_device(colour), on_device(variance), on_device(position), on_device(normal), on_device(modulation))
+            stays = out_colour is not None
+            images.out_colour = int(getattr(out_colour, "value", out_colour)) if stays else allocate()
+            if out_variance is not None:
+                images.out_variance = int(getattr(out_variance, "value", out_variance))
+            elif not stays and variance is not None:
+                images.out_variance = allocate()
+            if self.lib.filter_frame(C.byref(self.filter), C.byref(self.owner.app), C.byref(self.filter_settings(settings)), C.byref(images)):
+                raise RuntimeError("filter_frame failed")
+            if stays:
+                return None
+            self.owner.sync()
+            results = []
+            for address in (images.out_colour, images.out_variance):
+                results.append(None)
+                if address:
+                    results[-1] = np.zeros(shape, np.float32)
+                    if hip.hipMemcpy(results[-1].ctypes.data, address, nbytes, 2):
+                        raise RuntimeError("reading the filtered image back failed")
+            return tuple(results)
+        finally:
+            if owned:
+                self.owner.sync()
+            for address in owned:
+                hip.hipFree(address)
+
+    def close(self):
+        if self.filter.filtered:
+            self.lib.destroy_frame_filter(C.byref(self.filter), C.byref(self.owner.app))
+        if self in getattr(self.owner, "_frame_filters", ()):
+            self.owner._frame_filters.remove(self)
 
 
 def frames_in_flight_for(rank_count):
