@@ -289,6 +289,25 @@ class FrameFilter(C.Structure):
                 ("filtered", C.c_void_p)]
 
 
+# include/vkr_frame_history.h
+FRAME_HISTORY_MAX_SPATIAL_LENGTH, FRAME_HISTORY_MAX_EXTENT = 64, FRAME_FILTER_MAX_EXTENT
+
+
+class FrameHistorySettings(C.Structure):
+    _fields_ = [("max_length", C.c_float), ("sigma_depth", C.c_float), ("normal_threshold", C.c_float), ("spatial_length", C.c_uint32)]
+
+
+class FrameHistoryImages(C.Structure):
+    _fields_ = [("colour", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("reprojection", C.c_void_p),
+                ("modulation", C.c_void_p), ("out_colour", C.c_void_p), ("out_variance", C.c_void_p)]
+
+
+class FrameHistory(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("colour", C.c_void_p * 2), ("moments", C.c_void_p * 2),
+                ("position", C.c_void_p * 2), ("normal", C.c_void_p * 2), ("current", C.c_uint32), ("frame_count", C.c_uint32),
+                ("accumulated", C.c_void_p)]
+
+
 ABI_STRUCTS = [Device, PolygonalLight, Camera, LtcConstants, LtcTable, NoiseTable, Mesh, Materials,
                AccelerationStructure, Scene, SceneSpecification, RenderSettings, PerFrameConstants, Swapchain,
                RenderTargets, Screenshot, TileSchedule, LightTextures, ShadingPass, Application, Experiment, ExperimentList,
@@ -460,6 +479,10 @@ SIGNATURES = {
     "create_frame_filter": (C.c_int, [P(FrameFilter), P(Application), C.c_uint32, C.c_uint32]),
     "destroy_frame_filter": (None, [P(FrameFilter), P(Application)]),
     "filter_frame": (C.c_int, [P(FrameFilter), P(Application), P(FrameFilterSettings), P(FrameFilterImages)]),
+    "create_frame_history": (C.c_int, [P(FrameHistory), P(Application), C.c_uint32, C.c_uint32]),
+    "destroy_frame_history": (None, [P(FrameHistory), P(Application)]),
+    "reset_frame_history": (None, [P(FrameHistory)]),
+    "accumulate_frame_history": (C.c_int, [P(FrameHistory), P(Application), P(FrameHistorySettings), P(FrameHistoryImages)]),
     "update_scene_geometry": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_void_p, P(SceneUpdateOptions), P(SceneUpdateReport)]),
 }
 

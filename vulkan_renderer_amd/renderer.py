@@ -1040,11 +1040,37 @@ class Renderer(HostScene):
             modulation = features.get("diffuse_albedo")
         return frame_filter.apply(colour, variance, features["position"], features["normal"], modulation, settings, out_colour, out_variance)
 
+    # -- frame history (include/vkr_frame_history.h) ---------------------------------------
+    def create_frame_history(self, width=None, height=None):
+        """A reprojected history of accumulate_frame_history() for frames of an extent; None: the swapchain extent"""
+        return FrameHistory(self, width, height)
+
+    def accumulate_history(self, colour, features, settings=None, modulation=None, out_colour=None, out_variance=None, want_variance=True, frame_history=None):
+        """The temporal accumulation of include/vkr_frame_history.h.  colour and the values of features - {"position",
+        "normal"}, optionally "reprojection" (under the previous frame's matrix; without it every pixel stays where it is)
+        and, unless `modulation` names another image, optionally "diffuse_albedo" - are device addresses or float32 arrays
+        (height, width, 4), which are uploaded.  settings: the members of frame_history_settings_t that differ from
+        frame_history.DEFAULT_SETTINGS.  frame_history: a create_frame_history() of the images' extent; None: one of the
+        swapchain extent that the renderer keeps from call to call.  -> (accumulated colour, its variance or None without
+        want_variance) as arrays; with out_colour (and out_variance), device addresses, the results stay there, the call
+        returns once the kernels are queued and gives nothing."""
+        if frame_history is None:
+            e = self.app.swapchain.extent
+            kept = getattr(self, "_kept_frame_history", None)
+            if kept is None or not kept.history.accumulated or (kept.width, kept.height) != (e.width, e.height):
+                if kept is not None:
+                    kept.close()
+                kept = self._kept_frame_history = self.create_frame_history()
+            frame_history = kept
+        return frame_history.accumulate(colour, features, settings, modulation, out_colour, out_variance, want_variance)
+
     def close(self):
         for statistics in list(getattr(self, "_statistics", ())):
             statistics.close()
         for frame_filter in list(getattr(self, "_frame_filters", ())):
             frame_filter.close()
+        for frame_history in list(getattr(self, "_frame_histories", ())):
+            frame_history.close()
         for encoder in self._file_encoders:
             encoder.close()
         super().close()
@@ -1343,6 +1369,111 @@ class FrameFilter:
             self.lib.destroy_frame_filter(C.byref(self.filter), C.byref(self.owner.app))
         if self in getattr(self.owner, "_frame_filters", ()):
             self.owner._frame_filters.remove(self)
+
+
+class FrameHistory:
+    """Renderer.create_frame_history(): the two sets of history images and the event of accumulate_frame_history() for one
+    extent"""
+
+    def __init__(self, owner, width=None, height=None):
+        self.owner = owner
+        self.lib = owner.lib
+        self.history = capi.FrameHistory()
+        if self.lib.create_frame_history(C.byref(self.history), C.byref(owner.app), int(width or 0), int(height or 0)):
+            raise RuntimeError("create_frame_history failed")
+        if not hasattr(owner, "_frame_histories"):
+            owner._frame_histories = []
+        owner._frame_histories.append(self)
+
+    @property
+    def width(self):
+        return int(self.history.width)
+
+    @property
+    def height(self):
+        return int(self.history.height)
+
+    @property
+    def frame_count(self):
+        return int(self.history.frame_count)
+
+    def history_settings(self, settings=None):
+        from . import frame_history
+        values = dict(frame_history.DEFAULT_SETTINGS, **(settings or {}))
+        return capi.FrameHistorySettings(float(values["max_length"]), float(values["sigma_depth"]), float(values["normal_threshold"]), int(values["spatial_length"]))
+
+    def reset(self):
+        """The next frame finds no history"""
+        self.lib.reset_frame_history(C.byref(self.history))
+
+    def read(self):
+        """-> {"colour", "moments", "position", "normal"}: the set that the last call wrote, as arrays (height, width, 4)"""
+        self.owner.sync()
+        hip, images = _hip_runtime(), {}
+        for name in ("colour", "moments", "position", "normal"):
+            images[name] = np.zeros((self.height, self.width, 4), np.float32)
+            if hip.hipMemcpy(images[name].ctypes.data, getattr(self.history, name)[self.history.current], images[name].nbytes, 2):
+                raise RuntimeError("reading an image of the history back failed")
+        return images
+
+    def accumulate(self, colour, features, settings=None, modulation=None, out_colour=None, out_variance=None, want_variance=True):
+        """See Renderer.accumulate_history()"""
+        shape = (self.height, self.width, 4)
+        nbytes = 16 * self.width * self.height
+        hip, owned = _hip_runtime(), []
+
+        def allocate():
+            address = C.c_void_p()
+            if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
+                raise RuntimeError("no device memory for an image of the history")
+            owned.append(address)
+            return address.value
+
+        def on_device(image):
+            if image is None or not isinstance(image, np.ndarray):
+                return None if image is None else int(getattr(image, "value", image) or 0)
+            image = np.ascontiguousarray(image, np.float32)
+            if image.shape != shape:
+                raise ValueError("an image of this history is %r, not %r" % (shape, image.shape))
+            address = allocate()
+            if hip.hipMemcpy(address, image.ctypes.data, nbytes, 1):
+                raise RuntimeError("uploading an image of the history failed")
+            return address
+        if modulation is None:
+            modulation = features.get("diffuse_albedo")
+        try:
+            images = capi.FrameHistoryImages(on_device(colour), on_device(features["position"]), on_device(features["normal"]),
+                                             on_device(features.get("reprojection")), on_device(modulation))
+            stays = out_colour is not None
+            images.out_colour = int(getattr(out_colour, "value", out_colour)) if stays else allocate()
+            if out_variance is not None:
+                images.out_variance = int(getattr(out_variance, "value", out_variance))
+            elif not stays and want_variance:
+                images.out_variance = allocate()
+            if self.lib.accumulate_frame_history(C.byref(self.history), C.byref(self.owner.app), C.byref(self.history_settings(settings)), C.byref(images)):
+                raise RuntimeError("accumulate_frame_history failed")
+            if stays:
+                return None
+            self.owner.sync()
+            results = []
+            for address in (images.out_colour, images.out_variance):
+                results.append(None)
+                if address:
+                    results[-1] = np.zeros(shape, np.float32)
+                    if hip.hipMemcpy(results[-1].ctypes.data, address, nbytes, 2):
+                        raise RuntimeError("reading the accumulated image back failed")
+            return tuple(results)
+        finally:
+            if owned:
+                self.owner.sync()
+            for address in owned:
+                hip.hipFree(address)
+
+    def close(self):
+        if self.history.accumulated:
+            self.lib.destroy_frame_history(C.byref(self.history), C.byref(self.owner.app))
+        if self in getattr(self.owner, "_frame_histories", ()):
+            self.owner._frame_histories.remove(self)
 
 
 def frames_in_flight_for(rank_count):
