@@ -76,6 +76,70 @@ class DeviceBuffer:
             self.ptr = None
 
 
+# ---- what the GPU tests of the frame filter and of the frame history share ---------------------------------------------
+
+GUARD_BYTE, GUARD_BYTES = 0xA5, 256
+
+
+class Arena:
+    """[guard][out_colour][guard][out_variance][guard] in one allocation"""
+
+    def __init__(self, width, height):
+        self.shape = (height, width, 4)
+        self.image_bytes = width * height * 16
+        self.stride = GUARD_BYTES + self.image_bytes
+        self.outputs = DeviceBuffer(2 * self.stride + GUARD_BYTES)
+        self.reset()
+
+    def reset(self):
+        self.outputs.upload(np.full(self.outputs.nbytes, GUARD_BYTE, np.uint8))
+
+    def address(self, index):
+        return self.outputs.ptr.value + GUARD_BYTES + index * self.stride
+
+    def read(self):
+        """-> (out_colour, out_variance, whether every guard byte is intact)"""
+        after = self.outputs.download((self.outputs.nbytes,), np.uint8)
+        parts = [after[GUARD_BYTES + i * self.stride:GUARD_BYTES + i * self.stride + self.image_bytes] for i in range(2)]
+        guards = [after[i * self.stride:i * self.stride + GUARD_BYTES] for i in range(3)]
+        return (parts[0].view(np.float32).reshape(self.shape), parts[1].view(np.float32).reshape(self.shape),
+                all((guard == GUARD_BYTE).all() for guard in guards))
+
+    def untouched(self):
+        return (self.outputs.download((self.outputs.nbytes,), np.uint8) == GUARD_BYTE).all()
+
+    def free(self):
+        self.outputs.free()
+
+
+def differing(a, b):
+    return (np.ascontiguousarray(a).view(np.uint32) != np.ascontiguousarray(b).view(np.uint32)).any(axis=-1)
+
+
+def assert_same_bits(got, want, what):
+    different = differing(got, want)
+    assert not different.any(), (what, int(different.sum()), np.argwhere(different)[:4].tolist(), got[different][:2], want[different][:2])
+
+
+def flush_c_output():
+    import ctypes
+    ctypes.CDLL(None).fflush(None)
+
+
+def open_renderer(dataset, arithmetic="libm", extent=(83, 45), **arguments):
+    """A renderer behind whose pass the filter and the history run: the frame of tests/feature_buffer_cases.py with
+    animated noise, its visibility rendered"""
+    import feature_buffer_cases
+    r = renderer.Renderer(arithmetic=arithmetic, **arguments)
+    feature_buffer_cases.apply_frame(r, dataset, extent[0], extent[1], sample_count=1)
+    r.app.render_settings.animate_noise = 1
+    r.app.noise_table.random_seed = 4711
+    r.create_targets()
+    r.create_pass()
+    r.render_visibility()
+    return r
+
+
 # ---- pixels on a discontinuity of the shader ---------------------------------------------------
 #
 # Two arithmetics that agree to a few ulp per operation (libm vs polynomial transcendentals, IEEE vs

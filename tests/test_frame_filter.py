@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import frame_filter_cases as cases
+from helpers import flush_c_output
 from vulkan_renderer_amd import capi, frame_filter
 
 f32 = np.float32
@@ -305,10 +306,6 @@ def test_ctypes_mirror():
         assert "VKR_API int %s(" % symbol in header
         assert hasattr(lib, symbol) and symbol in capi.SIGNATURES
     assert "VKR_API void destroy_frame_filter(" in header and hasattr(lib, "destroy_frame_filter") and "destroy_frame_filter" in capi.SIGNATURES
-
-
-def flush_c_output():
-    C.CDLL(None).fflush(None)
 
 
 def test_refusals_that_need_no_device(capfd):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import frame_history_cases as cases
+from helpers import flush_c_output
 from vulkan_renderer_amd import capi, frame_history
 
 f32 = np.float32
@@ -337,10 +338,6 @@ def test_ctypes_mirror():
         assert hasattr(lib, symbol) and symbol in capi.SIGNATURES
     for symbol in ("destroy_frame_history", "reset_frame_history"):
         assert "VKR_API void %s(" % symbol in header and hasattr(lib, symbol) and symbol in capi.SIGNATURES
-
-
-def flush_c_output():
-    C.CDLL(None).fflush(None)
 
 
 def test_refusals_that_need_no_device(capfd):

@@ -7,15 +7,13 @@ import os
 import numpy as np
 import pytest
 
-import feature_buffer_cases as frames
 import frame_filter_cases as cases
 import png_cases
-from helpers import DeviceBuffer
+from helpers import GUARD_BYTE, Arena, DeviceBuffer, differing, flush_c_output, open_renderer
 from vulkan_renderer_amd import capi, frame_filter, renderer
 
 pytestmark = pytest.mark.gpu
 
-GUARD_BYTE, GUARD_BYTES = 0xA5, 256
 INPUT_NAMES = ("colour", "variance", "position", "normal", "modulation")
 
 
@@ -27,45 +25,24 @@ def device():
     r.close()
 
 
-class Arena:
-    """[guard][out_colour][guard][out_variance][guard] in one allocation, and the inputs of a case in buffers of their own"""
+class FilterArena(Arena):
+    """The guarded outputs, and the inputs of a case in buffers of their own"""
 
     def __init__(self, width, height, images):
-        self.shape = (height, width, 4)
-        self.image_bytes = width * height * 16
-        self.stride = GUARD_BYTES + self.image_bytes
-        self.outputs = DeviceBuffer(2 * self.stride + GUARD_BYTES)
+        super().__init__(width, height)
         self.inputs = {}
         for name in INPUT_NAMES:
             if images.get(name) is not None:
                 self.inputs[name] = DeviceBuffer(self.image_bytes)
                 self.inputs[name].upload(images[name])
-        self.reset()
-
-    def reset(self):
-        self.outputs.upload(np.full(self.outputs.nbytes, GUARD_BYTE, np.uint8))
-
-    def address(self, index):
-        return self.outputs.ptr.value + GUARD_BYTES + index * self.stride
 
     def images(self, want_variance=True):
         pointers = {name: (self.inputs[name].ptr.value if name in self.inputs else None) for name in INPUT_NAMES}
         return capi.FrameFilterImages(pointers["colour"], pointers["variance"], pointers["position"], pointers["normal"], pointers["modulation"],
                                       self.address(0), self.address(1) if want_variance and "variance" in self.inputs else None)
 
-    def read(self):
-        """-> (out_colour, out_variance, whether every guard byte and every unwritten image is intact)"""
-        after = self.outputs.download((self.outputs.nbytes,), np.uint8)
-        parts = [after[GUARD_BYTES + i * self.stride:GUARD_BYTES + i * self.stride + self.image_bytes] for i in range(2)]
-        guards = [after[i * self.stride:i * self.stride + GUARD_BYTES] for i in range(3)]
-        return (parts[0].view(np.float32).reshape(self.shape), parts[1].view(np.float32).reshape(self.shape),
-                all((guard == GUARD_BYTE).all() for guard in guards))
-
-    def untouched(self):
-        return (self.outputs.download((self.outputs.nbytes,), np.uint8) == GUARD_BYTE).all()
-
     def free(self):
-        self.outputs.free()
+        super().free()
         for buffer in self.inputs.values():
             buffer.free()
 
@@ -73,14 +50,6 @@ class Arena:
 def settings_struct(values):
     return capi.FrameFilterSettings(int(values["iteration_count"]), int(values["normal_squarings"]), float(values["sigma_luminance"]),
                                     float(values["sigma_depth"]), float(values["variance_scale"]))
-
-
-def differing(a, b):
-    return (np.ascontiguousarray(a).view(np.uint32) != np.ascontiguousarray(b).view(np.uint32)).any(axis=-1)
-
-
-def flush_c_output():
-    C.CDLL(None).fflush(None)
 
 
 # ---- 1. the cases against numpy ------------------------------------------------------------------------------------------
@@ -97,7 +66,7 @@ def test_cases_equal_numpy_in_every_bit(device, name, iteration_count):
     width, height = cases.CASES[name][:2]
     images = cases.inputs(name)
     want_colour, want_variance, _ = cases.expected(name, iteration_count)
-    arena = Arena(width, height, images)
+    arena = FilterArena(width, height, images)
     filter_ = device.create_frame_filter(width, height)
     lib = capi.load()
     try:
@@ -149,17 +118,6 @@ def test_python_interface_takes_arrays_and_pointers(device):
 
 EXTENT = (83, 45)
 FRAME_SETTINGS = dict(iteration_count=5, normal_squarings=7, sigma_luminance=4.0, sigma_depth=0.02)
-
-
-def open_renderer(dataset, arithmetic="libm", extent=EXTENT, **arguments):
-    r = renderer.Renderer(arithmetic=arithmetic, **arguments)
-    frames.apply_frame(r, dataset, extent[0], extent[1], sample_count=1)
-    r.app.render_settings.animate_noise = 1
-    r.app.noise_table.random_seed = 4711
-    r.create_targets()
-    r.create_pass()
-    r.render_visibility()
-    return r
 
 
 def test_rendered_frames_are_filtered_as_numpy_filters_them(dataset):
@@ -289,7 +247,7 @@ def test_create_and_destroy_twice(device):
 def test_refusals_write_nothing(device, capfd):
     name = "16x16"
     width, height = cases.CASES[name][:2]
-    arena = Arena(width, height, cases.inputs(name))
+    arena = FilterArena(width, height, cases.inputs(name))
     filter_ = device.create_frame_filter(width, height)
     lib = capi.load()
     good = cases.settings(name, 2)

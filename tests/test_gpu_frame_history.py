@@ -9,16 +9,12 @@ import os
 import numpy as np
 import pytest
 
-import feature_buffer_cases as frames
 import frame_history_cases as cases
 import png_cases
-from helpers import DeviceBuffer
+from helpers import GUARD_BYTE, Arena, DeviceBuffer, assert_same_bits, differing, flush_c_output, open_renderer
 from vulkan_renderer_amd import capi, feature_buffers, frame_filter, frame_history, renderer
 
 pytestmark = pytest.mark.gpu
-
-GUARD_BYTE, GUARD_BYTES = 0xA5, 256
-
 
 @pytest.fixture(scope="module")
 def device():
@@ -26,37 +22,6 @@ def device():
     r = renderer.Renderer()
     yield r
     r.close()
-
-
-class Arena:
-    """[guard][out_colour][guard][out_variance][guard] in one allocation"""
-
-    def __init__(self, width, height):
-        self.shape = (height, width, 4)
-        self.image_bytes = width * height * 16
-        self.stride = GUARD_BYTES + self.image_bytes
-        self.outputs = DeviceBuffer(2 * self.stride + GUARD_BYTES)
-        self.reset()
-
-    def reset(self):
-        self.outputs.upload(np.full(self.outputs.nbytes, GUARD_BYTE, np.uint8))
-
-    def address(self, index):
-        return self.outputs.ptr.value + GUARD_BYTES + index * self.stride
-
-    def read(self):
-        """-> (out_colour, out_variance, whether every guard byte is intact)"""
-        after = self.outputs.download((self.outputs.nbytes,), np.uint8)
-        parts = [after[GUARD_BYTES + i * self.stride:GUARD_BYTES + i * self.stride + self.image_bytes] for i in range(2)]
-        guards = [after[i * self.stride:i * self.stride + GUARD_BYTES] for i in range(3)]
-        return (parts[0].view(np.float32).reshape(self.shape), parts[1].view(np.float32).reshape(self.shape),
-                all((guard == GUARD_BYTE).all() for guard in guards))
-
-    def untouched(self):
-        return (self.outputs.download((self.outputs.nbytes,), np.uint8) == GUARD_BYTE).all()
-
-    def free(self):
-        self.outputs.free()
 
 
 class Uploads:
@@ -82,19 +47,6 @@ class Uploads:
 
 def settings_struct(values):
     return capi.FrameHistorySettings(float(values["max_length"]), float(values["sigma_depth"]), float(values["normal_threshold"]), int(values["spatial_length"]))
-
-
-def differing(a, b):
-    return (np.ascontiguousarray(a).view(np.uint32) != np.ascontiguousarray(b).view(np.uint32)).any(axis=-1)
-
-
-def assert_same_bits(got, want, what):
-    different = differing(got, want)
-    assert not different.any(), (what, int(different.sum()), np.argwhere(different)[:4].tolist(), got[different][:2], want[different][:2])
-
-
-def flush_c_output():
-    C.CDLL(None).fflush(None)
 
 
 def assert_frame(history, arena, expected, want_variance, what):
@@ -215,17 +167,6 @@ TURN = math.radians(1.5)
 HISTORY_SETTINGS = dict(max_length=32.0, sigma_depth=0.02, normal_threshold=0.9, spatial_length=4)
 FILTER_SETTINGS = dict(iteration_count=3, normal_squarings=7, sigma_luminance=4.0, sigma_depth=0.02, variance_scale=1.0)
 FEATURES = ("position", "normal", "diffuse_albedo", "reprojection")
-
-
-def open_renderer(dataset, arithmetic="libm", extent=EXTENT, **arguments):
-    r = renderer.Renderer(arithmetic=arithmetic, **arguments)
-    frames.apply_frame(r, dataset, extent[0], extent[1], sample_count=1)
-    r.app.render_settings.animate_noise = 1
-    r.app.noise_table.random_seed = 4711
-    r.create_targets()
-    r.create_pass()
-    r.render_visibility()
-    return r
 
 
 def test_rendered_frames_are_accumulated_and_filtered_as_numpy_does(dataset):

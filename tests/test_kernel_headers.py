@@ -16,9 +16,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vulkan_renderer_amd", "csrc")
-# the launch contract and what it includes, then the parts of the shading program
+# the launch contract and what it includes, then the parts of the shading program; what the frame-image units share
 NEW_HEADERS = ("device_types.h", "bvh_view.h", "psa_table_layout.h", "shade_params.h", "shading_inputs.h", "ltc_brdf.h", "light_records.h",
-               "shadow_terms.h", "kept_polygons.h", "ray_stream.h")
+               "shadow_terms.h", "kept_polygons.h", "ray_stream.h", "frame_images.h")
 PROGRAM_HEADER = "shading_kernel.h"  # the one that holds evaluate_light
 HOST_UNITS = ("frame_transfers", "pass_diagnostics", "render_targets", "slab_assembly", "output_encoding", "prepared_polygons")
 

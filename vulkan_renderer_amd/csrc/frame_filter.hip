@@ -3,13 +3,9 @@
 // contraction in the exact mode's flags, whatever the arithmetic mode of the pass; every result is restated in numpy bit
 // for bit (vulkan_renderer_amd/frame_filter.py).
 #include "vkr_frame_filter.h"
-#include "host/vkr_internal.h"
-#include "device_math.h"
+#include "frame_images.h"
 
 using namespace vkr;
-
-// (see shading_pass.hip: events that order streams of one device need a device-scope release only)
-constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
 
 // ---- kernel ------------------------------------------------------------------------------------------------------
 
@@ -24,12 +20,7 @@ struct filter_iteration {
 	float sigma_luminance, sigma_depth, variance_scale;
 };
 
-VKR_DEV f3 rgb(float4 a) { return mk3(a.x, a.y, a.z); }
 VKR_DEV float luminance(f3 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-VKR_DEV f3 divide3_full_range(f3 a, f3 b) { return mk3(divide_full_range(a.x, b.x), divide_full_range(a.y, b.y), divide_full_range(a.z, b.z)); }
-
-// m of the header from a pixel of the modulation image
-VKR_DEV f3 modulation_of(float4 a) { return mk3(gmax(a.x, 1.0f / 256.0f), gmax(a.y, 1.0f / 256.0f), gmax(a.z, 1.0f / 256.0f)); }
 
 // What the taps of a pixel are weighed against
 struct filter_centre {
@@ -94,14 +85,6 @@ template <bool LAST, bool VARIANCE> VKR_DEV void store_filtered(const filter_ite
 		if (modulated) v = v * (m * m);
 		f.out_variance[p] = make_float4(v.x, v.y, v.z, 1.0f);
 	}
-}
-
-// The lane's pixel: 16x16 pixels per workgroup, 8x8 per wave (the mapping of k_feature_buffers), so that a tap of a wave is
-// eight runs of 128 consecutive bytes per image
-VKR_DEV void lane_pixel(uint32_t& lx, uint32_t& ly) {
-	uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	lx = ((wave & 1) << 3) + (lane & 7);
-	ly = ((wave >> 1) << 3) + (lane >> 3);
 }
 
 // ---- the first launch: step 1 and the prepare, from an LDS tile ---------------------------------------------------
@@ -323,55 +306,20 @@ template <bool VARIANCE> static void launch_iteration(const filter_iteration& f,
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
+// The two pairs of scratch images that the iterations alternate between, and the event behind the last one
+static frame_image_set images_of(frame_filter_t* filter) {
+	return {"filter", &filter->width, &filter->height, &filter->filtered, 4,
+		{&filter->colour_scratch[0], &filter->colour_scratch[1], &filter->variance_scratch[0], &filter->variance_scratch[1]}};
+}
+
 extern "C" void destroy_frame_filter(frame_filter_t* filter, application_t* app) {
-	// (the filter's kernels may still read and write the scratch images)
-	if (filter->filtered && app && app->device.stream) (void) hipStreamSynchronize((hipStream_t) app->device.stream);
-	if (filter->filtered) {
-		// (the pass may still hold the event as the reader of a target)
-		if (app) vkr_forget_target_reader(app, filter->filtered);
-		(void) hipEventDestroy((hipEvent_t) filter->filtered);
-	}
-	for (int i = 0; i != 2; ++i) {
-		if (filter->colour_scratch[i]) (void) hipFree(filter->colour_scratch[i]);
-		if (filter->variance_scratch[i]) (void) hipFree(filter->variance_scratch[i]);
-	}
+	destroy_frame_images(images_of(filter), app);
 	memset(filter, 0, sizeof(*filter));
 }
 
 extern "C" int create_frame_filter(frame_filter_t* filter, application_t* app, uint32_t width, uint32_t height) {
 	memset(filter, 0, sizeof(*filter));
-	if (!width && !height) {
-		width = app->swapchain.extent.width;
-		height = app->swapchain.extent.height;
-	}
-	if (!width || !height || width > VKR_FRAME_FILTER_MAX_EXTENT || height > VKR_FRAME_FILTER_MAX_EXTENT) {
-		printf("A frame filter needs a width and a height between 1 and %d (an extent, or a swapchain extent).\n", VKR_FRAME_FILTER_MAX_EXTENT);
-		return 1;
-	}
-	filter->width = width;
-	filter->height = height;
-	size_t bytes = sizeof(float4) * (size_t) width * height;
-	for (int i = 0; i != 4; ++i) {
-		void** image = i < 2 ? &filter->colour_scratch[i] : &filter->variance_scratch[i - 2];
-		if (hipMalloc(image, bytes) != hipSuccess) {
-			printf("Failed to allocate %.1f MiB for the scratch images of a %ux%u frame filter.\n", 4.0 * bytes / 1048576.0, width, height);
-			*image = NULL;
-			destroy_frame_filter(filter, app);
-			return 1;
-		}
-	}
-	if (hip_failed(hipEventCreateWithFlags((hipEvent_t*) &filter->filtered, kSyncEventFlags), "creating the filter's event")) {
-		filter->filtered = NULL;
-		destroy_frame_filter(filter, app);
-		return 1;
-	}
-	return 0;
-}
-
-static bool overlap(const void* a, const void* b, size_t bytes) {
-	const uint8_t* x = (const uint8_t*) a;
-	const uint8_t* y = (const uint8_t*) b;
-	return x && y && x < y + bytes && y < x + bytes;
+	return create_frame_images(images_of(filter), app, width, height, VKR_FRAME_FILTER_MAX_EXTENT, false, "scratch images");
 }
 
 extern "C" int filter_frame(frame_filter_t* filter, application_t* app, const frame_filter_settings_t* settings, const frame_filter_images_t* images) {
@@ -391,32 +339,16 @@ extern "C" int filter_frame(frame_filter_t* filter, application_t* app, const fr
 		printf("filter_frame(): a variance output needs a variance image.\n");
 		return 1;
 	}
-	const void* inputs[5] = {images->colour, images->variance, images->position, images->normal, images->modulation};
-	void* outputs[2] = {images->out_colour, images->out_variance};
-	bool aligned = true;
-	for (const void* image : inputs) aligned = aligned && ((uintptr_t) image & 15u) == 0;
-	for (const void* image : outputs) aligned = aligned && ((uintptr_t) image & 15u) == 0;
-	if (!images->colour || !images->position || !images->normal || !images->out_colour || !aligned) {
-		printf("filter_frame() needs colour, position, normal and out_colour, and every image 16-byte aligned.\n");
-		return 1;
-	}
-	if (!filter->filtered || !filter->colour_scratch[0] || !filter->colour_scratch[1] || !filter->variance_scratch[0] || !filter->variance_scratch[1] || !filter->width || !filter->height) {
+	const frame_call call = {"filter_frame", {images->colour, images->variance, images->position, images->normal, images->modulation}, {images->out_colour, images->out_variance}};
+	if (check_frame_call_images(call, images->colour && images->position && images->normal && images->out_colour)) return 1;
+	const frame_image_set own = images_of(filter);
+	if (!frame_images_created(own)) {
 		printf("filter_frame() needs a filter created by create_frame_filter().\n");
 		return 1;
 	}
-	size_t bytes = sizeof(float4) * (size_t) filter->width * filter->height;
-	bool overlapping = overlap(outputs[0], outputs[1], bytes);
-	for (const void* input : inputs) overlapping = overlapping || overlap(outputs[0], input, bytes) || overlap(outputs[1], input, bytes);
-	if (overlapping) {
-		printf("filter_frame(): an output overlaps an input or the other output.\n");
-		return 1;
-	}
-	hipStream_t stream = (hipStream_t) app->device.stream;
-	// behind the frames in flight (an input may be a target of any of them); a writer outside the pass waits for the
-	// read-backs and noted readers of what it writes
-	if (vkr_order_behind_frames_in_flight(app, stream)) return 1;
-	for (void* output : outputs)
-		if (output) vkr_order_target_write(app, output, bytes, stream);
+	const size_t bytes = frame_image_bytes(own);
+	hipStream_t stream;
+	if (check_frame_call_overlap(call, bytes, NULL) || begin_frame_call(call, app, bytes, &stream)) return 1;
 	const uint32_t n = settings->iteration_count;
 	for (uint32_t i = 0; i != n; ++i) {
 		const bool first = i == 0, last = i + 1 == n;
@@ -439,14 +371,5 @@ extern "C" int filter_frame(frame_filter_t* filter, application_t* app, const fr
 		else launch_iteration<false>(f, first, last, stream);
 		if (hip_failed(hipGetLastError(), "filtering a frame")) return 1;
 	}
-	if (hip_failed(hipEventRecord((hipEvent_t) filter->filtered, stream), "marking the filtered frame")) return 1;
-	// frames in flight do not follow device->stream: one that writes an input or an output comes behind the filter this way
-	// (only a pass writes frames, and it is the pass that keeps the readers)
-	if (app->shading_pass.constants_device) {
-		for (const void* input : inputs)
-			if (input) vkr_note_target_reader(app, filter->filtered, input, bytes);
-		for (void* output : outputs)
-			if (output) vkr_note_target_reader(app, filter->filtered, output, bytes);
-	}
-	return 0;
+	return finish_frame_call(call, app, bytes, filter->filtered, "marking the filtered frame");
 }

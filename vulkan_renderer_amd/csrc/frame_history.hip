@@ -3,13 +3,9 @@
 // pixels with a short history by a spatial estimate.  Compiled without contraction in the exact mode's flags, whatever the
 // arithmetic mode of the pass; every result is restated in numpy bit for bit (vulkan_renderer_amd/frame_history.py).
 #include "vkr_frame_history.h"
-#include "host/vkr_internal.h"
-#include "device_math.h"
+#include "frame_images.h"
 
 using namespace vkr;
-
-// (see shading_pass.hip: events that order streams of one device need a device-scope release only)
-constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
 
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
@@ -23,22 +19,6 @@ struct history_frame {
 	uint32_t width, height, has_history;
 	float max_length, sigma_depth, normal_threshold, spatial_length;
 };
-
-VKR_DEV f3 rgb(float4 a) { return mk3(a.x, a.y, a.z); }
-VKR_DEV f3 divide3_full_range(f3 a, f3 b) { return mk3(divide_full_range(a.x, b.x), divide_full_range(a.y, b.y), divide_full_range(a.z, b.z)); }
-VKR_DEV f3 divide3_full_range(f3 a, float b) { return mk3(divide_full_range(a.x, b), divide_full_range(a.y, b), divide_full_range(a.z, b)); }
-VKR_DEV f3 gmax3(float a, f3 b) { return mk3(gmax(a, b.x), gmax(a, b.y), gmax(a, b.z)); }
-
-// m of the header from a pixel of the modulation image
-VKR_DEV f3 modulation_of(float4 a) { return mk3(gmax(a.x, 1.0f / 256.0f), gmax(a.y, 1.0f / 256.0f), gmax(a.z, 1.0f / 256.0f)); }
-
-// The lane's pixel: 16x16 pixels per workgroup, 8x8 per wave (the mapping of the frame filter), so that what a wave reads
-// and writes of an image is eight runs of 128 consecutive bytes
-VKR_DEV void lane_pixel(uint32_t& lx, uint32_t& ly) {
-	uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	lx = ((wave & 1) << 3) + (lane & 7);
-	ly = ((wave >> 1) << 3) + (lane >> 3);
-}
 
 // Whether a pixel at P_q with normal n_q belongs to the surface of p: the plane test and the normal test of the header
 VKR_DEV bool same_surface(const history_frame& f, f3 P_p, f3 n_p, float d_z, f3 P_q, f3 n_q) {
@@ -200,64 +180,25 @@ __global__ void __launch_bounds__(256) k_history_spatial_variance(const history_
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-static void** history_image(frame_history_t* history, int i) {
-	void** sets[4] = {history->colour, history->moments, history->position, history->normal};
-	return &sets[i >> 1][i & 1];
+// The two sets of colour, moments, position and normal, and the event behind the last call
+static frame_image_set images_of(frame_history_t* history) {
+	return {"history", &history->width, &history->height, &history->accumulated, 8,
+		{&history->colour[0], &history->colour[1], &history->moments[0], &history->moments[1], &history->position[0], &history->position[1], &history->normal[0], &history->normal[1]}};
 }
 
 extern "C" void destroy_frame_history(frame_history_t* history, application_t* app) {
-	// (the kernels of the last call may still read and write the history)
-	if (history->accumulated && app && app->device.stream) (void) hipStreamSynchronize((hipStream_t) app->device.stream);
-	if (history->accumulated) {
-		// (the pass may still hold the event as the reader of a target)
-		if (app) vkr_forget_target_reader(app, history->accumulated);
-		(void) hipEventDestroy((hipEvent_t) history->accumulated);
-	}
-	for (int i = 0; i != 8; ++i)
-		if (*history_image(history, i)) (void) hipFree(*history_image(history, i));
+	destroy_frame_images(images_of(history), app);
 	memset(history, 0, sizeof(*history));
 }
 
 extern "C" int create_frame_history(frame_history_t* history, application_t* app, uint32_t width, uint32_t height) {
 	memset(history, 0, sizeof(*history));
-	if (!width && !height) {
-		width = app->swapchain.extent.width;
-		height = app->swapchain.extent.height;
-	}
-	if (!width || !height || width > VKR_FRAME_HISTORY_MAX_EXTENT || height > VKR_FRAME_HISTORY_MAX_EXTENT) {
-		printf("A frame history needs a width and a height between 1 and %d (an extent, or a swapchain extent).\n", VKR_FRAME_HISTORY_MAX_EXTENT);
-		return 1;
-	}
-	history->width = width;
-	history->height = height;
-	size_t bytes = sizeof(float4) * (size_t) width * height;
-	for (int i = 0; i != 8; ++i) {
-		void** image = history_image(history, i);
-		// (cleared: reset_frame_history() touches no memory, and no call reads a set before one wrote it, but read() may)
-		bool allocated = hipMalloc(image, bytes) == hipSuccess;
-		if (!allocated) *image = NULL;
-		if (!allocated || hipMemset(*image, 0, bytes) != hipSuccess) {
-			printf("Failed to allocate %.1f MiB for the images of a %ux%u frame history.\n", 8.0 * bytes / 1048576.0, width, height);
-			destroy_frame_history(history, app);
-			return 1;
-		}
-	}
-	if (hip_failed(hipEventCreateWithFlags((hipEvent_t*) &history->accumulated, kSyncEventFlags), "creating the history's event")) {
-		history->accumulated = NULL;
-		destroy_frame_history(history, app);
-		return 1;
-	}
-	return 0;
+	// (cleared: reset_frame_history() touches no memory, and no call reads a set before one wrote it, but read() may)
+	return create_frame_images(images_of(history), app, width, height, VKR_FRAME_HISTORY_MAX_EXTENT, true, "images");
 }
 
 extern "C" void reset_frame_history(frame_history_t* history) {
 	if (history) history->frame_count = 0;
-}
-
-static bool overlap(const void* a, const void* b, size_t bytes) {
-	const uint8_t* x = (const uint8_t*) a;
-	const uint8_t* y = (const uint8_t*) b;
-	return x && y && x < y + bytes && y < x + bytes;
 }
 
 extern "C" int accumulate_frame_history(frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images) {
@@ -272,37 +213,16 @@ extern "C" int accumulate_frame_history(frame_history_t* history, application_t*
 		printf("accumulate_frame_history() takes a finite largest length >= 1, a finite sigma of the depth > 0, a normal threshold from -1 to 1 and a spatial length up to %d.\n", VKR_FRAME_HISTORY_MAX_SPATIAL_LENGTH);
 		return 1;
 	}
-	const void* inputs[5] = {images->colour, images->position, images->normal, images->reprojection, images->modulation};
-	void* outputs[2] = {images->out_colour, images->out_variance};
-	bool aligned = true;
-	for (const void* image : inputs) aligned = aligned && ((uintptr_t) image & 15u) == 0;
-	for (const void* image : outputs) aligned = aligned && ((uintptr_t) image & 15u) == 0;
-	if (!images->colour || !images->position || !images->normal || !images->out_colour || !aligned) {
-		printf("accumulate_frame_history() needs colour, position, normal and out_colour, and every image 16-byte aligned.\n");
-		return 1;
-	}
-	bool created = history->accumulated && history->width && history->height && history->current < 2;
-	for (int i = 0; i != 8; ++i) created = created && *history_image(history, i);
-	if (!created) {
+	const frame_call call = {"accumulate_frame_history", {images->colour, images->position, images->normal, images->reprojection, images->modulation}, {images->out_colour, images->out_variance}};
+	if (check_frame_call_images(call, images->colour && images->position && images->normal && images->out_colour)) return 1;
+	const frame_image_set own = images_of(history);
+	if (!frame_images_created(own) || history->current >= 2) {
 		printf("accumulate_frame_history() needs a history created by create_frame_history().\n");
 		return 1;
 	}
-	size_t bytes = sizeof(float4) * (size_t) history->width * history->height;
-	bool overlapping = overlap(outputs[0], outputs[1], bytes);
-	for (void* output : outputs) {
-		for (const void* input : inputs) overlapping = overlapping || overlap(output, input, bytes);
-		for (int i = 0; i != 8; ++i) overlapping = overlapping || overlap(output, *history_image(history, i), bytes);
-	}
-	if (overlapping) {
-		printf("accumulate_frame_history(): an output overlaps an input, the other output or an image of the history.\n");
-		return 1;
-	}
-	hipStream_t stream = (hipStream_t) app->device.stream;
-	// behind the frames in flight (an input may be a target of any of them); a writer outside the pass waits for the
-	// read-backs and noted readers of what it writes
-	if (vkr_order_behind_frames_in_flight(app, stream)) return 1;
-	for (void* output : outputs)
-		if (output) vkr_order_target_write(app, output, bytes, stream);
+	const size_t bytes = frame_image_bytes(own);
+	hipStream_t stream;
+	if (check_frame_call_overlap(call, bytes, &own) || begin_frame_call(call, app, bytes, &stream)) return 1;
 	const uint32_t old_set = history->current, new_set = old_set ^ 1u;
 	history_frame f;
 	f.colour = (const float4*) images->colour;
@@ -338,14 +258,5 @@ extern "C" int accumulate_frame_history(frame_history_t* history, application_t*
 	history->current = new_set;
 	// (a counter that wrapped to 0 would drop the history)
 	if (history->frame_count != UINT32_MAX) ++history->frame_count;
-	if (hip_failed(hipEventRecord((hipEvent_t) history->accumulated, stream), "marking the accumulated frame")) return 1;
-	// frames in flight do not follow device->stream: one that writes an input or an output comes behind this call this way
-	// (only a pass writes frames, and it is the pass that keeps the readers)
-	if (app->shading_pass.constants_device) {
-		for (const void* input : inputs)
-			if (input) vkr_note_target_reader(app, history->accumulated, input, bytes);
-		for (void* output : outputs)
-			if (output) vkr_note_target_reader(app, history->accumulated, output, bytes);
-	}
-	return 0;
+	return finish_frame_call(call, app, bytes, history->accumulated, "marking the accumulated frame");
 }

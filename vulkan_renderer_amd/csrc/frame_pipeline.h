@@ -5,11 +5,6 @@
 #include "pass_internal.h"
 #include "kept_inputs.h"
 
-// Events that order streams of one device: a device-scope release is all they need.  The default
-// (system-scope fence: L2 write-back and invalidation at every record) is paid by whatever runs
-// next on the device, and a frame records several.
-constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
-
 // events of a timed frame: its start, the start and the end of the (last band's) shading kernel, its end
 constexpr uint32_t kTimingFrameStart = 0, kTimingShadingStart = 1, kTimingShadingEnd = 2, kTimingFrameEnd = 3, kTimingEvents = 4;
 

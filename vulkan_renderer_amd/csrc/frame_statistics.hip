@@ -2,11 +2,8 @@
 // variance from them, and error sums of whole frames with a fixed order of additions.  Compiled without contraction
 // like shading_pass.hip; every result is restated in numpy bit for bit (vulkan_renderer_amd/frame_statistics.py).
 #include "vkr_frame_statistics.h"
-#include "host/vkr_internal.h"
-#include <hip/hip_runtime.h>
+#include "frame_images.h"
 
-// (see shading_pass.hip: events that order streams of one device need a device-scope release only)
-constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
 constexpr uint32_t kEventRing = VKR_MAX_ACCUMULATED_FRAMES * 2;
 constexpr uint32_t kBlock = 256;
 // (the grid's x extent)
@@ -224,13 +221,9 @@ extern "C" int resolve_frame_statistics(frame_statistics_t* stats, application_t
 	if (out_mean) vkr_order_target_write(app, out_mean, bytes, stream);
 	if (out_variance) vkr_order_target_write(app, out_variance, bytes, stream);
 	k_resolve_statistics<<<block_count(stats->pixel_count, kBlock), kBlock, 0, stream>>>((const double2*) stats->sums, stats->pixel_count, stats->frame_count, (float4*) out_mean, (float4*) out_variance);
-	if (hip_failed(hipGetLastError(), "resolving the statistics")
-		|| hip_failed(hipEventRecord((hipEvent_t) stats->resolved, stream), "marking the resolve"))
-		return 1;
-	// frames in flight do not follow device->stream: one that writes an output comes behind the resolve this way
-	if (out_mean && app->shading_pass.constants_device) vkr_note_target_reader(app, stats->resolved, out_mean, bytes);
-	if (out_variance && app->shading_pass.constants_device) vkr_note_target_reader(app, stats->resolved, out_variance, bytes);
-	return 0;
+	if (hip_failed(hipGetLastError(), "resolving the statistics")) return 1;
+	const frame_call call = {"resolve_frame_statistics", {}, {out_mean, out_variance}};
+	return finish_frame_call(call, app, bytes, stats->resolved, "marking the resolve");
 }
 
 extern "C" int read_back_frame_statistics(frame_statistics_t* stats, application_t* app, double* sums, double* squares) {

@@ -13,6 +13,13 @@ static inline int hip_failed(hipError_t error, const char* what) {
 	return 1;
 }
 
+#ifdef __cplusplus
+/*! Events that order streams of one device: a device-scope release is all they need.  The default (system-scope fence:
+	L2 write-back and invalidation at every record) is paid by whatever runs next on the device, and a frame records
+	several. */
+constexpr unsigned kSyncEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
+#endif
+
 /*! workgroups of `block` lanes that cover `lanes` lanes */
 static inline uint32_t block_count(uint64_t lanes, uint32_t block) { return (uint32_t) ((lanes + block - 1) / block); }
 

@@ -166,12 +166,9 @@ def main(arguments=None):
     import argparse
     import os
 
-    from . import renderer as R
+    from . import frame_images
     parser = argparse.ArgumentParser(prog="python -m vulkan_renderer_amd.feature_buffers", description="Writes feature images of a dataset's frame.")
-    parser.add_argument("dataset", help="directory of a dataset (scene.vks, LTC tables), as bench.py and the tests write it")
-    parser.add_argument("--config", type=int, default=3)
-    parser.add_argument("--width", type=int, default=None)
-    parser.add_argument("--height", type=int, default=None)
+    frame_images.add_dataset_arguments(parser, spp=False)
     parser.add_argument("--feature", action="append", choices=PIXEL_FEATURES, required=True)
     parser.add_argument("--range", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="of the position and reprojection previews (--png)")
     output = parser.add_mutually_exclusive_group(required=True)
@@ -181,14 +178,7 @@ def main(arguments=None):
     options = parser.parse_args(arguments)
     directory = options.npy or options.hdr or options.png
     os.makedirs(directory, exist_ok=True)
-    ltc = os.path.join(options.dataset, "ltc")
-    dataset = {"scene": os.path.join(options.dataset, "scene.vks"), "textures": os.path.join(options.dataset, "textures"), "ltc": ltc,
-               "fresnel_count": len([name for name in os.listdir(ltc) if name.startswith("fit")])}
-    scene = R.Renderer()
-    try:
-        R.setup_config(scene, options.config, dataset, width=options.width, height=options.height, acceleration_structure=True)
-        scene.create_targets()
-        scene.create_pass()
+    with frame_images.open_dataset(options) as scene:
         scene.render_visibility()
         images = scene.render_features(options.feature)
         for name, image in images.items():
@@ -207,8 +197,6 @@ def main(arguments=None):
                 with open(os.path.join(directory, name + ".png"), "wb") as file:
                     file.write(scene.encode_png(scene.feature_preview(name, image, value_range)))
             print("%s -> %s" % (name, directory))
-    finally:
-        scene.close()
     return 0
 
 

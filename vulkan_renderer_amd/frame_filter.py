@@ -191,52 +191,28 @@ def filter_frame(colour, variance, position, normal, modulation=None, settings=N
 
 def main(arguments=None):
     import argparse
-    import ctypes as C
     import os
 
-    from . import renderer as R
+    from . import frame_images
     parser = argparse.ArgumentParser(prog="python -m vulkan_renderer_amd.frame_filter",
                                      description="Renders frames of a dataset with animated noise, accumulates them, filters their mean on the device and writes the noisy and the filtered image.")
-    parser.add_argument("dataset", help="directory of a dataset (scene.vks, LTC tables), as bench.py and the tests write it")
-    parser.add_argument("--config", type=int, default=3)
-    parser.add_argument("--width", type=int, default=None)
-    parser.add_argument("--height", type=int, default=None)
-    parser.add_argument("--spp", type=int, default=1, help="samples per pixel of a frame")
+    frame_images.add_dataset_arguments(parser)
     parser.add_argument("--frames", type=int, default=4, help="frames that are accumulated; their variance guides the filter from two on")
     parser.add_argument("--iterations", type=int, default=DEFAULT_SETTINGS["iteration_count"])
     parser.add_argument("--sigma-luminance", type=float, default=DEFAULT_SETTINGS["sigma_luminance"])
     parser.add_argument("--sigma-depth", type=float, default=DEFAULT_SETTINGS["sigma_depth"])
     parser.add_argument("--normal-squarings", type=int, default=DEFAULT_SETTINGS["normal_squarings"])
-    parser.add_argument("--out", metavar="DIR", required=True)
-    output = parser.add_mutually_exclusive_group()
-    output.add_argument("--hdr", action="store_true", help="Radiance files through the device's encoder (the default)")
-    output.add_argument("--png", action="store_true", help="PNG files of the sRGB8 encoding through the device's encoder")
+    frame_images.add_output_arguments(parser)
     options = parser.parse_args(arguments)
     if options.frames < 1 or options.spp < 1:
         parser.error("at least one frame and one sample")
     os.makedirs(options.out, exist_ok=True)
-    ltc = os.path.join(options.dataset, "ltc")
-    dataset = {"scene": os.path.join(options.dataset, "scene.vks"), "textures": os.path.join(options.dataset, "textures"), "ltc": ltc,
-               "fresnel_count": len([name for name in os.listdir(ltc) if name.startswith("fit")])}
-    scene = R.Renderer()
-    hip, owned = R._hip_runtime(), []
-    try:
-        R.setup_config(scene, options.config, dataset, width=options.width, height=options.height, sample_count=options.spp, acceleration_structure=True)
-        scene.app.render_settings.animate_noise = 1
-        scene.create_targets()
-        scene.create_pass()
+    with frame_images.open_dataset(options, animate_noise=True, sample_count=options.spp) as scene, frame_images._DeviceScratch(scene, "an image of the frame") as scratch:
         scene.render_visibility()
         extent = scene.app.swapchain.extent
         pixels = extent.width * extent.height
-
-        def allocate():
-            address = C.c_void_p()
-            if hip.hipMalloc(C.byref(address), max(16 * pixels, 16)):
-                raise RuntimeError("no device memory for an image of the frame")
-            owned.append(address)
-            return address.value
-        mean, variance, filtered, encoded = allocate(), allocate(), allocate(), allocate()
-        features = {name: allocate() for name in ("position", "normal", "diffuse_albedo")}
+        mean, variance, filtered = (scratch.allocate(16 * pixels) for _ in range(3))
+        features = {name: scratch.allocate(16 * pixels) for name in ("position", "normal", "diffuse_albedo")}
         if options.frames < 2:
             variance = None
         statistics = scene.create_statistics(pixels)
@@ -248,22 +224,7 @@ def main(arguments=None):
         settings = dict(iteration_count=options.iterations, normal_squarings=options.normal_squarings, sigma_luminance=options.sigma_luminance,
                         sigma_depth=options.sigma_depth, variance_scale=1.0 / options.frames)
         scene.filter_frame(mean, variance, features, settings, out_colour=filtered)
-        for name, image in (("noisy", mean), ("filtered", filtered)):
-            if options.png:
-                scene.encode_slab(image, encoded, pixels)
-                data, suffix = scene.encode_png(encoded, width=extent.width, height=extent.height), ".png"
-            else:
-                data, suffix = scene.encode_hdr(image, width=extent.width, height=extent.height), ".hdr"
-            path = os.path.join(options.out, name + suffix)
-            with open(path, "wb") as file:
-                file.write(data)
-            print("%s -> %s (%d bytes)" % (name, path, len(data)))
-    finally:
-        if owned:
-            scene.sync()
-        for address in owned:
-            hip.hipFree(address)
-        scene.close()
+        frame_images.write_images(scene, scratch, options, (("noisy", mean), ("filtered", filtered)))
     return 0
 
 

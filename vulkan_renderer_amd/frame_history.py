@@ -170,52 +170,27 @@ def _accumulate(state, colour, position, normal, reprojection, modulation, setti
 
 def main(arguments=None):
     import argparse
-    import ctypes as C
     import math
     import os
 
-    from . import feature_buffers
-    from . import renderer as R
+    from . import feature_buffers, frame_images
     parser = argparse.ArgumentParser(prog="python -m vulkan_renderer_amd.frame_history",
                                      description="Renders frames of a dataset with animated noise while the camera turns, accumulates them in a reprojected history on the device and writes the last noisy frame, the accumulated and the filtered image.")
-    parser.add_argument("dataset", help="directory of a dataset (scene.vks, LTC tables), as bench.py and the tests write it")
-    parser.add_argument("--config", type=int, default=3)
-    parser.add_argument("--width", type=int, default=None)
-    parser.add_argument("--height", type=int, default=None)
+    frame_images.add_dataset_arguments(parser)
     parser.add_argument("--frames", type=int, default=8)
-    parser.add_argument("--spp", type=int, default=1, help="samples per pixel of a frame")
     parser.add_argument("--turn", type=float, default=0.0, metavar="DEGREES", help="about the vertical axis, over all frames")
     parser.add_argument("--max-length", type=float, default=DEFAULT_SETTINGS["max_length"])
     parser.add_argument("--filter", action="store_true", help="filter_frame() on the accumulated image and its variance (without it the filtered image is the accumulated one)")
-    parser.add_argument("--out", metavar="DIR", required=True)
-    output = parser.add_mutually_exclusive_group()
-    output.add_argument("--hdr", action="store_true", help="Radiance files through the device's encoder (the default)")
-    output.add_argument("--png", action="store_true", help="PNG files of the sRGB8 encoding through the device's encoder")
+    frame_images.add_output_arguments(parser)
     options = parser.parse_args(arguments)
     if options.frames < 1 or options.spp < 1:
         parser.error("at least one frame and one sample")
     os.makedirs(options.out, exist_ok=True)
-    ltc = os.path.join(options.dataset, "ltc")
-    dataset = {"scene": os.path.join(options.dataset, "scene.vks"), "textures": os.path.join(options.dataset, "textures"), "ltc": ltc,
-               "fresnel_count": len([name for name in os.listdir(ltc) if name.startswith("fit")])}
-    scene = R.Renderer()
-    hip, owned = R._hip_runtime(), []
-    try:
-        R.setup_config(scene, options.config, dataset, width=options.width, height=options.height, sample_count=options.spp, acceleration_structure=True)
-        scene.app.render_settings.animate_noise = 1
-        scene.create_targets()
-        scene.create_pass()
+    with frame_images.open_dataset(options, animate_noise=True, sample_count=options.spp) as scene, frame_images._DeviceScratch(scene, "an image of the frame") as scratch:
         extent = scene.app.swapchain.extent
         pixels = extent.width * extent.height
-
-        def allocate():
-            address = C.c_void_p()
-            if hip.hipMalloc(C.byref(address), max(16 * pixels, 16)):
-                raise RuntimeError("no device memory for an image of the frame")
-            owned.append(address)
-            return address.value
-        noisy, accumulated, variance, filtered, encoded = allocate(), allocate(), allocate(), allocate(), allocate()
-        features = {name: allocate() for name in ("position", "normal", "diffuse_albedo", "reprojection")}
+        noisy, accumulated, variance, filtered = (scratch.allocate(16 * pixels) for _ in range(4))
+        features = {name: scratch.allocate(16 * pixels) for name in ("position", "normal", "diffuse_albedo", "reprojection")}
         history = scene.create_frame_history()
         camera = scene.app.scene_specification.camera
         step = math.radians(options.turn) / max(options.frames - 1, 1)
@@ -230,22 +205,7 @@ def main(arguments=None):
             camera.rotation_z += step
         if options.filter:
             scene.filter_frame(accumulated, variance, features, dict(variance_scale=1.0), out_colour=filtered)
-        for name, image in (("noisy", noisy), ("accumulated", accumulated), ("filtered", filtered if options.filter else accumulated)):
-            if options.png:
-                scene.encode_slab(image, encoded, pixels)
-                data, suffix = scene.encode_png(encoded, width=extent.width, height=extent.height), ".png"
-            else:
-                data, suffix = scene.encode_hdr(image, width=extent.width, height=extent.height), ".hdr"
-            path = os.path.join(options.out, name + suffix)
-            with open(path, "wb") as file:
-                file.write(data)
-            print("%s -> %s (%d bytes)" % (name, path, len(data)))
-    finally:
-        if owned:
-            scene.sync()
-        for address in owned:
-            hip.hipFree(address)
-        scene.close()
+        frame_images.write_images(scene, scratch, options, (("noisy", noisy), ("accumulated", accumulated), ("filtered", filtered if options.filter else accumulated)))
     return 0
 
 

@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from . import capi
+from .frame_images import FrameFilter, FrameHistory, FrameStatistics, _DeviceScratch, _hip_runtime  # noqa: F401 (used under this module's name)
 
 STRATEGY = {"diffuse_only": 0, "diffuse_ggx_mis": 1, "diffuse_specular_separately": 2,
             "diffuse_specular_mis": 3, "diffuse_specular_random": 4}
@@ -244,6 +245,9 @@ class Renderer(HostScene):
         super().__init__()
         # the open JPEG, HDR and PNG encoders, and those that encode_jpeg(), encode_hdr() and encode_png() keep
         self._file_encoders, self._file_encoder_cache = [], {}
+        # the open FrameStatistics, FrameFilter and FrameHistory objects, and those that filter_frame() and
+        # accumulate_history() keep
+        self._frame_objects, self._kept_frame_objects = [], {}
         self.binary_traversal = binary_traversal
         self.exchange = None
         self.timing_stride = timing_stride
@@ -651,35 +655,17 @@ class Renderer(HostScene):
             buffers.reprojection_matrix[i][:] = [float(v) for v in matrix[i]]
         e = self.app.swapchain.extent
         nbytes = e.width * e.height * 16
-        hip, owned = _hip_runtime(), {}
-        try:
+        with _DeviceScratch(self, "the feature images") as scratch:
             for name in names:
                 index = capi.PIXEL_FEATURES.index(name)
-                if pointers is not None:
-                    buffers.images[index] = int(pointers[name])
-                    continue
-                address = C.c_void_p()
-                if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
-                    raise RuntimeError("no device memory for the %s image" % name)
-                owned[name] = address
-                buffers.images[index] = address.value
+                buffers.images[index] = int(pointers[name]) if pointers is not None else scratch.allocate(nbytes, "the %s image" % name)
             if self.lib.render_feature_buffers(C.byref(self.app), C.byref(buffers)):
                 raise RuntimeError("render_feature_buffers failed")
             if pointers is not None:
                 return None
             self.sync()
-            images = {}
-            for name, address in owned.items():
-                image = np.zeros((e.height, e.width, 4), np.uint32 if name == "identity" else np.float32)
-                if hip.hipMemcpy(image.ctypes.data, address, nbytes, 2):
-                    raise RuntimeError("reading the %s image back failed" % name)
-                images[name] = image
-            return images
-        finally:
-            if owned:
-                self.sync()
-            for address in owned.values():
-                hip.hipFree(address)
+            return {name: scratch.download(buffers.images[capi.PIXEL_FEATURES.index(name)], (e.height, e.width, 4), np.uint32 if name == "identity" else np.float32, "the %s image" % name)
+                    for name in names}
 
     def feature_preview(self, name, image_or_pointer, range=(0.0, 1.0), out_pointer=None):
         """The RGBA8 preview of a feature image (encode_feature_preview) - an array as render_features() returns it, which
@@ -687,39 +673,20 @@ class Renderer(HostScene):
         motion in pixels that saturates).  -> uint8 array (height, width, 4); with out_pointer, a device address, the
         preview stays there (for encode_png() / encode_jpeg()) and the call returns once the kernel is queued."""
         e = self.app.swapchain.extent
-        hip, owned = _hip_runtime(), []
-
-        def allocate(nbytes):
-            address = C.c_void_p()
-            if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
-                raise RuntimeError("no device memory for the preview")
-            owned.append(address)
-            return address.value
-        try:
+        with _DeviceScratch(self, "the preview") as scratch:
             source = image_or_pointer
             if isinstance(image_or_pointer, np.ndarray):
-                image = np.ascontiguousarray(image_or_pointer)
-                if image.shape != (e.height, e.width, 4) or image.dtype.itemsize != 4:
+                if image_or_pointer.shape != (e.height, e.width, 4) or image_or_pointer.dtype.itemsize != 4:
                     raise ValueError("a feature image is (height, width, 4) of 32-bit values")
-                source = allocate(image.nbytes)
-                if hip.hipMemcpy(source, image.ctypes.data, image.nbytes, 1):
-                    raise RuntimeError("uploading the feature image failed")
-            target = out_pointer if out_pointer is not None else allocate(e.width * e.height * 4)
+                source = scratch.upload(image_or_pointer, dtype=None, what="the feature image")
+            target = out_pointer if out_pointer is not None else scratch.allocate(e.width * e.height * 4)
             feature = capi.PIXEL_FEATURES.index(name) if isinstance(name, str) else int(name)
             if self.lib.encode_feature_preview(C.byref(self.app), feature, source, target, float(range[0]), float(range[1])):
                 raise RuntimeError("encode_feature_preview failed")
             if out_pointer is not None:
                 return None
             self.sync()
-            out = np.zeros((e.height, e.width, 4), np.uint8)
-            if hip.hipMemcpy(out.ctypes.data, target, out.nbytes, 2):
-                raise RuntimeError("reading the preview back failed")
-            return out
-        finally:
-            if owned:
-                self.sync()
-            for address in owned:
-                hip.hipFree(address)
+            return scratch.download(target, (e.height, e.width, 4), np.uint8, "the preview")
 
     # -- ray queries (include/vkr_ray_queries.h) ------------------------------------------
     def _trace(self, closest, origins, directions, t_min, t_max, cull_back_faces, walk, lds_stack_entries, rays_pointer, out_pointer, count, stream):
@@ -1029,13 +996,7 @@ class Renderer(HostScene):
         out_colour (and out_variance), device addresses, the results stay there, the call returns once the kernels are
         queued and gives nothing."""
         if frame_filter is None:
-            e = self.app.swapchain.extent
-            kept = getattr(self, "_kept_frame_filter", None)
-            if kept is None or not kept.filter.filtered or (kept.width, kept.height) != (e.width, e.height):
-                if kept is not None:
-                    kept.close()
-                kept = self._kept_frame_filter = self.create_frame_filter()
-            frame_filter = kept
+            frame_filter = self._kept_for_the_frame(FrameFilter)
         if modulation is None:
             modulation = features.get("diffuse_albedo")
         return frame_filter.apply(colour, variance, features["position"], features["normal"], modulation, settings, out_colour, out_variance)
@@ -1055,41 +1016,26 @@ class Renderer(HostScene):
         want_variance) as arrays; with out_colour (and out_variance), device addresses, the results stay there, the call
         returns once the kernels are queued and gives nothing."""
         if frame_history is None:
-            e = self.app.swapchain.extent
-            kept = getattr(self, "_kept_frame_history", None)
-            if kept is None or not kept.history.accumulated or (kept.width, kept.height) != (e.width, e.height):
-                if kept is not None:
-                    kept.close()
-                kept = self._kept_frame_history = self.create_frame_history()
-            frame_history = kept
+            frame_history = self._kept_for_the_frame(FrameHistory)
         return frame_history.accumulate(colour, features, settings, modulation, out_colour, out_variance, want_variance)
 
+    def _kept_for_the_frame(self, frame_object_class):
+        """The object of that class that the renderer keeps for the swapchain extent: made again when the extent changed
+        or somebody closed it"""
+        e = self.app.swapchain.extent
+        kept = self._kept_frame_objects.get(frame_object_class)
+        if kept is None or not kept.alive or (kept.width, kept.height) != (e.width, e.height):
+            if kept is not None:
+                kept.close()
+            kept = self._kept_frame_objects[frame_object_class] = frame_object_class(self)
+        return kept
+
     def close(self):
-        for statistics in list(getattr(self, "_statistics", ())):
-            statistics.close()
-        for frame_filter in list(getattr(self, "_frame_filters", ())):
-            frame_filter.close()
-        for frame_history in list(getattr(self, "_frame_histories", ())):
-            frame_history.close()
+        for frame_object in list(self._frame_objects):
+            frame_object.close()
         for encoder in self._file_encoders:
             encoder.close()
         super().close()
-
-
-_HIP_RUNTIME = None
-
-
-def _hip_runtime():
-    """The HIP runtime that the library has loaded, opened once, with the signatures of the three calls that the file
-    encoders' encode_image() makes"""
-    global _HIP_RUNTIME
-    if _HIP_RUNTIME is None:
-        hip = C.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes, hip.hipMalloc.restype = [C.POINTER(C.c_void_p), C.c_size_t], C.c_int
-        hip.hipMemcpy.argtypes, hip.hipMemcpy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
-        hip.hipFree.argtypes, hip.hipFree.restype = [C.c_void_p], C.c_int
-        _HIP_RUNTIME = hip
-    return _HIP_RUNTIME
 
 
 class _FileEncoder:
@@ -1207,273 +1153,6 @@ class HdrEncoder(_FileEncoder):
 
     def encode_on_device(self, pointer, out_pointer, capacity, size_pointer, channel_count=4, row_stride_bytes=0, through_half=False, stream=None):
         self._encode_on_device(pointer, out_pointer, capacity, size_pointer, channel_count, row_stride_bytes, stream, int(bool(through_half)))
-
-
-class FrameStatistics:
-    """Renderer.create_statistics(): sums of frames in binary64 on the device, mean and variance from them.  mean() and
-    variance() return numpy arrays (pixels, 4); mean_into() / variance_into() write device buffers instead."""
-
-    def __init__(self, owner, pixel_count=None):
-        self.owner = owner
-        self.lib = owner.lib
-        self.stats = capi.FrameStatistics()
-        if self.lib.create_frame_statistics(C.byref(self.stats), C.byref(owner.app), int(pixel_count or 0)):
-            raise RuntimeError("create_frame_statistics failed")
-        if not hasattr(owner, "_statistics"):
-            owner._statistics = []
-        owner._statistics.append(self)
-        self._hip = C.CDLL("libamdhip64.so")
-        self._scratch = C.c_void_p()
-
-    @property
-    def pixel_count(self):
-        return int(self.stats.pixel_count)
-
-    @property
-    def frame_count(self):
-        return int(self.stats.frame_count)
-
-    def accumulate(self, pointers=None):
-        """Adds the RGBA32F device buffers `pointers` (1 ... 8 addresses, in that order) with one kernel; None: the
-        radiance target.  Returns at once."""
-        if pointers is None:
-            array, count = None, 1
-        else:
-            values = [int(getattr(p, "value", p) or 0) for p in pointers]
-            array, count = (C.c_void_p * len(values))(*values), len(values)
-        if self.lib.accumulate_frames(C.byref(self.stats), C.byref(self.owner.app), array, count):
-            raise RuntimeError("accumulate_frames failed")
-
-    def resolve(self, mean_pointer=None, variance_pointer=None):
-        """Writes mean and / or variance into RGBA32F device buffers (resolve_frame_statistics)"""
-        if self.lib.resolve_frame_statistics(C.byref(self.stats), C.byref(self.owner.app), mean_pointer, variance_pointer):
-            raise RuntimeError("resolve_frame_statistics failed")
-
-    def _resolved(self, want_variance):
-        nbytes = 16 * self.pixel_count
-        if not self._scratch and self._hip.hipMalloc(C.byref(self._scratch), C.c_size_t(nbytes)):
-            raise RuntimeError("out of device memory for the resolved statistics")
-        self.resolve(None if want_variance else self._scratch, self._scratch if want_variance else None)
-        out = np.zeros((self.pixel_count, 4), np.float32)
-        # (ordered behind the resolve on the device's stream)
-        if self.lib.wait_for_device(C.byref(self.owner.app.device)) or self._hip.hipMemcpy(C.c_void_p(out.ctypes.data), self._scratch, C.c_size_t(nbytes), 2):
-            raise RuntimeError("reading the resolved statistics back failed")
-        return out
-
-    def mean(self):
-        return self._resolved(False)
-
-    def variance(self):
-        return self._resolved(True)
-
-    def sums(self):
-        """(S, Q): the accumulators as float64 arrays (pixels, 3)"""
-        sums, squares = np.zeros((self.pixel_count, 3), np.float64), np.zeros((self.pixel_count, 3), np.float64)
-        if self.lib.read_back_frame_statistics(C.byref(self.stats), C.byref(self.owner.app), sums.ctypes.data, squares.ctypes.data):
-            raise RuntimeError("read_back_frame_statistics failed")
-        return sums, squares
-
-    def reset(self):
-        if self.lib.reset_frame_statistics(C.byref(self.stats), C.byref(self.owner.app)):
-            raise RuntimeError("reset_frame_statistics failed")
-
-    def close(self):
-        if self.stats.sums:
-            self.lib.destroy_frame_statistics(C.byref(self.stats), C.byref(self.owner.app))
-        if self._scratch:
-            self._hip.hipFree(self._scratch)
-            self._scratch = C.c_void_p()
-        if self in getattr(self.owner, "_statistics", ()):
-            self.owner._statistics.remove(self)
-
-
-class FrameFilter:
-    """Renderer.create_frame_filter(): the scratch images and the event of filter_frame() for one extent"""
-
-    def __init__(self, owner, width=None, height=None):
-        self.owner = owner
-        self.lib = owner.lib
-        self.filter = capi.FrameFilter()
-        if self.lib.create_frame_filter(C.byref(self.filter), C.byref(owner.app), int(width or 0), int(height or 0)):
-            raise RuntimeError("create_frame_filter failed")
-        if not hasattr(owner, "_frame_filters"):
-            owner._frame_filters = []
-        owner._frame_filters.append(self)
-
-    @property
-    def width(self):
-        return int(self.filter.width)
-
-    @property
-    def height(self):
-        return int(self.filter.height)
-
-    def filter_settings(self, settings=None):
-        from . import frame_filter
-        values = dict(frame_filter.DEFAULT_SETTINGS, **(settings or {}))
-        return capi.FrameFilterSettings(int(values["iteration_count"]), int(values["normal_squarings"]), float(values["sigma_luminance"]),
-                                        float(values["sigma_depth"]), float(values["variance_scale"]))
-
-    def apply(self, colour, variance, position, normal, modulation=None, settings=None, out_colour=None, out_variance=None):
-        """See Renderer.filter_frame()"""
-        shape = (self.height, self.width, 4)
-        nbytes = 16 * self.width * self.height
-        hip, owned = _hip_runtime(), []
-
-        def allocate():
-            address = C.c_void_p()
-            if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
-                raise RuntimeError("no device memory for an image of the filter")
-            owned.append(address)
-            return address.value
-
-        def on_device(image):
-            if image is None or not isinstance(image, np.ndarray):
-                return None if image is None else int(getattr(image, "value", image) or 0)
-            image = np.ascontiguousarray(image, np.float32)
-            if image.shape != shape:
-                raise ValueError("an image of this filter is %r, not %r" % (shape, image.shape))
-            address = allocate()
-            if hip.hipMemcpy(address, image.ctypes.data, nbytes, 1):
-                raise RuntimeError("uploading an image of the filter failed")
-            return address
-        try:
-            images = capi.FrameFilterImages(on_device(colour), on_device(variance), on_device(position), on_device(normal), on_device(modulation))
-            stays = out_colour is not None
-            images.out_colour = int(getattr(out_colour, "value", out_colour)) if stays else allocate()
-            if out_variance is not None:
-                images.out_variance = int(getattr(out_variance, "value", out_variance))
-            elif not stays and variance is not None:
-                images.out_variance = allocate()
-            if self.lib.filter_frame(C.byref(self.filter), C.byref(self.owner.app), C.byref(self.filter_settings(settings)), C.byref(images)):
-                raise RuntimeError("filter_frame failed")
-            if stays:
-                return None
-            self.owner.sync()
-            results = []
-            for address in (images.out_colour, images.out_variance):
-                results.append(None)
-                if address:
-                    results[-1] = np.zeros(shape, np.float32)
-                    if hip.hipMemcpy(results[-1].ctypes.data, address, nbytes, 2):
-                        raise RuntimeError("reading the filtered image back failed")
-            return tuple(results)
-        finally:
-            if owned:
-                self.owner.sync()
-            for address in owned:
-                hip.hipFree(address)
-
-    def close(self):
-        if self.filter.filtered:
-            self.lib.destroy_frame_filter(C.byref(self.filter), C.byref(self.owner.app))
-        if self in getattr(self.owner, "_frame_filters", ()):
-            self.owner._frame_filters.remove(self)
-
-
-class FrameHistory:
-    """Renderer.create_frame_history(): the two sets of history images and the event of accumulate_frame_history() for one
-    extent"""
-
-    def __init__(self, owner, width=None, height=None):
-        self.owner = owner
-        self.lib = owner.lib
-        self.history = capi.FrameHistory()
-        if self.lib.create_frame_history(C.byref(self.history), C.byref(owner.app), int(width or 0), int(height or 0)):
-            raise RuntimeError("create_frame_history failed")
-        if not hasattr(owner, "_frame_histories"):
-            owner._frame_histories = []
-        owner._frame_histories.append(self)
-
-    @property
-    def width(self):
-        return int(self.history.width)
-
-    @property
-    def height(self):
-        return int(self.history.height)
-
-    @property
-    def frame_count(self):
-        return int(self.history.frame_count)
-
-    def history_settings(self, settings=None):
-        from . import frame_history
-        values = dict(frame_history.DEFAULT_SETTINGS, **(settings or {}))
-        return capi.FrameHistorySettings(float(values["max_length"]), float(values["sigma_depth"]), float(values["normal_threshold"]), int(values["spatial_length"]))
-
-    def reset(self):
-        """The next frame finds no history"""
-        self.lib.reset_frame_history(C.byref(self.history))
-
-    def read(self):
-        """-> {"colour", "moments", "position", "normal"}: the set that the last call wrote, as arrays (height, width, 4)"""
-        self.owner.sync()
-        hip, images = _hip_runtime(), {}
-        for name in ("colour", "moments", "position", "normal"):
-            images[name] = np.zeros((self.height, self.width, 4), np.float32)
-            if hip.hipMemcpy(images[name].ctypes.data, getattr(self.history, name)[self.history.current], images[name].nbytes, 2):
-                raise RuntimeError("reading an image of the history back failed")
-        return images
-
-    def accumulate(self, colour, features, settings=None, modulation=None, out_colour=None, out_variance=None, want_variance=True):
-        """See Renderer.accumulate_history()"""
-        shape = (self.height, self.width, 4)
-        nbytes = 16 * self.width * self.height
-        hip, owned = _hip_runtime(), []
-
-        def allocate():
-            address = C.c_void_p()
-            if hip.hipMalloc(C.byref(address), max(nbytes, 16)):
-                raise RuntimeError("no device memory for an image of the history")
-            owned.append(address)
-            return address.value
-
-        def on_device(image):
-            if image is None or not isinstance(image, np.ndarray):
-                return None if image is None else int(getattr(image, "value", image) or 0)
-            image = np.ascontiguousarray(image, np.float32)
-            if image.shape != shape:
-                raise ValueError("an image of this history is %r, not %r" % (shape, image.shape))
-            address = allocate()
-            if hip.hipMemcpy(address, image.ctypes.data, nbytes, 1):
-                raise RuntimeError("uploading an image of the history failed")
-            return address
-        if modulation is None:
-            modulation = features.get("diffuse_albedo")
-        try:
-            images = capi.FrameHistoryImages(on_device(colour), on_device(features["position"]), on_device(features["normal"]),
-                                             on_device(features.get("reprojection")), on_device(modulation))
-            stays = out_colour is not None
-            images.out_colour = int(getattr(out_colour, "value", out_colour)) if stays else allocate()
-            if out_variance is not None:
-                images.out_variance = int(getattr(out_variance, "value", out_variance))
-            elif not stays and want_variance:
-                images.out_variance = allocate()
-            if self.lib.accumulate_frame_history(C.byref(self.history), C.byref(self.owner.app), C.byref(self.history_settings(settings)), C.byref(images)):
-                raise RuntimeError("accumulate_frame_history failed")
-            if stays:
-                return None
-            self.owner.sync()
-            results = []
-            for address in (images.out_colour, images.out_variance):
-                results.append(None)
-                if address:
-                    results[-1] = np.zeros(shape, np.float32)
-                    if hip.hipMemcpy(results[-1].ctypes.data, address, nbytes, 2):
-                        raise RuntimeError("reading the accumulated image back failed")
-            return tuple(results)
-        finally:
-            if owned:
-                self.owner.sync()
-            for address in owned:
-                hip.hipFree(address)
-
-    def close(self):
-        if self.history.accumulated:
-            self.lib.destroy_frame_history(C.byref(self.history), C.byref(self.owner.app))
-        if self in getattr(self.owner, "_frame_histories", ()):
-            self.owner._frame_histories.remove(self)
 
 
 def frames_in_flight_for(rank_count):
