@@ -26,7 +26,8 @@
  *         X = (c_0 / c_3 + 1) * (0.5f * width) - 0.5f,  Y = (c_1 / c_3 + 1) * (0.5f * height) - 0.5f
  *       X, Y are pixel indices: pixel p has its centre at NDC (2 p + 1) / extent - 1, the convention of write_constants().
  *       The pixel is {X, Y, c_3, inside}; inside = 1.0f if c_3 > 0, X >= -0.5, X < width - 0.5, Y >= -0.5 and
- *       Y < height - 0.5 (a NaN fails every comparison), else 0.0f.  The reprojection sees the camera only, not moving geometry.
+ *       Y < height - 0.5 (a NaN fails every comparison), else 0.0f.  The reprojection sees the camera only, not moving geometry:
+ *       render_motion_buffers() (vkr_motion_buffers.h) writes the same image for a mesh that update_scene_geometry() moved.
  *
  * Previews.  encode_feature_preview() turns a feature image into width * height RGBA8 pixels that encode_png*() and
  * encode_jpeg*() take as they are; alpha is 255.  u8(x): clamp to [0, 1], x * 255 + 0.5, truncate; a NaN gives 0.

@@ -2,7 +2,8 @@
  * found where each pixel was under the previous camera (pixel_feature_reprojection of render_feature_buffers(), rendered
  * with the PREVIOUS frame's world_to_projection_space), and gives the accumulated colour and its variance: what
  * filter_frame() takes as colour and variance with variance_scale 1.  The history is two sets of four images that take
- * turns; it sees the camera only, not moving geometry.  No reference counterpart.
+ * turns.  accumulate_frame_history() sees the camera only; accumulate_moving_frame_history() follows geometry that
+ * update_scene_geometry() moved, with the images of render_motion_buffers() (the last paragraph).  No reference counterpart.
  *
  * All arithmetic is IEEE binary32 with every operation rounded on its own (nothing contracted, denormals kept), in an order
  * that is part of the interface: vulkan_renderer_amd/frame_history.py restates it in numpy, bit for bit.  a / b is the
@@ -63,7 +64,16 @@
  *     v = gmax(0, M2 - M1 * M1) * (1 / n'_p),   out_variance[p] = {v * (m * m), 1}
  * Every other pixel keeps what the first launch wrote.
  *
- * Then current ^= 1 and frame_count += 1. */
+ * Then current ^= 1 and frame_count += 1.
+ *
+ * Moving geometry.  accumulate_moving_frame_history() takes reprojection from render_motion_buffers()
+ * (include/vkr_motion_buffers.h), which looks the pixel's surface up where it was, and that call's previous_position
+ * image.  The rule above has one change: in the tap test of "A tap counts iff", P_p = previous_position[p].xyz - the
+ * point whose history the tap holds, in the world space of the frame that stored it, so that a surface that moved by more
+ * than sigma_depth * position_p.w along its normal still finds its history.  n_p and the scale position_p.w stay this
+ * frame's: the normals of the previous frame are not kept, and a rotation of one frame's worth is what normal_threshold and
+ * sigma_depth already have to tolerate.  The stores (h'.position gets position[p]), the spatial variance launch, coverage,
+ * the order of the checks and every refusal are unchanged. */
 #ifndef VKR_FRAME_HISTORY_H
 #define VKR_FRAME_HISTORY_H
 #include "vkr_frame_filter.h"
@@ -115,5 +125,11 @@ VKR_API void reset_frame_history(frame_history_t* history);
 	and the history as it was, for a missing or misaligned image, settings outside their ranges (a NaN fails), a history
 	that was not created, and an output that overlaps an input, the other output or an image of the history. */
 VKR_API int accumulate_frame_history(frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images);
+/*! accumulate_frame_history() for geometry that moved ("Moving geometry" above).  previous_position: device, the
+	previous_position image of render_motion_buffers() for this frame, width * height pixels of 16 bytes, 16-byte aligned;
+	it is one more input: no output may overlap it, and the call is noted as its reader.  NULL: accumulate_frame_history(),
+	in every byte. */
+VKR_API int accumulate_moving_frame_history(frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images,
+	const void* previous_position);
 
 #endif

@@ -270,6 +270,14 @@ class FeatureBuffers(C.Structure):
     _fields_ = [("images", C.c_void_p * len(PIXEL_FEATURES)), ("reprojection_matrix", (C.c_float * 4) * 4)]
 
 
+# the images of include/vkr_motion_buffers.h, in the order of motion_buffers_t
+MOTION_IMAGES = ("reprojection", "previous_position", "motion")
+
+
+class MotionBuffers(C.Structure):
+    _fields_ = [("previous_positions", C.c_void_p), ("previous_matrix", (C.c_float * 4) * 4)] + [(name, C.c_void_p) for name in MOTION_IMAGES]
+
+
 # include/vkr_frame_filter.h
 FRAME_FILTER_MAX_ITERATIONS, FRAME_FILTER_MAX_NORMAL_SQUARINGS, FRAME_FILTER_MAX_EXTENT = 5, 8, 32768
 
@@ -483,6 +491,8 @@ SIGNATURES = {
     "destroy_frame_history": (None, [P(FrameHistory), P(Application)]),
     "reset_frame_history": (None, [P(FrameHistory)]),
     "accumulate_frame_history": (C.c_int, [P(FrameHistory), P(Application), P(FrameHistorySettings), P(FrameHistoryImages)]),
+    "accumulate_moving_frame_history": (C.c_int, [P(FrameHistory), P(Application), P(FrameHistorySettings), P(FrameHistoryImages), C.c_void_p]),
+    "render_motion_buffers": (C.c_int, [P(Application), P(MotionBuffers)]),
     "update_scene_geometry": (C.c_int, [P(Scene), P(Device), C.c_void_p, C.c_void_p, P(SceneUpdateOptions), P(SceneUpdateReport)]),
 }
 

@@ -1,6 +1,6 @@
 // Frame history (include/vkr_frame_history.h): the frame blended into a history that is fetched where each pixel was under
-// the previous camera, and the variance of the result.  One launch accumulates; a second one replaces the variance of
-// pixels with a short history by a spatial estimate.  Compiled without contraction in the exact mode's flags, whatever the
+// the previous camera - or, with the images of render_motion_buffers(), where its surface was -, and the variance of the
+// result.  One launch accumulates; a second one replaces the variance of pixels with a short history by a spatial estimate.  Compiled without contraction in the exact mode's flags, whatever the
 // arithmetic mode of the pass; every result is restated in numpy bit for bit (vulkan_renderer_amd/frame_history.py).
 #include "vkr_frame_history.h"
 #include "frame_images.h"
@@ -9,10 +9,10 @@ using namespace vkr;
 
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
-// One call: the caller's images (reprojection, modulation, out_variance: NULL when not given), the set h that is read (only
-// with has_history) and the set h' that is written, and the settings.  All wave-uniform.
+// One call: the caller's images (reprojection, modulation, previous_position, out_variance: NULL when not given), the set h
+// that is read (only with has_history) and the set h' that is written, and the settings.  All wave-uniform.
 struct history_frame {
-	const float4 *colour, *position, *normal, *reprojection, *modulation;
+	const float4 *colour, *position, *normal, *reprojection, *modulation, *previous_position;
 	const float4 *old_colour, *old_moments, *old_position, *old_normal;
 	float4 *new_colour, *new_moments, *new_position, *new_normal;
 	float4 *out_colour, *out_variance;
@@ -28,8 +28,9 @@ VKR_DEV bool same_surface(const history_frame& f, f3 P_p, f3 n_p, float d_z, f3 
 
 // The sixteen loads of the four taps are issued together, before the verdict on any of them (a tap out of the frame, and
 // every tap of a pixel that is not usable, reads the lane's own pixel and is not used): sixteen loads in flight per lane
-// instead of four chains of four.  The first frame of a history reads no history at all.
-template <bool VARIANCE>
+// instead of four chains of four.  The first frame of a history reads no history at all.  MOVING
+// (accumulate_moving_frame_history()): the taps' positions are compared with where the pixel's surface was, one more load.
+template <bool VARIANCE, bool MOVING>
 __global__ void __launch_bounds__(256) k_accumulate_history(const history_frame f) {
 	uint32_t lx, ly;
 	lane_pixel(lx, ly);
@@ -72,7 +73,9 @@ __global__ void __launch_bounds__(256) k_accumulate_history(const history_frame 
 			tap_colour[k] = f.old_colour[q];
 			tap_moments[k] = f.old_moments[q];
 		}
-		const f3 P_p = rgb(position_p), n_p = rgb(normal_p);
+		f3 P_p = rgb(position_p);
+		if (MOVING) P_p = rgb(f.previous_position[p]);
+		const f3 n_p = rgb(normal_p);
 		const float d_z = f.sigma_depth * position_p.w;
 #pragma unroll
 		for (int k = 0; k != 4; ++k) {
@@ -201,23 +204,24 @@ extern "C" void reset_frame_history(frame_history_t* history) {
 	if (history) history->frame_count = 0;
 }
 
-extern "C" int accumulate_frame_history(frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images) {
+// Both entry points; `function`: the caller's name, for messages
+static int accumulate(const char* function, frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images, const void* previous_position) {
 	if (!history || !app || !settings || !images) {
-		printf("accumulate_frame_history() needs a history, an application, settings and images.\n");
+		printf("%s() needs a history, an application, settings and images.\n", function);
 		return 1;
 	}
 	// (written so that a NaN fails)
 	if (!(settings->max_length >= 1.0f && settings->max_length < INFINITY) || !(settings->sigma_depth > 0.0f && settings->sigma_depth < INFINITY)
 		|| !(settings->normal_threshold >= -1.0f && settings->normal_threshold <= 1.0f) || settings->spatial_length > VKR_FRAME_HISTORY_MAX_SPATIAL_LENGTH)
 	{
-		printf("accumulate_frame_history() takes a finite largest length >= 1, a finite sigma of the depth > 0, a normal threshold from -1 to 1 and a spatial length up to %d.\n", VKR_FRAME_HISTORY_MAX_SPATIAL_LENGTH);
+		printf("%s() takes a finite largest length >= 1, a finite sigma of the depth > 0, a normal threshold from -1 to 1 and a spatial length up to %d.\n", function, VKR_FRAME_HISTORY_MAX_SPATIAL_LENGTH);
 		return 1;
 	}
-	const frame_call call = {"accumulate_frame_history", {images->colour, images->position, images->normal, images->reprojection, images->modulation}, {images->out_colour, images->out_variance}};
+	const frame_call call = {function, {images->colour, images->position, images->normal, images->reprojection, images->modulation, previous_position}, {images->out_colour, images->out_variance}};
 	if (check_frame_call_images(call, images->colour && images->position && images->normal && images->out_colour)) return 1;
 	const frame_image_set own = images_of(history);
 	if (!frame_images_created(own) || history->current >= 2) {
-		printf("accumulate_frame_history() needs a history created by create_frame_history().\n");
+		printf("%s() needs a history created by create_frame_history().\n", function);
 		return 1;
 	}
 	const size_t bytes = frame_image_bytes(own);
@@ -230,6 +234,7 @@ extern "C" int accumulate_frame_history(frame_history_t* history, application_t*
 	f.normal = (const float4*) images->normal;
 	f.reprojection = (const float4*) images->reprojection;
 	f.modulation = (const float4*) images->modulation;
+	f.previous_position = (const float4*) previous_position;
 	f.old_colour = (const float4*) history->colour[old_set];
 	f.old_moments = (const float4*) history->moments[old_set];
 	f.old_position = (const float4*) history->position[old_set];
@@ -248,8 +253,12 @@ extern "C" int accumulate_frame_history(frame_history_t* history, application_t*
 	f.normal_threshold = settings->normal_threshold;
 	f.spatial_length = (float) settings->spatial_length;
 	dim3 grid((f.width + 15) / 16, (f.height + 15) / 16);
-	if (images->out_variance) k_accumulate_history<true><<<grid, 256, 0, stream>>>(f);
-	else k_accumulate_history<false><<<grid, 256, 0, stream>>>(f);
+	if (previous_position) {
+		if (images->out_variance) k_accumulate_history<true, true><<<grid, 256, 0, stream>>>(f);
+		else k_accumulate_history<false, true><<<grid, 256, 0, stream>>>(f);
+	}
+	else if (images->out_variance) k_accumulate_history<true, false><<<grid, 256, 0, stream>>>(f);
+	else k_accumulate_history<false, false><<<grid, 256, 0, stream>>>(f);
 	if (hip_failed(hipGetLastError(), "accumulating a frame")) return 1;
 	if (images->out_variance && settings->spatial_length) {
 		k_history_spatial_variance<<<grid, 256, 0, stream>>>(f);
@@ -259,4 +268,12 @@ extern "C" int accumulate_frame_history(frame_history_t* history, application_t*
 	// (a counter that wrapped to 0 would drop the history)
 	if (history->frame_count != UINT32_MAX) ++history->frame_count;
 	return finish_frame_call(call, app, bytes, history->accumulated, "marking the accumulated frame");
+}
+
+extern "C" int accumulate_frame_history(frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images) {
+	return accumulate("accumulate_frame_history", history, app, settings, images, NULL);
+}
+
+extern "C" int accumulate_moving_frame_history(frame_history_t* history, application_t* app, const frame_history_settings_t* settings, const frame_history_images_t* images, const void* previous_position) {
+	return accumulate("accumulate_moving_frame_history", history, app, settings, images, previous_position);
 }

@@ -42,7 +42,7 @@ VKR_DEV void lane_pixel(uint32_t& lx, uint32_t& ly) {
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-constexpr uint32_t kMaxFrameImages = 8, kFrameCallInputs = 5, kFrameCallOutputs = 2;
+constexpr uint32_t kMaxFrameImages = 8, kFrameCallInputs = 6, kFrameCallOutputs = 2;
 
 // The images and the event that an object owns, as pointers into its public struct
 struct frame_image_set {

@@ -38,5 +38,9 @@ VKR_DECLARE_MODE_LAUNCHES(sampler_launch_function_t, vkr_launch_texture_sampler,
 // pointers, NULL = not wanted; reprojection: the sixteen floats of the caller's matrix, row-major; textured: sample the
 // material textures in the kernel (p->texture_descriptors, texels, srgb_table set)
 VKR_DECLARE_MODE_LAUNCHES(feature_launch_function_t, vkr_launch_feature_buffers, const vkr::shade_params* p, void* const* images, const float* reprojection, int textured, void* stream)
+// k_motion_buffers (motion_buffers_variants.hip; include/vkr_motion_buffers.h): previous_positions: device, the layout of
+// p->positions; images: three device pointers - reprojection, previous_position, motion -, NULL = not wanted;
+// previous_matrix: the sixteen floats of the caller's matrix, row-major
+VKR_DECLARE_MODE_LAUNCHES(motion_launch_function_t, vkr_launch_motion_buffers, const vkr::shade_params* p, const void* previous_positions, void* const* images, const float* previous_matrix, void* stream)
 // [arithmetic_mode_t]
 #define VKR_MODE_LAUNCHERS(name) {name##_libm, name##_fast, name##_exact}

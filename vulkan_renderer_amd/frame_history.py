@@ -50,17 +50,20 @@ def same_surface(P_p, n_p, d_z, P_q, n_q, normal_threshold):
     return np.abs(dot3(n_p, P_q - P_p)) <= d_z, dot3(n_p, n_q) >= normal_threshold
 
 
-def accumulate(state, colour, position, normal, reprojection=None, modulation=None, settings=None, diagnostics=None):
-    """accumulate_frame_history() on float32 images (height, width, 4); reprojection and modulation may be None.  state: what
+def accumulate(state, colour, position, normal, reprojection=None, modulation=None, settings=None, diagnostics=None, previous_position=None):
+    """accumulate_frame_history() on float32 images (height, width, 4); reprojection and modulation may be None; with
+    previous_position, the image of render_motion_buffers(), accumulate_moving_frame_history().  state: what
     new_state() or an earlier call gave.  -> (the new state, out_colour, out_variance); out_variance is what the call writes
     when it is given the image (without it the other results are the same).  diagnostics: a dict that gets the number of
     taps rejected per TAP_REJECTIONS and the number of pixels per PIXEL_CLASSES."""
     with np.errstate(all="ignore"):
-        return _accumulate(state, colour, position, normal, reprojection, modulation, check_settings(settings or {}), diagnostics)
+        return _accumulate(state, colour, position, normal, reprojection, modulation, check_settings(settings or {}), diagnostics, previous_position)
 
 
-def _accumulate(state, colour, position, normal, reprojection, modulation, settings, diagnostics):
+def _accumulate(state, colour, position, normal, reprojection, modulation, settings, diagnostics, previous_position):
     colour, position, normal = (np.ascontiguousarray(a, f32) for a in (colour, position, normal))
+    if previous_position is not None and np.shape(previous_position) != colour.shape:
+        raise ValueError("images are (height, width, 4), of the history's extent")
     if colour.ndim != 3 or colour.shape[2] != 4 or position.shape != colour.shape or normal.shape != colour.shape or state["colour"].shape != colour.shape:
         raise ValueError("images are (height, width, 4), of the history's extent")
     height, width = colour.shape[:2]
@@ -69,6 +72,8 @@ def _accumulate(state, colour, position, normal, reprojection, modulation, setti
     ys, xs = np.mgrid[0:height, 0:width]
     covered = position[..., 3] > 0
     P_p, n_p = position[..., :3], normal[..., :3]
+    # where the pixel's surface was: what the taps of the history are compared with ("Moving geometry" of the header)
+    P_was = P_p if previous_position is None else np.ascontiguousarray(previous_position, f32)[..., :3]
     d_z = sigma_depth * position[..., 3]
     counts = dict.fromkeys(TAP_REJECTIONS + PIXEL_CLASSES, 0)
     # prepare
@@ -102,7 +107,7 @@ def _accumulate(state, colour, position, normal, reprojection, modulation, setti
         b = (tx if k & 1 else f32(1.0) - tx) * (ty if k >> 1 else f32(1.0) - ty)
         has_weight = b > 0
         tap_covered = state["position"][qy, qx, 3] > 0
-        plane, facing = same_surface(P_p, n_p, d_z, state["position"][qy, qx, :3], state["normal"][qy, qx, :3], normal_threshold)
+        plane, facing = same_surface(P_was, n_p, d_z, state["position"][qy, qx, :3], state["normal"][qy, qx, :3], normal_threshold)
         left = considered
         for name, passed in zip(TAP_REJECTIONS, (inside, has_weight, tap_covered, plane, facing)):
             counts[name] += int((left & ~passed).sum())
@@ -173,12 +178,14 @@ def main(arguments=None):
     import math
     import os
 
-    from . import feature_buffers, frame_images
+    from . import feature_buffers, frame_images, scene_update
     parser = argparse.ArgumentParser(prog="python -m vulkan_renderer_amd.frame_history",
-                                     description="Renders frames of a dataset with animated noise while the camera turns, accumulates them in a reprojected history on the device and writes the last noisy frame, the accumulated and the filtered image.")
+                                     description="Renders frames of a dataset with animated noise while the camera turns and, with --move, its mesh wobbles, accumulates them in a reprojected history on the device and writes the last noisy frame, the accumulated and the filtered image.")
     frame_images.add_dataset_arguments(parser)
     parser.add_argument("--frames", type=int, default=8)
     parser.add_argument("--turn", type=float, default=0.0, metavar="DEGREES", help="about the vertical axis, over all frames")
+    parser.add_argument("--move", type=float, default=None, metavar="AMPLITUDE", help="the mesh moves every frame by the wobble of vulkan_renderer_amd.scene_update, in world units; the history follows it through the motion buffers")
+    parser.add_argument("--no-motion", action="store_true", help="with --move: the camera-only reprojection of the feature buffers instead of the motion buffers")
     parser.add_argument("--max-length", type=float, default=DEFAULT_SETTINGS["max_length"])
     parser.add_argument("--filter", action="store_true", help="filter_frame() on the accumulated image and its variance (without it the filtered image is the accumulated one)")
     frame_images.add_output_arguments(parser)
@@ -191,17 +198,30 @@ def main(arguments=None):
         pixels = extent.width * extent.height
         noisy, accumulated, variance, filtered = (scratch.allocate(16 * pixels) for _ in range(4))
         features = {name: scratch.allocate(16 * pixels) for name in ("position", "normal", "diffuse_albedo", "reprojection")}
+        with_motion = options.move is not None and not options.no_motion
+        if with_motion:
+            features["previous_position"] = scratch.allocate(16 * pixels)
         history = scene.create_frame_history()
         camera = scene.app.scene_specification.camera
         step = math.radians(options.turn) / max(options.frames - 1, 1)
-        previous = None
-        for _ in range(options.frames):
+        motion = scene_update.Wobble(scene, options.move) if options.move is not None else None
+        previous, previous_words = None, None
+        for frame in range(options.frames):
+            if motion:
+                words = motion.words(frame)
+                scene.update_geometry(words)
             scene.render_visibility()
             matrix = feature_buffers.world_to_projection_space(scene.constants())
             scene.render(noisy)
-            scene.render_features(list(features), previous if previous is not None else matrix, pointers=features)
+            if with_motion:
+                scene.render_features(["position", "normal", "diffuse_albedo"], pointers=features)
+                scene.render_motion(previous_words, previous if previous is not None else matrix, ["reprojection", "previous_position"], pointers=features)
+            else:
+                scene.render_features(["position", "normal", "diffuse_albedo", "reprojection"], previous if previous is not None else matrix, pointers=features)
             history.accumulate(noisy, features, dict(max_length=options.max_length), out_colour=accumulated, out_variance=variance)
             previous = matrix
+            if motion:
+                previous_words = words
             camera.rotation_z += step
         if options.filter:
             scene.filter_frame(accumulated, variance, features, dict(variance_scale=1.0), out_colour=filtered)

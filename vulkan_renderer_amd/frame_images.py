@@ -186,22 +186,26 @@ class _FrameImageObject(_FrameObject):
     def height(self):
         return int(self.struct.height)
 
-    def _call(self, inputs, settings, out_colour, out_variance, want_variance):
+    def _call(self, inputs, settings, out_colour, out_variance, want_variance, call=None, further=()):
         """inputs: device addresses, None or float32 arrays (height, width, 4), which are uploaded, in the order of the
         images struct; settings: the struct.  With out_colour the results stay on the device (out_variance too, if given)
-        and the call gives nothing; else -> (colour, variance or None without want_variance) as arrays."""
+        and the call gives nothing; else -> (colour, variance or None without want_variance) as arrays.  call: another C
+        function than CALL, which takes the images `further`, given like inputs, behind the images struct."""
+        call = call or self.CALL
         shape = (self.height, self.width, 4)
         nbytes = 16 * self.width * self.height
         with _DeviceScratch(self.owner, "an image of the %s" % self.NOUN, "an image of this %s" % self.NOUN) as scratch:
-            images = self.IMAGES(*(scratch.upload(image, shape) if isinstance(image, np.ndarray) else (None if image is None else _address(image)) for image in inputs))
+            def address(image):
+                return scratch.upload(image, shape) if isinstance(image, np.ndarray) else (None if image is None else _address(image))
+            images = self.IMAGES(*(address(image) for image in inputs))
             stays = out_colour is not None
             images.out_colour = _address(out_colour) if stays else scratch.allocate(nbytes)
             if out_variance is not None:
                 images.out_variance = _address(out_variance)
             elif not stays and want_variance:
                 images.out_variance = scratch.allocate(nbytes)
-            if getattr(self.lib, self.CALL)(C.byref(self.struct), C.byref(self.owner.app), C.byref(settings), C.byref(images)):
-                raise RuntimeError("%s failed" % self.CALL)
+            if getattr(self.lib, call)(C.byref(self.struct), C.byref(self.owner.app), C.byref(settings), C.byref(images), *(address(image) for image in further)):
+                raise RuntimeError("%s failed" % call)
             if stays:
                 return None
             self.owner.sync()
@@ -262,7 +266,9 @@ class FrameHistory(_FrameImageObject):
         if modulation is None:
             modulation = features.get("diffuse_albedo")
         inputs = (colour, features["position"], features["normal"], features.get("reprojection"), modulation)
-        return self._call(inputs, self.history_settings(settings), out_colour, out_variance, want_variance)
+        if features.get("previous_position") is None:
+            return self._call(inputs, self.history_settings(settings), out_colour, out_variance, want_variance)
+        return self._call(inputs, self.history_settings(settings), out_colour, out_variance, want_variance, "accumulate_moving_frame_history", (features["previous_position"],))
 
 
 # ---- what the command lines share ---------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from . import capi
-from .frame_images import FrameFilter, FrameHistory, FrameStatistics, _DeviceScratch, _hip_runtime  # noqa: F401 (used under this module's name)
+from .frame_images import FrameFilter, FrameHistory, FrameStatistics, _address, _DeviceScratch, _hip_runtime  # noqa: F401 (used under this module's name)
 
 STRATEGY = {"diffuse_only": 0, "diffuse_ggx_mis": 1, "diffuse_specular_separately": 2,
             "diffuse_specular_mis": 3, "diffuse_specular_random": 4}
@@ -667,6 +667,41 @@ class Renderer(HostScene):
             return {name: scratch.download(buffers.images[capi.PIXEL_FEATURES.index(name)], (e.height, e.width, 4), np.uint32 if name == "identity" else np.float32, "the %s image" % name)
                     for name in names}
 
+    # -- motion buffers (include/vkr_motion_buffers.h) --------------------------------------
+    def render_motion(self, previous_positions, previous_matrix, names=capi.MOTION_IMAGES, pointers=None):
+        """The motion images of the current frame (render_motion_buffers): names out of capi.MOTION_IMAGES.
+        previous_positions: the position words of the mesh before the last update_geometry(), an array as that call takes
+        it - (3 T, 2) uint32, which is uploaded - or a device address; None: nothing moved.  previous_matrix: the (4, 4)
+        world_to_projection_space of the previous frame.  -> {name: float32 array (height, width, 4)}.  With pointers,
+        {name: device address} for every name, the images stay on the device, the call returns once the kernel is queued
+        and gives nothing (previous_positions as an array is then waited for: it is freed on the way out)."""
+        names = [names] if isinstance(names, str) else list(names)
+        buffers = capi.MotionBuffers()
+        matrix = np.ascontiguousarray(previous_matrix, np.float32).reshape(4, 4)
+        for i in range(4):
+            buffers.previous_matrix[i][:] = [float(v) for v in matrix[i]]
+        e = self.app.swapchain.extent
+        nbytes = e.width * e.height * 16
+        with _DeviceScratch(self, "the motion images") as scratch:
+            if isinstance(previous_positions, np.ndarray):
+                words = np.ascontiguousarray(previous_positions, np.uint32)
+                vertex_count = 3 * int(self.app.scene.mesh.triangle_count)
+                if words.size != 2 * vertex_count:
+                    raise ValueError("expected %d x 2 uint32 for the %d triangles of the mesh, got %d values" % (vertex_count, vertex_count // 3, words.size))
+                buffers.previous_positions = scratch.upload(words, dtype=None, what="the previous positions")
+            elif previous_positions is not None:
+                buffers.previous_positions = _address(previous_positions)
+            for name in names:
+                if name not in capi.MOTION_IMAGES:
+                    raise ValueError("%r is no motion image (%s)" % (name, ", ".join(capi.MOTION_IMAGES)))
+                setattr(buffers, name, int(pointers[name]) if pointers is not None else scratch.allocate(nbytes, "the %s image" % name))
+            if self.lib.render_motion_buffers(C.byref(self.app), C.byref(buffers)):
+                raise RuntimeError("render_motion_buffers failed")
+            if pointers is not None:
+                return None
+            self.sync()
+            return {name: scratch.download(getattr(buffers, name), (e.height, e.width, 4), np.float32, "the %s image" % name) for name in names}
+
     def feature_preview(self, name, image_or_pointer, range=(0.0, 1.0), out_pointer=None):
         """The RGBA8 preview of a feature image (encode_feature_preview) - an array as render_features() returns it, which
         is uploaded, or a device address.  range: (low, high) for "position" (distances) and "reprojection" (high: the
@@ -1008,7 +1043,8 @@ class Renderer(HostScene):
 
     def accumulate_history(self, colour, features, settings=None, modulation=None, out_colour=None, out_variance=None, want_variance=True, frame_history=None):
         """The temporal accumulation of include/vkr_frame_history.h.  colour and the values of features - {"position",
-        "normal"}, optionally "reprojection" (under the previous frame's matrix; without it every pixel stays where it is)
+        "normal"}, optionally "reprojection" (under the previous frame's matrix; without it every pixel stays where it is),
+        optionally "previous_position" (of render_motion(), with its reprojection: accumulate_moving_frame_history())
         and, unless `modulation` names another image, optionally "diffuse_albedo" - are device addresses or float32 arrays
         (height, width, 4), which are uploaded.  settings: the members of frame_history_settings_t that differ from
         frame_history.DEFAULT_SETTINGS.  frame_history: a create_frame_history() of the images' extent; None: one of the

@@ -264,6 +264,22 @@ def wobble(positions, t, amplitude=0.05, fixed=None, wavelength=4.0):
     return np.clip(p + d[:, None, :], flat.min(axis=0), flat.max(axis=0))
 
 
+class Wobble:
+    """The motion of the command lines: the mesh of a Renderer as it is now - at rest -, and the position words of frame
+    0, 1, ... of its wobble.  rest_words: what update_geometry() takes to put the mesh back."""
+
+    def __init__(self, scene, amplitude):
+        mesh = scene.app.scene.mesh
+        self.amplitude = amplitude
+        self.factor, self.summand = np.array(mesh.dequantization_factor[:], np.float32), np.array(mesh.dequantization_summand[:], np.float32)
+        self.rest_words = np.ctypeslib.as_array(mesh.host_positions, (3 * mesh.triangle_count, 2)).copy()
+        self.rest = ray_queries.dequantize(self.rest_words, self.factor, self.summand).astype(np.float64)
+
+    def words(self, frame):
+        codes, _ = quantize(wobble(self.rest, 0.5 * frame, self.amplitude), self.factor, self.summand)
+        return pack_positions(codes)
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
@@ -292,13 +308,9 @@ def main(argv=None):
         renderer.setup_config(r, 3, dataset, width=args.width, height=args.height)
         r.create_targets()
         r.create_pass()
-        mesh = r.app.scene.mesh
-        factor, summand = np.array(mesh.dequantization_factor[:], np.float32), np.array(mesh.dequantization_summand[:], np.float32)
-        words = np.ctypeslib.as_array(mesh.host_positions, (3 * mesh.triangle_count, 2)).copy()
-        rest = ray_queries.dequantize(words, factor, summand).astype(np.float64)
+        motion = Wobble(r, args.amplitude)
         for frame in range(args.frames):
-            codes, _ = quantize(wobble(rest, 0.5 * frame, args.amplitude), factor, summand)
-            moved = pack_positions(codes)
+            moved = motion.words(frame)
             report = r.update_geometry(moved, policy=args.policy, measure_cost=args.time, rebuild_above=args.rebuild_above)
             if args.time:
                 line = "frame %d: %s %.3f ms, cost ratio %.4f" % (frame, "rebuild" if report["rebuilt"] else "refit", report["milliseconds"], report["cost"] / report["built_cost"] if report["built_cost"] else 0.0)
